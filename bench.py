@@ -3,12 +3,20 @@
 all-reduce when N>1) over one synthetic event-tensor sequence batch.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload base_1mpx|tiny_gen1] [--dtype bf16|f32]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Both forms work for N > 1: without a launcher (`WORLD_SIZE` unset) the first form starts its N ranks itself under
-torch.distributed.run (`self_launch`).  The default N=1 line also carries `also`: BASELINE configs[1] (RVT-Tiny / Gen1
-training step) and configs[4] (streaming-inference latency) measured right after the headline run.
+torch.distributed.run (`self_launch`).
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the JSON line.  `--full` adds
+everything else, measured around the headline run: the instrumented steps behind `roofline` / `roofline_table` (and
+`--op-breakdown`, which implies `--full`), the sustained-MFMA probe, the host-enqueue probe, and at N=1 `also` (BASELINE
+configs[1], the RVT-Tiny / Gen1 training step, and configs[4], streaming-inference latency) and `cpu_baseline`.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files (see `OutputCapture`); the inputs,
+weights and cotangents are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (default): BASELINE.json configs[2] — RVT-Base, 1 Mpx shape (20x360x640 uint8, padded to 384x640
 by the model), T=21, batch=24 per GPU, bf16, random-init weights, inputs resident in HBM.
@@ -16,7 +24,7 @@ A "step" = forward_sequence over (T,B) + backward with random upstream gradients
 features of all T frames (what the FPN consumes) + fused AdamW on the backbone parameters; with N>1 the
 per-stage gradient buckets are all-reduced over RCCL, overlapped with the remaining backward.
 Metric: event-tensors/s = N*B*T / step time (weak scaling: per-GPU work fixed).
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (with `roofline` and `cpu_baseline` under `--full`).
 """
 from __future__ import annotations
 
@@ -230,6 +238,85 @@ def build_model(wl, dtype, device):
 def make_batch(wl, device, seed):
     g = torch.Generator(device=device).manual_seed(seed)      # dense random 0..10 (DVFS-honest: not zero-heavy)
     return torch.randint(0, 11, (wl['T'], wl['B'], 20, *wl['hw']), generator=g, dtype=torch.uint8, device=device)
+
+
+# --dump-outputs: an array of more than DUMP_SAMPLE elements is stored as the same DUMP_SAMPLE seeded positions of its row-major
+# flattening on every run (12 arrays of at most 4 MiB of float32 each)
+DUMP_SAMPLE = 1 << 20
+
+
+def sample_index(shape, seed, device):
+    """Index tuple of DUMP_SAMPLE fixed, seeded positions in a tensor of `shape` (sorted, row-major), or None: keep it whole."""
+    n = 1
+    for d in shape:
+        n *= d
+    if n <= DUMP_SAMPLE:
+        return None
+    flat = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return tuple(i.to(device) for i in torch.unravel_index(flat, tuple(shape)))
+
+
+def take_sample(t, index):
+    """float32 copy of `t` (whole) or of its positions `index` - own memory, so later steps cannot change it."""
+    return (t if index is None else t[index]).detach().to(torch.float32, copy=True)
+
+
+class OutputCapture:
+    """What a caller of the timed step receives from its LAST call: the features of stages 2-4 (all T frames) and the final ConvLSTM
+    states (h, c) of the four stages, sampled right after the forward (before the backward), and every parameter gradient after the
+    backward (references to the gradient buckets, which only the next backward rewrites).
+
+    That step starts from the seeded initial weights (`restore`, one multi-tensor copy): the weights the optimizer steps before it
+    leave behind differ from run to run (AdamW's normalised update turns the last-bit differences of atomically accumulated gradients
+    into whole steps of lr), so without the restore no two runs would feed that step the same inputs.  The sample positions are built
+    before the timed region; inside it the capture costs the copy and a dozen gathers in the last step."""
+
+    def __init__(self, model, geoms, T, B, device):
+        self.params = [p for _, p in model.named_parameters()]
+        self.initial = [p.detach().clone() for p in self.params]
+        self.plan = {}
+        for s in (2, 3, 4):
+            g = geoms[s - 1]
+            self.plan[f'features_stage{s}'] = (T, B, g.C, g.H, g.W)
+        for s, g in enumerate(geoms, 1):
+            self.plan[f'state_stage{s}_h'] = self.plan[f'state_stage{s}_c'] = (B, g.C, g.H, g.W)
+        self.index = {k: sample_index(shp, seed, device) for seed, (k, shp) in enumerate(self.plan.items())}
+        self.grad_total = sum(p.numel() for p in self.params)
+        self.grad_index = sample_index((self.grad_total,), len(self.plan), device)
+        self.got = self.grads = None
+
+    def restore(self):
+        with torch.no_grad():
+            torch._foreach_copy_(self.params, self.initial)
+
+    def after_forward(self, feats, states):
+        got = {f'features_stage{s}': feats[s] for s in (2, 3, 4)}
+        for s, (h, c) in enumerate(states, 1):
+            got[f'state_stage{s}_h'], got[f'state_stage{s}_c'] = h, c
+        for k, t in got.items():
+            assert tuple(t.shape) == self.plan[k], (k, tuple(t.shape), self.plan[k])
+        with torch.no_grad():
+            self.got = {k: take_sample(t, self.index[k]) for k, t in got.items()}
+
+    def after_backward(self):
+        self.grads = [p.grad for p in self.params]
+
+    def dump(self, out_dir):
+        """DIR/<name>.npy, float32: the arrays above and `grads` (every parameter gradient, flattened and concatenated in
+        named_parameters() order; zeros where a parameter got none)."""
+        import numpy as np
+        torch.cuda.synchronize()
+        arrays = dict(self.got)
+        flat = torch.cat([(g if g is not None else torch.zeros_like(p)).reshape(-1).float() for p, g in zip(self.params, self.grads)])
+        arrays['grads'] = take_sample(flat, self.grad_index)
+        os.makedirs(out_dir, exist_ok=True)
+        total = 0
+        for k, t in arrays.items():
+            a = t.cpu().numpy()
+            np.save(os.path.join(out_dir, f'{k}.npy'), a)
+            total += a.nbytes
+        assert total <= 64 * 2**20, total
+        return total
 
 
 def usable_cores() -> int:
@@ -512,7 +599,17 @@ def main():
                     help='skip the `also` object (BASELINE configs[1] and [4] measured after the headline run)')
     ap.add_argument('--tuning', action='append', default=[], metavar='FIELD=INT',
                     help='experiment only: override a field of the RvtTuning record (the line then carries config.tuning_overrides)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: roofline / per-kernel tables (instrumented steps), the '
+                         'sustained-MFMA and host-enqueue probes, and at N=1 `also` and `cpu_baseline`')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (float32; features, final states, parameter '
+                         'gradients; large arrays as a fixed seeded sample).  That step starts from the seeded initial weights, so '
+                         'the same arguments give it the same inputs on every run.  With --graph on/auto: the last step of the eager pass')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    full = args.full or bool(args.op_breakdown)       # the per-op table comes from the instrumented steps of --full
     tuning_overrides = {kv.split('=')[0]: int(kv.split('=')[1]) for kv in args.tuning}
     if tuning_overrides:
         from rvt_amd import tuning as _tuning
@@ -570,11 +667,19 @@ def main():
     cots = {s + 1: torch.randn((T, B, geoms[s].H, geoms[s].W, geoms[s].C), generator=gen, device=device,
                                dtype=dtype).permute(0, 1, 4, 2, 3) for s in (1, 2, 3)}
 
-    def step():
+    capture = OutputCapture(model, geoms, T, B, device) if args.dump_outputs and rank == 0 else None
+
+    def step(keep=False):
+        if keep:
+            capture.restore()
         feats, states = model.forward_sequence(xs, None)
+        if keep:
+            capture.after_forward(feats, states)
         torch.autograd.backward([feats[s] for s in (2, 3, 4)], [cots[s] for s in (2, 3, 4)])
         if reducer is not None:
             reducer.finish()
+        if keep:
+            capture.after_backward()
         if opt is not None:
             opt.step()
             opt.zero_grad(set_to_none=True)
@@ -590,65 +695,66 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    # which kernel dominates?  One instrumented, untimed step with HIP events around EVERY launch; groups = (entry point, problem
-    # shape), i.e. one kernel at one shape; every entry point has an algorithmic FLOP / byte model (opmodel.py), so the choice is
-    # over ALL of them (round 3 could only price GEMM-family launches)
-    # (the C-side training stage driver - route_stage_driver_train, the default - issues a stage's launches from inside ONE library
-    # call, where this per-launch timer cannot bracket them: the instrumented passes run on the Python host loop, which launches the
-    # same kernels with the same arguments in the same order, tests/test_stage_driver.py)
-    from rvt_amd import tuning as _tn
-    host_loop = dict(_tn.overrides(), route_stage_driver_train=0)
-    timer = OpTimer()
-    timer.preallocate(6000)
-    timer.install()
-    with _tn.override(**host_loop):
-        step()
-        timer.two_pass_min(step)
-    prof = timer.summary()
-    sustained = mfma_peak_sustained(device) if args.dtype == 'bf16' else None
-    groups = kernel_groups(timer.records)
-    table = [r for r in (group_roofline(k, v, args.dtype) for k, v in groups.items()) if r is not None]
-    table.sort(key=lambda r: -r['ms'])
-    dom_key = max((k for k in groups if opmodel.model(k[0], groups[k][0][2]) is not None),
-                  key=lambda k: sum(a.elapsed_time(b) for a, b, _ in groups[k]))
-    dominant = dom_key[0]
-    step_ms_instrumented = sum(v['total_ms'] for v in prof.values())
-    algorithmic_bytes_step = sum((opmodel.model(n, r[2]) or (0.0, 0.0))[1] for n, recs in timer.records.items() for r in recs)
-    algorithmic_flops_step = sum((opmodel.model(n, r[2]) or (0.0, 0.0))[0] for n, recs in timer.records.items() for r in recs)
-    executed_flops_step = sum((opmodel.executed(n, r[2]) or 0.0) for n, recs in timer.records.items() for r in recs)
-    by_entry = {}
-    for r in table:
-        e = by_entry.setdefault(r['kernel'], [0.0, 0.0, 0.0, 0, 0.0])
-        e[0] += r['ms']; e[1] += r['algorithmic_gflop']; e[2] += r['algorithmic_gbyte']; e[3] += r['launches']
-        e[4] += r.get('executed_gflop', r['algorithmic_gflop'])
-    entry_table = [opmodel.roofline_entry(n, e[1] * 1e9, e[2] * 1e9, e[0], e[3], args.dtype, executed_flops=e[4] * 1e9) for n, e in
-                   sorted(by_entry.items(), key=lambda kv: -kv[1][0])[:10]]
-    if args.op_breakdown and rank == 0:
-        with open(args.op_breakdown, 'w') as f:
-            tot = sum(v['total_ms'] for v in prof.values())
-            f.write(f'# per-op HIP-event time of ONE step ({wl["label"]}, {args.dtype}); sum = {tot:.2f} ms\n')
-            for n, v in sorted(prof.items(), key=lambda kv: -kv[1]['total_ms']):
-                f.write(f'{n:28s} calls={v["calls"]:5d} total={v["total_ms"]:9.3f} ms avg={v["avg_ms"]:8.4f} ms max={v["max_ms"]:8.4f} ms '
-                        f'({100 * v["total_ms"] / tot:5.1f} %)\n')
-            f.write('# by (op, integer args after the pointers) — which stage / shape the time goes to\n')
-            by = {}
-            for n, recs in timer.records.items():
-                for a, b, ar in recs:
-                    key = (n, tuple(x for x in ar if isinstance(x, int) and not isinstance(x, bool) and 0 <= x < (1 << 31))[-8:])
-                    e = by.setdefault(key, [0, 0.0])
-                    e[0] += 1
-                    e[1] += a.elapsed_time(b)
-            for (n, key), (cnt, ms) in sorted(by.items(), key=lambda kv: -kv[1][1])[:60]:
-                f.write(f'{n:28s} {str(key):60s} calls={cnt:4d} total={ms:9.3f} ms\n')
-    timer.records.clear()
-    timer.enabled_for = {dominant}
-    top_table = table[:12]
-    # two more untimed steps: the instrumented step above perturbs the caching allocator's stream-tagged pools (the
-    # weight-gradient side stream), and a timed region that still grows the pool pays hipMalloc inside it
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    timer.records.clear()
+    if full:
+        # which kernel dominates?  One instrumented, untimed step with HIP events around EVERY launch; groups = (entry point, problem
+        # shape), i.e. one kernel at one shape; every entry point has an algorithmic FLOP / byte model (opmodel.py), so the choice is
+        # over ALL of them (round 3 could only price GEMM-family launches)
+        # (the C-side training stage driver - route_stage_driver_train, the default - issues a stage's launches from inside ONE library
+        # call, where this per-launch timer cannot bracket them: the instrumented passes run on the Python host loop, which launches the
+        # same kernels with the same arguments in the same order, tests/test_stage_driver.py)
+        from rvt_amd import tuning as _tn
+        host_loop = dict(_tn.overrides(), route_stage_driver_train=0)
+        timer = OpTimer()
+        timer.preallocate(6000)
+        timer.install()
+        with _tn.override(**host_loop):
+            step()
+            timer.two_pass_min(step)
+        prof = timer.summary()
+        sustained = mfma_peak_sustained(device) if args.dtype == 'bf16' else None
+        groups = kernel_groups(timer.records)
+        table = [r for r in (group_roofline(k, v, args.dtype) for k, v in groups.items()) if r is not None]
+        table.sort(key=lambda r: -r['ms'])
+        dom_key = max((k for k in groups if opmodel.model(k[0], groups[k][0][2]) is not None),
+                      key=lambda k: sum(a.elapsed_time(b) for a, b, _ in groups[k]))
+        dominant = dom_key[0]
+        step_ms_instrumented = sum(v['total_ms'] for v in prof.values())
+        algorithmic_bytes_step = sum((opmodel.model(n, r[2]) or (0.0, 0.0))[1] for n, recs in timer.records.items() for r in recs)
+        algorithmic_flops_step = sum((opmodel.model(n, r[2]) or (0.0, 0.0))[0] for n, recs in timer.records.items() for r in recs)
+        executed_flops_step = sum((opmodel.executed(n, r[2]) or 0.0) for n, recs in timer.records.items() for r in recs)
+        by_entry = {}
+        for r in table:
+            e = by_entry.setdefault(r['kernel'], [0.0, 0.0, 0.0, 0, 0.0])
+            e[0] += r['ms']; e[1] += r['algorithmic_gflop']; e[2] += r['algorithmic_gbyte']; e[3] += r['launches']
+            e[4] += r.get('executed_gflop', r['algorithmic_gflop'])
+        entry_table = [opmodel.roofline_entry(n, e[1] * 1e9, e[2] * 1e9, e[0], e[3], args.dtype, executed_flops=e[4] * 1e9) for n, e in
+                       sorted(by_entry.items(), key=lambda kv: -kv[1][0])[:10]]
+        if args.op_breakdown and rank == 0:
+            with open(args.op_breakdown, 'w') as f:
+                tot = sum(v['total_ms'] for v in prof.values())
+                f.write(f'# per-op HIP-event time of ONE step ({wl["label"]}, {args.dtype}); sum = {tot:.2f} ms\n')
+                for n, v in sorted(prof.items(), key=lambda kv: -kv[1]['total_ms']):
+                    f.write(f'{n:28s} calls={v["calls"]:5d} total={v["total_ms"]:9.3f} ms avg={v["avg_ms"]:8.4f} ms max={v["max_ms"]:8.4f} ms '
+                            f'({100 * v["total_ms"] / tot:5.1f} %)\n')
+                f.write('# by (op, integer args after the pointers) — which stage / shape the time goes to\n')
+                by = {}
+                for n, recs in timer.records.items():
+                    for a, b, ar in recs:
+                        key = (n, tuple(x for x in ar if isinstance(x, int) and not isinstance(x, bool) and 0 <= x < (1 << 31))[-8:])
+                        e = by.setdefault(key, [0, 0.0])
+                        e[0] += 1
+                        e[1] += a.elapsed_time(b)
+                for (n, key), (cnt, ms) in sorted(by.items(), key=lambda kv: -kv[1][1])[:60]:
+                    f.write(f'{n:28s} {str(key):60s} calls={cnt:4d} total={ms:9.3f} ms\n')
+        timer.records.clear()
+        timer.enabled_for = {dominant}
+        top_table = table[:12]
+        # two more untimed steps: the instrumented step above perturbs the caching allocator's stream-tagged pools (the
+        # weight-gradient side stream), and a timed region that still grows the pool pays hipMalloc inside it
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        timer.records.clear()
 
     # a full (generation-2) Python GC pass over the module / autograd object graph takes 30-90 ms and lands inside one
     # step in three (seen as one 47-110 ms step among 16.6 ms ones on the Tiny workload): collect now and move the
@@ -657,14 +763,15 @@ def main():
     gc.collect()
     gc.freeze()
 
-    def timed_region(fn):
+    def timed_region(fn, last=None):
+        """K steps of `fn` (the last one `last`, when given) between two barriers: wall time, host time, per-step GPU times."""
         barrier()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         e0.record()
         marks = []
-        for _ in range(args.steps):
-            fn()
+        for i in range(args.steps):
+            (last if last is not None and i == args.steps - 1 else fn)()
             m = torch.cuda.Event(enable_timing=True)
             m.record()
             marks.append(m)
@@ -674,34 +781,39 @@ def main():
         wall_ = time.perf_counter() - t0
         return wall_, host, [a.elapsed_time(b) for a, b in zip([e0] + marks[:-1], marks)]
 
-    # host cost of enqueueing ONE step into an empty queue (the K-step region below measures something else on the host side:
-    # with ~800 launches per step the HIP queue fills up and the host blocks on the GPU, so its host time approaches the GPU time)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    step()
-    host_one_step = time.perf_counter() - t0
-    torch.cuda.synchronize()
-    timer.records.clear()
-
-    # eager pass: EXACTLY K steps on the production route (C-side stage drivers): the headline timing unless the graph replay below runs.
-    timer.uninstall()
-    if reducer is not None:
-        reducer.tail_ms()                             # (drop the warm-up steps' records)
-    wall, host_enqueue, per_step = timed_region(step)
-    eager_ms = 1e3 * wall / args.steps
-    tails = reducer.tail_ms() if reducer is not None else []
-    # the `roofline` measurement: K more steps with HIP events around every launch of the dominant entry point, on the stream it is
-    # launched on - on the Python host loop (same kernels, same arguments), because the stage driver hides the individual launches
-    timer.install()
-    with _tn.override(**host_loop):
+    if full:
+        # host cost of enqueueing ONE step into an empty queue (the K-step region below measures something else on the host side:
+        # with ~800 launches per step the HIP queue fills up and the host blocks on the GPU, so its host time approaches the GPU time)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
         step()
+        host_one_step = time.perf_counter() - t0
         torch.cuda.synchronize()
         timer.records.clear()
-        roof_wall, _, _ = timed_region(step)
-    timer.uninstall()
-    roof_pass_ms = 1e3 * roof_wall / args.steps
+        timer.uninstall()
+
+    # eager pass: EXACTLY K steps on the production route (C-side stage drivers): the headline timing unless the graph replay below runs.
     if reducer is not None:
-        reducer.tail_ms()
+        reducer.tail_ms()                             # (drop the warm-up steps' records)
+    wall, host_enqueue, per_step = timed_region(step, last=(lambda: step(keep=True)) if capture is not None else None)
+    eager_ms = 1e3 * wall / args.steps
+    tails = reducer.tail_ms() if reducer is not None else []
+    if capture is not None:
+        nbytes = capture.dump(args.dump_outputs)
+        print(f'[bench] outputs of the last timed step: {nbytes / 2**20:.1f} MiB of float32 in {args.dump_outputs}', file=sys.stderr, flush=True)
+    if full:
+        # the `roofline` measurement: K more steps with HIP events around every launch of the dominant entry point, on the stream it is
+        # launched on - on the Python host loop (same kernels, same arguments), because the stage driver hides the individual launches
+        timer.install()
+        with _tn.override(**host_loop):
+            step()
+            torch.cuda.synchronize()
+            timer.records.clear()
+            roof_wall, _, _ = timed_region(step)
+        timer.uninstall()
+        roof_pass_ms = 1e3 * roof_wall / args.steps
+        if reducer is not None:
+            reducer.tail_ms()
     graph_note = 'off'
     if use_graph:
         # the same K steps replayed as ONE captured hipGraph per step (no Python, no per-kernel launch cost)
@@ -716,13 +828,14 @@ def main():
             graph_note = f'failed: {type(e).__name__}: {str(e)[:120]}'
             print(f'[bench] hipGraph capture failed, reporting the eager timing: {e}', file=sys.stderr, flush=True)
     if rank == 0:
+        host_note = (f'host_enqueue_ms_per_step={1e3 * host_one_step:.1f} (empty queue; {1e3 * host_enqueue / args.steps:.1f} inside the '
+                     f'timed region, where the host blocks on a full queue)' if full else
+                     f'host_ms_per_step_in_timed_region={1e3 * host_enqueue / args.steps:.1f}')
         print(f'[bench] per-step ms: {[round(x, 1) for x in per_step]}  reserved={torch.cuda.memory_reserved() / 2**30:.1f} GiB '
               f'peak_alloc={torch.cuda.max_memory_allocated() / 2**30:.1f} GiB '
               f'alloc_retries={torch.cuda.memory_stats().get("num_alloc_retries", 0)} '
-              f'host_enqueue_ms_per_step={1e3 * host_one_step:.1f} (empty queue; {1e3 * host_enqueue / args.steps:.1f} inside the timed region, '
-              f'where the host blocks on a full queue) eager_ms_per_step={eager_ms:.1f} '
+              f'{host_note} eager_ms_per_step={eager_ms:.1f} '
               f'graph={graph_note}', file=sys.stderr, flush=True)
-    timer.uninstall()
     dist_info = None
     if world > 1 or args.force_reducer:
         # what RCCL itself sees, every rank's own clock, and the part of the gradient exchange the backward did not hide
@@ -743,26 +856,8 @@ def main():
     events_per_s = world * B * T / (wall / args.steps)
 
     if rank == 0:
-        # roofline of the dominant kernel (entry point at one problem shape): algorithmic FLOPs / bytes of its launches inside the
-        # timed region / the HIP-event time of the same launches
         peak = PEAK_TFLOPS[args.dtype]
         path_tflops = events_per_s / world * wl['f_fwdbwd'] / 1e12
-        recs = [r for r in timer.records[dominant] if shape_key(r[2]) == dom_key[1]]
-        roof = group_roofline(dom_key, recs, args.dtype)
-        wkey = f'{args.workload}:{args.dtype}:B{B}:T{T}'
-        dom_ms = roof['ms']
-        ordered = {k: roof[k] for k in ('bound', 'achieved', 'peak', 'unit', 'frac')}
-        ordered['traffic'] = traffic_lookup(wkey, dom_key)
-        ordered.update({k: v for k, v in roof.items() if k not in ordered})
-        ordered.update({'algorithmic_bytes_per_launch': int(roof['algorithmic_gbyte'] * 1e9 / max(len(recs), 1)),
-                        'share_of_step': round(dom_ms / (roof_pass_ms * args.steps), 3),
-                        'timing': 'HIP events on the launch stream around every launch of this kernel, inside a timed region of K steps that '
-                                  'follows the headline region and runs the Python host loop (route_stage_driver_train = 0: same kernels, same '
-                                  f'arguments; {roof_pass_ms:.3f} ms per step) - the C-side stage driver of the headline region issues a stage\'s '
-                                  'launches inside one library call, where they cannot be bracketed',
-                        'chosen_as': 'largest total time of one (entry point, problem shape) group over ALL entry points '
-                                     '(instrumented step; opmodel.py prices every entry point)'})
-        roof = ordered
         out = {
             'metric': 'event-tensors/sec (fwd+bwd) RVT-Base T=21 1Mpx; % MFMA roofline' if args.workload == 'base_1mpx'
             else 'event-tensors/sec (fwd+bwd)',
@@ -772,44 +867,64 @@ def main():
             'config': {'workload': wl['label'], 'global_batch': world * B, 'seq_len': T,
                        'parallelism': f'dp{world}', 'optimizer': 'none' if opt is None else 'AdamW(fused)',
                        'hipgraph': graph_note, 'eager_ms_per_step': round(eager_ms, 3),
-                       'host_enqueue_ms_per_step': round(1e3 * host_one_step, 2),
+                       **({'host_enqueue_ms_per_step': round(1e3 * host_one_step, 2)} if full else {}),
                        'host_ms_per_step_in_timed_region': round(1e3 * host_enqueue / args.steps, 2),
                        'upstream_grads': 'random cotangents on stage 2-4 features of all T frames',
                        **({'tuning_overrides': tuning_overrides} if tuning_overrides else {})},
             'mfma_roofline_frac_whole_step': round(path_tflops / peak, 4),
             'algorithmic_tflops_per_gpu': round(path_tflops, 2),
-            'roofline': roof,
-            # the 12 heaviest kernels (entry point at one shape) and the 10 heaviest entry points of ONE instrumented step
-            # (HIP events around every launch, one stream, untimed): ms, algorithmic GFLOP / GB, which roof binds, fraction of it
-            'roofline_table': top_table,
-            'roofline_entry_points': entry_table,
-            'instrumented_step_ms': round(step_ms_instrumented, 3),
-            'instrumented_step_note': 'sum over launches of min(duration in pass 1, duration in pass 2) of two instrumented steps: a lower '
-                                      'envelope, not comparable with eager_ms_per_step (a mean over K un-instrumented steps)',
-            'hbm_traffic_per_step': {'measured_bytes': step_traffic(wkey), 'source': 'profiles/latest_traffic.json (rocprofv3 FETCH_SIZE x2 + '
-                                     'WRITE_SIZE passes of this command), null when no pass of THIS workload is committed',
-                                     # what the launches of one step move if every operand / result crosses HBM exactly once (opmodel.py, sum
-                                     # over the instrumented step) and what a fully fused stage-by-stage path would (19.4 MB per
-                                     # event tensor forward, x3 for forward + backward)
-                                     'algorithmic_gbyte_per_step': round(algorithmic_bytes_step / 1e9, 2),
-                                     'fused_minimum_gbyte_per_step': round(19.4e6 * B * T * 3 / 1e9, 2) if args.workload == 'base_1mpx' else None},
-            'flops_per_step': {'algorithmic_gflop_of_the_launches': round(algorithmic_flops_step / 1e9, 1),
-                               'executed_gflop_incl_recompute': round(executed_flops_step / 1e9, 1),
-                               'survey_8d_gflop': round(wl['f_fwdbwd'] * B * T / 1e9, 1)},
-            'mfma_peak_sustained': None if not sustained else {
-                'tflops': round(sustained, 1), 'implied_clock_ghz': round(sustained * 1e12 / (256 * 4096) / 1e9, 3),
-                'whole_step_frac_of_sustained': round(path_tflops / sustained, 4),
-                'method': 'rvt_probe_mfma: 4096 workgroups of nothing but independent v_mfma_f32_32x32x16_bf16, HIP-event timed'},
         }
+        if full:
+            # roofline of the dominant kernel (entry point at one problem shape): algorithmic FLOPs / bytes of its launches inside the
+            # timed region / the HIP-event time of the same launches
+            recs = [r for r in timer.records[dominant] if shape_key(r[2]) == dom_key[1]]
+            roof = group_roofline(dom_key, recs, args.dtype)
+            wkey = f'{args.workload}:{args.dtype}:B{B}:T{T}'
+            dom_ms = roof['ms']
+            ordered = {k: roof[k] for k in ('bound', 'achieved', 'peak', 'unit', 'frac')}
+            ordered['traffic'] = traffic_lookup(wkey, dom_key)
+            ordered.update({k: v for k, v in roof.items() if k not in ordered})
+            ordered.update({'algorithmic_bytes_per_launch': int(roof['algorithmic_gbyte'] * 1e9 / max(len(recs), 1)),
+                            'share_of_step': round(dom_ms / (roof_pass_ms * args.steps), 3),
+                            'timing': 'HIP events on the launch stream around every launch of this kernel, inside a timed region of K steps that '
+                                      'follows the headline region and runs the Python host loop (route_stage_driver_train = 0: same kernels, same '
+                                      f'arguments; {roof_pass_ms:.3f} ms per step) - the C-side stage driver of the headline region issues a stage\'s '
+                                      'launches inside one library call, where they cannot be bracketed',
+                            'chosen_as': 'largest total time of one (entry point, problem shape) group over ALL entry points '
+                                         '(instrumented step; opmodel.py prices every entry point)'})
+            out.update({
+                'roofline': ordered,
+                # the 12 heaviest kernels (entry point at one shape) and the 10 heaviest entry points of ONE instrumented step
+                # (HIP events around every launch, one stream, untimed): ms, algorithmic GFLOP / GB, which roof binds, fraction of it
+                'roofline_table': top_table,
+                'roofline_entry_points': entry_table,
+                'instrumented_step_ms': round(step_ms_instrumented, 3),
+                'instrumented_step_note': 'sum over launches of min(duration in pass 1, duration in pass 2) of two instrumented steps: a lower '
+                                          'envelope, not comparable with eager_ms_per_step (a mean over K un-instrumented steps)',
+                'hbm_traffic_per_step': {'measured_bytes': step_traffic(wkey), 'source': 'profiles/latest_traffic.json (rocprofv3 FETCH_SIZE x2 + '
+                                         'WRITE_SIZE passes of this command), null when no pass of THIS workload is committed',
+                                         # what the launches of one step move if every operand / result crosses HBM exactly once (opmodel.py, sum
+                                         # over the instrumented step) and what a fully fused stage-by-stage path would (19.4 MB per
+                                         # event tensor forward, x3 for forward + backward)
+                                         'algorithmic_gbyte_per_step': round(algorithmic_bytes_step / 1e9, 2),
+                                         'fused_minimum_gbyte_per_step': round(19.4e6 * B * T * 3 / 1e9, 2) if args.workload == 'base_1mpx' else None},
+                'flops_per_step': {'algorithmic_gflop_of_the_launches': round(algorithmic_flops_step / 1e9, 1),
+                                   'executed_gflop_incl_recompute': round(executed_flops_step / 1e9, 1),
+                                   'survey_8d_gflop': round(wl['f_fwdbwd'] * B * T / 1e9, 1)},
+                'mfma_peak_sustained': None if not sustained else {
+                    'tflops': round(sustained, 1), 'implied_clock_ghz': round(sustained * 1e12 / (256 * 4096) / 1e9, 3),
+                    'whole_step_frac_of_sustained': round(path_tflops / sustained, 4),
+                    'method': 'rvt_probe_mfma: 4096 workgroups of nothing but independent v_mfma_f32_32x32x16_bf16, HIP-event timed'},
+            })
         if dist_info is not None:
             out['distributed'] = dist_info
-        if world == 1 and args.workload == 'base_1mpx' and not args.no_also and not (args.batch or args.seq):
+        if full and world == 1 and args.workload == 'base_1mpx' and not args.no_also and not (args.batch or args.seq):
             del xs, cots
             model = opt = params = None
             gc.collect()
             torch.cuda.empty_cache()
             out['also'] = also_configs(args.dtype, device, args)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.workload)
         print(json.dumps(out), flush=True)
     if world > 1 or args.force_reducer:

@@ -13,7 +13,7 @@ done 2>&1 | tee $OUT/microbench.txt
 for rep in 1 2; do
 for v in base new; do
   if [ $v = base ]; then export RVT_HIP_LIB=$ROOT/rvt_amd/librvt_hip_$SUF.so; else unset RVT_HIP_LIB; fi
-  timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-also --op-breakdown $OUT/op_$v.txt > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err
+  timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-also --op-breakdown $OUT/op_$v.txt > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err
   python -c "
 import json
 d=json.loads([l for l in open('$OUT/bench_${v}_$rep.json') if l.startswith('{')][-1]); print('$v', $rep, d['ms_per_step'], d['value'])"

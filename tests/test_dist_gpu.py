@@ -72,9 +72,9 @@ def test_bench_gpus2_self_launch_reports_missing_device():
 
 
 def test_bench_default_line_carries_also_configs():
-    """The N=1 headline line carries BASELINE configs[1] and configs[4] under `also` (driver-visible)."""
+    """The N=1 `--full` line carries BASELINE configs[1] and configs[4] under `also` (driver-visible)."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--full'],
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -82,3 +82,27 @@ def test_bench_default_line_carries_also_configs():
     assert also['tiny_gen1']['value'] > 0 and also['tiny_gen1']['ms_per_step'] > 0, also
     assert also['stream_latency']['p50'] > 0 and also['stream_latency']['p99'] >= also['stream_latency']['p50'], also
     assert line['roofline']['frac'] < 1 and line['n_gpus'] == 1
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run carries the headline fields only (no instrumented steps, `also` or `cpu_baseline`), and --dump-outputs writes
+    the last timed step's features, final states and parameter gradients as float32 .npy files within 64 MiB."""
+    import json
+    import numpy as np
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['steps'] == 2 and line['ms_per_step'] > 0 and line['value'] > 0 and line['dtype'] == 'bf16', line
+    assert line['higher_is_better'] is True and line['unit'] == 'event-tensors/s'
+    assert not {'roofline', 'roofline_table', 'also', 'cpu_baseline'} & set(line), sorted(line)
+    names = sorted(f.name for f in out.iterdir())
+    assert names == sorted(['features_stage2.npy', 'features_stage3.npy', 'features_stage4.npy', 'grads.npy'] +
+                           [f'state_stage{s}_{k}.npy' for s in range(1, 5) for k in 'hc']), names
+    total = 0
+    for f in out.iterdir():
+        a = np.load(f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all() and np.abs(a).max() > 0, f.name
+        total += f.stat().st_size
+    assert total <= 64 * 2**20, total

@@ -334,128 +334,107 @@ def test_default_gradient_handoff_obeys_autograd_contracts():
 
 
 DROPIN_WORKER = r'''
-# The drop-in claim of INTEGRATION.md section 1, executed: the reference's OWN detector class is built with the registry branch
-# a maintainer would add, gets rvt_amd.RNNDetector as its backbone, loads a reference state_dict strictly, and
-# YoloXDetector.forward_backbone is compared with the unmodified reference backbone over a short sequence with carried states.
+# The drop-in claim of INTEGRATION.md section 1, executed: a detector with the reference YoloXDetector's layout (backbone / fpn /
+# yolox_head, detector.py:18-41) whose three parts come from the registry branches a maintainer would add (INTEGRATION.md sections
+# 1, 5 and 6) loads the reference detector's state_dict names strictly, and its forward_backbone over a short sequence with carried
+# states, its detections, losses and feature gradients are compared with the reference's own detector, recorded with the same seeded
+# weights and inputs in tests/golden/dropin_detector.npz (oracle/make_golden_dropin.py).
 import os, sys
 sys.dont_write_bytecode = True
 root = sys.argv[1]
-sys.path.insert(0, os.path.join(root, 'oracle', '_stubs'))     # omegaconf / strenum / torchvision stand-ins (not installed here)
-sys.path.insert(1, '/root/reference')
-sys.path.insert(2, root)
+sys.path.insert(0, os.path.join(root, 'oracle', '_stubs'))     # omegaconf stand-in (not installed here)
+sys.path.insert(1, root)
+import numpy as np
 import torch
 import torch.nn.functional as F
 torch.set_num_threads(4)
 from omegaconf import OmegaConf
-import models.detection.recurrent_backbone as registry
-import models.detection.yolox_extension.models.detector as detector_mod
-from models.detection.yolox_extension.models.detector import YoloXDetector
 import rvt_amd
 from rvt_amd import _lib, tuning
+from rvt_amd.fpn import build_yolox_fpn
+from rvt_amd.head import build_yolox_head
+from tests import casegen_dropin as cg
 from tests.backends import emu_library
 tuning.use(**tuning.TEST_GEOMETRY)
-_lib._install_test_library(emu_library())          # CPU SIMT-emulator build of the HIP kernels (tests only; no GPU in this container)
+_lib._install_test_library(emu_library())          # CPU SIMT-emulator build of the HIP kernels (tests only)
 
-reference_builder = registry.build_recurrent_backbone
-def build_recurrent_backbone(backbone_cfg):          # == the branch of INTEGRATION.md section 1
-    if backbone_cfg.name == 'MaxViTRNN' and backbone_cfg.get('impl', 'torch') == 'mi355x':
-        return rvt_amd.RNNDetector(backbone_cfg, compute_dtype=torch.float32)
-    return reference_builder(backbone_cfg)
-detector_mod.build_recurrent_backbone = build_recurrent_backbone     # (detector.py:11 binds the name at import)
-reference_fpn_builder = detector_mod.build_yolox_fpn
-def build_yolox_fpn(fpn_cfg, in_channels):           # == the branch of INTEGRATION.md section 5 (yolox_extension/models/build.py:21-29)
-    if fpn_cfg.get('impl', 'torch') == 'mi355x':
-        from rvt_amd.fpn import build_yolox_fpn as ours
-        return ours({k: v for k, v in fpn_cfg.items() if k != 'impl'}, in_channels, compute_dtype=torch.float32)
-    return reference_fpn_builder(OmegaConf.create({k: v for k, v in fpn_cfg.items() if k != 'impl'}), in_channels)
-detector_mod.build_yolox_fpn = build_yolox_fpn
-reference_head_builder = detector_mod.build_yolox_head
-def build_yolox_head(head_cfg, in_channels, strides):  # == the branch of INTEGRATION.md section 6 (yolox_extension/models/build.py:9-18)
-    if head_cfg.get('impl', 'torch') == 'mi355x':
-        from rvt_amd.head import build_yolox_head as ours
-        return ours({k: v for k, v in head_cfg.items() if k != 'impl'}, in_channels, strides, compute_dtype=torch.float32)
-    return reference_head_builder(OmegaConf.create({k: v for k, v in head_cfg.items() if k != 'impl'}), in_channels, strides)
-detector_mod.build_yolox_head = build_yolox_head
 
-def model_cfg(impl):
-    return OmegaConf.create({
-        'backbone': {'name': 'MaxViTRNN', 'impl': impl, 'compile': {'enable': False, 'args': {'mode': 'reduce-overhead'}},
-                     'input_channels': 20, 'enable_masking': False, 'partition_split_32': 1, 'embed_dim': 32,
-                     'dim_multiplier': [1, 2, 4, 8], 'num_blocks': [1, 1, 1, 1], 'T_max_chrono_init': [4, 8, 16, 32],
-                     'stem': {'patch_size': 4}, 'in_res_hw': [64, 96],
-                     'stage': {'downsample': {'type': 'patch', 'overlap': True, 'norm_affine': True},
-                               'attention': {'use_torch_mha': False, 'partition_size': [2, 3], 'dim_head': 32,
-                                             'attention_bias': True, 'mlp_activation': 'gelu', 'mlp_gated': False,
-                                             'mlp_bias': True, 'mlp_ratio': 4, 'drop_mlp': 0, 'drop_path': 0,
-                                             'ls_init_value': 1e-5},
-                               'lstm': {'dws_conv': False, 'dws_conv_only_hidden': True, 'dws_conv_kernel_size': 3,
-                                        'drop_cell_update': 0}}},
-        'fpn': {'name': 'PAFPN', 'impl': impl, 'compile': {'enable': False, 'args': {'mode': 'reduce-overhead'}}, 'depth': 0.67,
-                'in_stages': [2, 3, 4], 'depthwise': False, 'act': 'silu'},
-        'head': {'name': 'YoloX', 'impl': impl, 'compile': {'enable': False, 'args': {'mode': 'reduce-overhead'}}, 'depthwise': False,
-                 'act': 'silu', 'num_classes': 3},
-    })
+class Detector(torch.nn.Module):
+    # YoloXDetector's parts and calls, each part built by its `impl: mi355x` registry branch
+    def __init__(self, cfg):
+        super().__init__()
+        assert cfg.backbone.name == 'MaxViTRNN' and cfg.backbone.get('impl', 'torch') == 'mi355x'
+        self.backbone = rvt_amd.RNNDetector(cfg.backbone, compute_dtype=torch.float32)
+        in_channels = self.backbone.get_stage_dims(cfg.fpn.in_stages)
+        strides = self.backbone.get_strides(cfg.fpn.in_stages)
+        self.fpn = build_yolox_fpn({k: v for k, v in cfg.fpn.items() if k != 'impl'}, in_channels, compute_dtype=torch.float32)
+        self.yolox_head = build_yolox_head({k: v for k, v in cfg.head.items() if k != 'impl'}, in_channels, strides,
+                                           compute_dtype=torch.float32)
 
-torch.manual_seed(0)
-ref = YoloXDetector(model_cfg('torch')).eval()
-ours = YoloXDetector(model_cfg('mi355x')).eval()
-assert type(ours.backbone).__module__.startswith('rvt_amd'), type(ours.backbone)
-assert type(ref.backbone).__module__.startswith('models.detection'), type(ref.backbone)
-g = torch.Generator().manual_seed(5)
-with torch.no_grad():                                # LayerScale 1e-5 would hide the attention / MLP branches
-    for n, p in ref.named_parameters():
-        if n.endswith('.gamma'):
-            p.copy_(0.5 + torch.rand(p.shape, generator=g))
-missing = ours.load_state_dict(ref.state_dict(), strict=True)          # the WHOLE detector: backbone + FPN + head names agree
+    def forward_backbone(self, x, previous_states=None):
+        return self.backbone(x, previous_states)
+
+    def forward_detect(self, backbone_features, targets=None):
+        fpn_features = self.fpn(backbone_features)
+        if self.training:
+            return self.yolox_head(fpn_features, targets)
+        return self.yolox_head(fpn_features)
+
+
+gold = np.load(os.path.join(root, 'tests', 'golden', cg.GOLDEN + '.npz'))
+ours = Detector(OmegaConf.create(cg.model_cfg('mi355x'))).eval()
+sd = ours.state_dict()
+names = [str(n) for n in gold['names']]
+assert sorted(sd) == sorted(names), 'state_dict names differ from the reference detector'
+shapes = dict(zip(names, (str(x) for x in gold['shapes'])))
+assert all(','.join(map(str, t.shape)) == shapes[n] for n, t in sd.items()), 'state_dict shapes differ from the reference detector'
+assert [n for n in sd if n.startswith('fpn.')] == [n for n in names if n.startswith('fpn.')]   # OUR PAFPN, in the reference's order
+ints = {n[4:]: gold[n] for n in gold.files if n.startswith('int:')}
+missing = ours.load_state_dict(cg.seeded_state(sd, ints), strict=True)      # the WHOLE detector: backbone + FPN + head
 assert not missing.missing_keys and not missing.unexpected_keys
-assert type(ours.fpn).__module__.startswith('rvt_amd'), type(ours.fpn)  # ... and OUR PAFPN (rvt_amd/fpn.py) sits between backbone and head
-assert list(ours.fpn.state_dict()) == list(ref.fpn.state_dict())      # FPN / head were built from OUR get_stage_dims / get_strides
-xs = torch.randint(0, 11, (3, 2, 20, 60, 90), generator=g, dtype=torch.uint8)
-st_r = st_o = None
+assert type(ours.fpn).__module__.startswith('rvt_amd') and type(ours.yolox_head).__module__.startswith('rvt_amd')
+
+
+def rel(a, ref):
+    ref = torch.from_numpy(np.asarray(ref))
+    assert tuple(a.shape) == tuple(ref.shape), (tuple(a.shape), tuple(ref.shape))
+    return (a.detach().float() - ref).abs().max().item() / ref.abs().max().item()
+
+
+xs = cg.make_inputs()
+st_o = None
 with torch.no_grad():
-    for t in range(3):
-        x = F.pad(xs[t].float(), [0, 6, 0, 4])                          # modules/detection.py:133-134
-        fr, st_r = ref.forward_backbone(x, st_r)
-        fo, st_o = ours.forward_backbone(x, st_o)
-        assert sorted(fo) == sorted(fr) == [1, 2, 3, 4]
-        for s in fr:
-            assert tuple(fo[s].shape) == tuple(fr[s].shape)
-            err = (fo[s].float() - fr[s]).abs().max().item() / fr[s].abs().max().item()
+    for t in range(xs.shape[0]):
+        fo, st_o = ours.forward_backbone(F.pad(xs[t].float(), [0, 6, 0, 4]), st_o)     # modules/detection.py:133-134
+        assert sorted(fo) == [1, 2, 3, 4]
+        for s in fo:
+            err = rel(fo[s], gold[f'feat_t{t}_s{s}'])
             assert err < 1e-3, (t, s, err)
-        for (ho, co), (hr, cr) in zip(st_o, st_r):
-            assert (co.float() - cr).abs().max().item() <= 1e-3 * cr.abs().max().item()
+    for i, (ho, co) in enumerate(st_o):
+        assert rel(ho, gold[f'h{i}']) < 1e-3 and rel(co, gold[f'c{i}']) <= 1e-3, i
     # OUR PAFPN + OUR head (HIP kernels, eval-mode BatchNorm) consume OUR features (eval: decoded predictions)
-    assert type(ours.yolox_head).__module__.startswith('rvt_amd'), type(ours.yolox_head)
     out_o, _ = ours.forward_detect(backbone_features=fo)
-    out_r, _ = ref.forward_detect(backbone_features=fr)
-    assert out_o.shape == out_r.shape
-    assert (out_o - out_r).abs().max().item() <= 2e-3 * out_r.abs().max().item()
-# training mode through the reference detector's forward_detect: targets -> OUR batched on-device SimOTA + losses vs the reference's
-# per-image loop (yolo_head.py:291-606); same assignment, same losses, same gradient into the backbone features
-targets = torch.zeros(2, 4, 5)
-targets[0, 0] = torch.tensor([1., 30., 20., 24., 18.]); targets[0, 1] = torch.tensor([0., 70., 44., 30., 28.])
-targets[1, 0] = torch.tensor([2., 50., 30., 60., 40.])
-ref.train(); ours.train()
-fr_g = {s: v.detach().clone().requires_grad_(True) for s, v in fr.items()}
-fo_g = {s: v.detach().float().clone().requires_grad_(True) for s, v in fr.items()}       # the SAME features into both necks
-out_r, loss_r = ref.forward_detect(backbone_features=fr_g, targets=targets)
-out_o, loss_o = ours.forward_detect(backbone_features=fo_g, targets=targets)
-assert sorted(loss_o) == sorted(loss_r)
+    assert rel(out_o, gold['detections']) <= 2e-3
+# training mode: targets -> OUR batched on-device SimOTA + losses against the reference's per-image loop (yolo_head.py:291-606) on the
+# reference's own last-step features: same losses, same gradient into the backbone features
+ours.train()
+fo_g = {s: torch.from_numpy(gold[f'feat_t{xs.shape[0] - 1}_s{s}']).clone().requires_grad_(True) for s in (1, 2, 3, 4)}
+_, loss_o = ours.forward_detect(backbone_features=fo_g, targets=cg.make_targets())
+assert sorted(loss_o) == sorted(n[5:] for n in gold.files if n.startswith('loss:'))
 for k in ('loss', 'iou_loss', 'conf_loss', 'cls_loss', 'num_fg'):
-    a, b = float(loss_o[k]), float(loss_r[k])
+    a, b = float(loss_o[k]), float(gold['loss:' + k])
     assert abs(a - b) <= 2e-3 * max(abs(b), 1e-6), (k, a, b)
-loss_r['loss'].backward(); loss_o['loss'].backward()
+loss_o['loss'].backward()
 for s in (2, 3, 4):
-    err = (fo_g[s].grad - fr_g[s].grad).abs().max().item() / fr_g[s].grad.abs().max().item()
+    err = rel(fo_g[s].grad, gold[f'feat_grad_s{s}'])
     assert err < 2e-3, (s, err)
 print('DROPIN OK')
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/models'), reason='the reference tree exists only in the authoring container')
 def test_dropin_through_reference_registry_and_detector(tmp_path):
-    """VERDICT r3 item 9 / SURVEY.md §8b: the drop-in claim executed through the reference's own `YoloXDetector`
-    (models/detection/yolox_extension/models/detector.py:18-41) and registry branch, on the emulator library."""
+    """VERDICT r3 item 9 / SURVEY.md §8b: the drop-in claim, against the reference's own `YoloXDetector`
+    (models/detection/yolox_extension/models/detector.py:18-41) as recorded in tests/golden/dropin_detector.npz, on the emulator library."""
     script = tmp_path / 'dropin.py'
     script.write_text(DROPIN_WORKER)
     r = subprocess.run([sys.executable, str(script), ROOT], capture_output=True, text=True, timeout=600)
