@@ -20,6 +20,7 @@
  *       rvt_stage_seq_fwd (+ _ws_bytes)                one call per backbone stage and sequence (no-grad forward)
  *       rvt_stacked_histogram                          event stream -> input tensor (row f4)
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
+ *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *   Operator level — every other entry below: one launch each, what the stage driver sequences and what the Python mirror
  *       (rvt_amd/stage.py, the training backward) calls directly.  Stable and tested one by one (tests/test_kernels.py), but a host
@@ -508,6 +509,27 @@ size_t rvt_simota_ws_bytes(int B, int G, int A);
 int rvt_simota_loss(const float* pred_train, const float* labels, const int* level_hw, const int* level_stride, int L, int B, int G, int A,
                     int num_classes, float* losses, float* g_pred, int* match_out, float* piou_out, void* ws, size_t ws_bytes,
                     void* stream);
+
+/* Detection post-processing of the eval-mode detections (rvt_amd/csrc/nms.hpp; host mirror rvt_amd/postprocess.py).  Replaces
+ * models/detection/yolox/utils/boxes.py:32-76 (`postprocess`: a Python loop over the images, boolean-mask indexing and
+ * torchvision's NMS) by ONE launch for the whole batch with no host synchronisation and no device-to-host copy: capturable.
+ *   pred [B][A][5+nc] fp32 rows cx cy w h obj cls... (the pred_infer of rvt_yolox_decode); it is only read.
+ *   Per image: class_conf = max over the class columns, class_pred = its index (lowest index on an exact tie);
+ *   score = obj * class_conf (one fp32 multiply); candidates are the anchors with score >= conf_thre, ordered by descending
+ *   score, the lower anchor first on an exact tie; greedy NMS in that order: a candidate still alive is kept and kills every
+ *   later candidate of the same class (of any class if class_agnostic) whose IoU with it is > nms_thre.  Corners are
+ *   cx -+ w/2, cy -+ h/2; area = (x2-x1)*(y2-y1); inter = max(0, min(x2)-max(x1)) * max(0, min(y2)-max(y1));
+ *   iou = inter / (area_a + area_b - inter) in fp32 in exactly this order (torchvision's CPU kernel, no "+1"); a pair whose
+ *   union is not positive never suppresses.  Every keep / kill decision equals the same formula evaluated by torch.
+ *   det [B][max_det][7] = x1 y1 x2 y2 obj class_conf class_pred of the kept rows in descending score order; rows from
+ *   min(count, max_det) on are zero.  count [B] = rows kept BEFORE the max_det cap (count > max_det: truncated).
+ *   anchor_idx [B][max_det] (NULL = skip) = source anchor of each row, -1 past the last.
+ *   Supported: 1 <= A <= 16384 anchors per image, 1 <= num_classes <= 80, 1 <= B <= 65535; anything else returns non-zero with
+ *   the last error set before any launch.  Non-finite inputs are outside the contract but terminate in bounds.
+ *   ws: the ws_bytes query's size (52 bytes per anchor and image; 0 = shape unsupported), contents need not survive the call. */
+size_t rvt_yolox_postprocess_ws_bytes(int B, int A, int num_classes);
+int rvt_yolox_postprocess(const float* pred, int B, int A, int num_classes, float conf_thre, float nms_thre, int class_agnostic,
+                          int max_det, float* det, int* count, int* anchor_idx, void* ws, size_t ws_bytes, void* stream);
 
 /* Zero state rows of samples with mask[b] != 0 (modules/utils/detection.py:96-113).
  * st is [B][per_sample] of float32 (is_f32) or `dtype`. */

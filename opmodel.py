@@ -191,6 +191,9 @@ def model(name: str, a) -> Optional[Tuple[float, float]]:
     if name == 'rvt_simota_loss':                                # pred in (cost, select/resolve, loss passes), cost + IoU matrices out and back
         L_, B, G, A, nc = a[4:9]
         return 0.0, 3.0 * B * A * (5 + nc) * 4 + (B * A * (5 + nc) * 4 if P(10) else 0) + 4.0 * B * G * A * 4 + 6.0 * B * A * 4
+    if name == 'rvt_yolox_postprocess':                          # pred in, det / count / anchor_idx out, the workspace written and read back
+        B, A, nc, max_det = a[1], a[2], a[3], a[7]
+        return 0.0, 1.0 * B * A * (5 + nc) * 4 + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if P(10) else 0) + 2.0 * 52 * B * A
     return None
 
 
@@ -217,6 +220,9 @@ def executed(name: str, a) -> Optional[float]:
     if name == 'rvt_attn_block_bwd_preln':
         F, H, W, C, dh, ph, pw = a[12:19]
         return fl + F * H * W * (6.0 * C * C + 2.0 * ph * pw * C)
+    if name == 'rvt_yolox_postprocess':                          # vector (not MFMA) work, data dependent: the all-pairs bound of the greedy
+        B, A = a[1], a[2]                                        # NMS, 12 flops per IoU test (4 min/max, 3 sub, 2 max, mul, add, div)
+        return 12.0 * B * A * (A - 1) / 2
     if name == 'rvt_lstm_scan_bwd' and not P(16):
         M, C, T = a[18], a[19], a[20]
         return fl + 16.0 * M * C * C * T

@@ -1,7 +1,9 @@
 // extern "C" entry points, part 10: the YOLOX head's tail — box decode, batched on-device SimOTA
-// assignment and the detection losses with their gradient (simota.hpp; reference models/detection/yolox/models/yolo_head.py).
+// assignment and the detection losses with their gradient (simota.hpp; reference models/detection/yolox/models/yolo_head.py),
+// and the detection post-processing that follows the eval-mode decode (nms.hpp; reference models/detection/yolox/utils/boxes.py).
 #include "host.hpp"
 #include "simota.hpp"
+#include "nms.hpp"
 
 using namespace rvt;
 
@@ -42,6 +44,26 @@ static SimotaWs carve_simota(char* base, int B, int G, int A) {
     w.match = (int*)take(ba * 4);
     w.bytes = off;
     return w;
+}
+static size_t carve_nms(char* base, int B, int A, NmsWs& w) {
+    size_t off = 0;
+    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += (n + 255) & ~(size_t)255; return p; };
+    const size_t ba = (size_t)B * A;
+    w.keys = (unsigned long long*)take(ba * 8);
+    w.sorted = (unsigned long long*)take(ba * 8);
+    w.x1 = (float*)take(ba * 4);
+    w.y1 = (float*)take(ba * 4);
+    w.x2 = (float*)take(ba * 4);
+    w.y2 = (float*)take(ba * 4);
+    w.area = (float*)take(ba * 4);
+    w.obj = (float*)take(ba * 4);
+    w.conf = (float*)take(ba * 4);
+    w.cls = (int*)take(ba * 4);
+    w.acls = (int*)take(ba * 4);
+    return off;
+}
+static bool nms_range_ok(int B, int A, int nc) {
+    return B >= 1 && B <= 65535 && A >= 1 && A <= NMS_MAX_A && nc >= 1 && nc <= NMS_MAX_NC;
 }
 }  // namespace
 
@@ -95,6 +117,27 @@ int rvt_simota_loss(const float* pred_train, const float* labels, const int* lev
     hipLaunchKernelGGL(yolox_loss_kernel, ga, dim3(256), 0, st, pred_train, labels, match, piou, w.meta, G, A, num_classes, w.partial, g_pred);
     hipLaunchKernelGGL(yolox_loss_finalize_kernel, dim3(1), dim3(256), 0, st, w.partial, (int)(ga.x * ga.y), w.meta, losses);
     return check_launch("simota_loss");
+}
+
+size_t rvt_yolox_postprocess_ws_bytes(int B, int A, int num_classes) {
+    if (!nms_range_ok(B, A, num_classes)) return 0;
+    NmsWs w;
+    return carve_nms(nullptr, B, A, w);
+}
+
+int rvt_yolox_postprocess(const float* pred, int B, int A, int num_classes, float conf_thre, float nms_thre, int class_agnostic,
+                          int max_det, float* det, int* count, int* anchor_idx, void* ws, size_t ws_bytes, void* stream) {
+    RVT_CHECK(A >= 1 && A <= NMS_MAX_A, "yolox_postprocess: A=%d anchors outside the supported range 1..%d", A, NMS_MAX_A);
+    RVT_CHECK(num_classes >= 1 && num_classes <= NMS_MAX_NC, "yolox_postprocess: num_classes=%d outside the supported range 1..%d",
+              num_classes, NMS_MAX_NC);
+    RVT_CHECK(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= (1 << 24), "yolox_postprocess: B=%d max_det=%d out of range", B, max_det);
+    RVT_CHECK(pred && det && count && ws, "yolox_postprocess: null argument");
+    NmsWs w;
+    const size_t need = carve_nms((char*)ws, B, A, w);
+    RVT_CHECK(ws_bytes >= need, "yolox_postprocess: workspace %zu < %zu bytes", ws_bytes, need);
+    hipLaunchKernelGGL(yolox_postprocess_kernel, dim3(B), dim3(NMS_THREADS), 0, (hipStream_t)stream, pred, A, num_classes, conf_thre,
+                       nms_thre, class_agnostic != 0 ? 1 : 0, max_det, det, count, anchor_idx, w);
+    return check_launch("yolox_postprocess");
 }
 
 }  // extern "C"

@@ -17,7 +17,8 @@ What runs where:
 
 Differences a caller can see: `losses["num_fg"]` is a 0-dim device tensor instead of a Python float (reading it is the caller's
 choice of sync point); `outputs` carries no autograd history (the reference returns it attached, nothing in the reference
-differentiates it: modules/detection.py uses it for the detections only); use_l1 (never switched on by RVT), depthwise and
+differentiates it: modules/detection.py uses it for the detections only, after `postprocess` — score filter + NMS, built as
+rvt_amd.postprocess on the same pattern: one launch for the batch, no host synchronisation); use_l1 (never switched on by RVT), depthwise and
 decode_in_inference=False are not built; an image whose ground truths have no candidate anchor at all gets no matches where the
 reference's torch.topk raises.
 """
