@@ -21,6 +21,7 @@
  *       rvt_stacked_histogram                          event stream -> input tensor (row f4)
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
  *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
+ *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *   Operator level — every other entry below: one launch each, what the stage driver sequences and what the Python mirror
  *       (rvt_amd/stage.py, the training backward) calls directly.  Stable and tested one by one (tests/test_kernels.py), but a host
@@ -553,6 +554,38 @@ int rvt_layerscale_grad_table(const void* descs, int n_desc, int total_blocks, v
 int rvt_stacked_histogram(const long long* x, const long long* y, const long long* pol, const long long* time,
                           size_t n_events, int bins, int H, int W, int count_cutoff, int fastmode, unsigned* scratch,
                           unsigned char* out, void* stream);
+
+/* Spatial training augmentation (rvt_amd/csrc/augment.hpp; data/utils/augmentor.py RandomSpatialAugmentorGenX and
+ * data/genx_utils/labels.py): horizontal flip, then zoom-in or zoom-out, of a batch of sequences and of their box labels.
+ * Frame f belongs to sample f % B; every per-sample parameter is read from a device table the host writes, so neither call
+ * synchronises with the host and both replay in a hipGraph with a rewritten table.  Bit-exact with the reference.
+ *
+ * rvt_augment_planes: in / out uint8 [F][C][H][W] (the loader's NCHW planes), out must not overlap in.  A list of T separately
+ *   allocated (B,C,H,W) tensors is one call per tensor with F = B.  table int32 [B][8]: flip, mode (0 none, 1 zoom-in,
+ *   2 zoom-out), x0, y0, zh, zw, 0, 0 with zh = int(H / factor), zw = int(W / factor) computed by the host in double.
+ *     n(i; n_out, n_in) = min((int)floorf((i + 0.5f) * ((float)n_in / (float)n_out)), n_in - 1)     (PyTorch's nearest-exact)
+ *     S[y][x] = flip ? in[y][W-1-x] : in[y][x]
+ *     mode 0: out = S;   mode 1: out[y][x] = S[y0 + n(y; H, zh)][x0 + n(x; W, zw)];
+ *     mode 2: out[y][x] = S[n(y-y0; zh, H)][n(x-x0; zw, W)] for y0 <= y < y0+zh and x0 <= x < x0+zw, else 0.
+ *   The kernel clamps the window into the frame, so any table contents terminate in bounds; a window outside the frame is the
+ *   host's to reject.  16-byte accesses when W % 16 == 0 and both bases are 16-byte aligned, byte accesses otherwise.
+ *   Supported: 1 <= W <= 2048, C*H <= 2^24; anything else returns non-zero with the last error set before any launch.
+ *
+ * rvt_augment_labels: rows fp32 [F][G][7] (t x y w h class_id class_confidence), count int32 [F] (-1 = a frame without
+ *   labels).  rows_out [F][G][7]: the surviving rows in their original order, zero rows behind them; count_out [F]: survivors,
+ *   -1 carried through; yolox_out [F][G][5] (NULL = skip): class, x + 0.5*w, y + 0.5*h, w, h of the survivors, zero padded.
+ *   table fp32 [B][12]: flip, mode, W-1, x0, y0, hx, hy, m, capx, capy, 0, 0 (each computed in double and rounded once).
+ *   Every line is one rounded fp32 operation, no fused multiply-add:
+ *     flip:     x = ((W-1) - x) - w
+ *     mode 1:   cx0 = min(max(x, x0), hx); cx1 = min(max(x + w, x0), hx) (y likewise); x = cx0 - x0; w = cx1 - cx0;
+ *               rows without w > 0 and h > 0 are dropped; then scale
+ *     mode 2:   scale; then x = x + x0; y = y + y0
+ *     scale:    x1 = min((x + w) * m, capx); y1 likewise; x = x * m; y = y * m; w = x1 - x; h = y1 - y; dropped unless w, h > 0
+ *   with, for zoom factor f:  mode 1: hx = min(x0 + W/f, W-1) - 1, m = f, capx = f * (W/f) - 1;  mode 2: m = 1/f,
+ *   capx = (1/f) * W - 1 (y likewise). */
+int rvt_augment_planes(const void* in, void* out, const int* table, int F, int B, int C, int H, int W, void* stream);
+int rvt_augment_labels(const float* rows, const int* count, const float* table, int F, int B, int G, float* rows_out, int* count_out,
+                       float* yolox_out, void* stream);
 
 #ifdef __cplusplus
 }

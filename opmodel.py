@@ -194,7 +194,24 @@ def model(name: str, a) -> Optional[Tuple[float, float]]:
     if name == 'rvt_yolox_postprocess':                          # pred in, det / count / anchor_idx out, the workspace written and read back
         B, A, nc, max_det = a[1], a[2], a[3], a[7]
         return 0.0, 1.0 * B * A * (5 + nc) * 4 + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if P(10) else 0) + 2.0 * 52 * B * A
+    if name == 'rvt_augment_planes':                             # uint8 planes in and out; the per-sample windows live in the device table,
+        F, B, C, H, W = a[3:8]                                   # so this is the bound of a flip: every byte read once, written once
+        return 0.0, 2.0 * F * C * H * W + 32.0 * B
+    if name == 'rvt_augment_labels':                             # rows + count in, rows + count (+ yolox) out
+        F, B, G = a[3:6]
+        return 0.0, 2.0 * F * (G * 7 * 4 + 4) + (F * G * 5 * 4 if P(8) else 0) + 48.0 * B
     return None
+
+
+def augment_planes_bytes(F: int, C: int, H: int, W: int, windows) -> float:
+    """HBM bytes of one rvt_augment_planes launch when the table is known: windows[b] = (mode, zh, zw) of sample b = f % B.
+    Every output byte is written once; a zoom-in reads its zh x zw source window, a zoom-out the zh source rows it keeps."""
+    total = 0.0
+    for f in range(F):
+        mode, zh, zw = windows[f % len(windows)]
+        read = {1: zh * zw, 2: zh * W}.get(mode, H * W)
+        total += C * (H * W + read)
+    return total
 
 
 def executed(name: str, a) -> Optional[float]:

@@ -79,6 +79,8 @@ _SIGS = {
     'rvt_yolox_decode_bwd': [_vp] * 5 + [_i] * 10 + [_vp],
     'rvt_simota_loss': [_vp] * 4 + [_i] * 5 + [_vp] * 5 + [ctypes.c_size_t, _vp],
     'rvt_yolox_postprocess': [_vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    'rvt_augment_planes': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    'rvt_augment_labels': [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ['rvt_last_error', 'rvt_is_emulator', 'rvt_wgrad_workspace_floats',
                                'rvt_mlp_fused_supported', 'rvt_lstm_scan_supported', 'rvt_mlp_bwd_fused_supported',

@@ -1,0 +1,207 @@
+// Spatial training augmentation on the device: horizontal flip, zoom-in and zoom-out of the uint8 event planes and of the box
+// labels of a whole batch of sequences, every per-sample parameter read from a small device table the host writes.
+// Reference: data/utils/augmentor.py (RandomSpatialAugmentorGenX: th.flip, interpolate(mode='nearest-exact') on a crop / into a
+// zero canvas) and data/genx_utils/labels.py (ObjectLabels.flip_lr_ / zoom_in_and_rescale_ / zoom_out_and_rescale_ / scale_).
+//
+// Planes (augment_planes_kernel): in / out uint8 [F][C][H][W], frame f of sample f % B.  The reference's order is flip, then zoom:
+//     n(i; n_out, n_in) = min((int)floorf((i + 0.5f) * ((float)n_in / (float)n_out)), n_in - 1)         PyTorch's CPU nearest-exact
+//     S[y][x] = flip ? in[y][W-1-x] : in[y][x]
+//     mode 0: out = S      mode 1: out[y][x] = S[y0 + n(y; H, zh)][x0 + n(x; W, zw)]
+//     mode 2: out[y][x] = S[n(y-y0; zh, H)][n(x-x0; zw, W)] inside the window [y0, y0+zh) x [x0, x0+zw), 0 outside
+// A pure byte mover.  One workgroup takes 64 consecutive (plane, row) pairs of one frame.  All of them share one x map, built once
+// per workgroup in LDS as the LDS position of the source byte of every output column (flip and window offset folded in; columns
+// outside a zoom-out window point at a zero byte).  Eight source rows at a time are brought into LDS with 16-byte loads of the
+// contiguous source segment ([x0, x0+zw) for zoom-in, the whole row otherwise), and every lane assembles 16 output pixels with
+// byte reads from LDS and writes them with one 16-byte store.  Source byte x sits at LDS position x + 4 * (x / 256): a wave's 64
+// lanes read dwords about 4 apart, and the skew spreads what would be a 4-way bank conflict over neighbouring banks.
+// W % 16 != 0 or a base that is not 16-byte aligned takes the same kernel with byte-wide global accesses (VEC = false).
+// The table is clamped into the frame on the device, so any table contents terminate in bounds.
+//
+// Labels (augment_labels_kernel): rows fp32 [F][G][7] (t x y w h class_id class_confidence), count int32 [F] (-1 = no labels).
+// One thread per frame walks its rows in order, so survivors keep their order.  Every operation is one rounded fp32 operation in
+// the reference's order (this translation unit is compiled with -ffp-contract=off: x1 - x*m rounds x*m first); the constants
+// come from the host, computed in double and rounded once, which is what torch does with Python scalars on fp32 tensors.
+#pragma once
+#include "common.hpp"
+
+namespace rvt {
+
+constexpr int AUG_THREADS = 256;
+constexpr int AUG_MAX_W = 2048;                       // x map: one ushort per column in LDS
+constexpr int AUG_ROWS = 8;                           // source rows staged in LDS at once
+constexpr int AUG_CHUNK = 64;                         // (plane, row) pairs per workgroup
+constexpr int AUG_LDS_ROW = AUG_MAX_W + 4 * (AUG_MAX_W / 256) + 16;
+constexpr int AUG_PT = 8;                             // planes table, int32 per sample: flip mode x0 y0 zh zw - -
+constexpr int AUG_LT = 12;                            // label table, fp32 per sample: flip mode W-1 x0 y0 hx hy m capx capy - -
+
+__device__ __forceinline__ int aug_min(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int aug_max(int a, int b) { return a > b ? a : b; }
+__device__ __forceinline__ int aug_pos(int x) { return x + ((x >> 8) << 2); }
+
+__device__ __forceinline__ int aug_nearest(int i, int n_out, int n_in) {
+    const float scale = (float)n_in / (float)n_out;
+    const int s = (int)floorf(((float)i + 0.5f) * scale);
+    return s < n_in - 1 ? s : n_in - 1;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS)
+augment_planes_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, const int* __restrict__ table,
+                      int B, int C, int H, int W, int chunks) {
+    __shared__ __attribute__((aligned(16))) unsigned short xmap[AUG_MAX_W];
+    __shared__ __attribute__((aligned(16))) unsigned char srow[AUG_ROWS * AUG_LDS_ROW];
+    __shared__ int s_src[AUG_CHUNK];                  // source row inside the frame (plane * H + y), -1 = a zero row
+    constexpr int T = AUG_THREADS, V = VEC ? 16 : 1;
+    const int tid = threadIdx.x;
+    const int f = blockIdx.x / chunks, q0 = (blockIdx.x % chunks) * AUG_CHUNK, NR = C * H;
+    const int* tb = table + (size_t)(f % B) * AUG_PT;
+    const bool flip = tb[0] != 0;
+    const int mode = (tb[1] == 1 || tb[1] == 2) ? tb[1] : 0;
+    const int zh = aug_min(aug_max(tb[4], 1), H), zw = aug_min(aug_max(tb[5], 1), W);
+    const int x0 = aug_min(aug_max(tb[2], 0), W - zw), y0 = aug_min(aug_max(tb[3], 0), H - zh);
+    const int LW = ((aug_pos(W - 1) + 4) & ~3) + 4, ZREL = LW - 4;      // LDS row pitch; its last dword stays zero
+    const unsigned char* fin = in + (size_t)f * NR * W;
+    unsigned char* fout = out + (size_t)f * NR * W;
+
+    for (int x = tid; x < W; x += T) {
+        int sx = x;
+        if (mode == 1) sx = x0 + aug_nearest(x, W, zw);
+        else if (mode == 2) sx = (x >= x0 && x < x0 + zw) ? aug_nearest(x - x0, zw, W) : -1;
+        if (sx >= 0 && flip) sx = W - 1 - sx;
+        xmap[x] = (unsigned short)(sx < 0 ? ZREL : aug_pos(sx));
+    }
+    if (tid < AUG_CHUNK) {
+        const int q = q0 + tid;
+        int src = -1;
+        if (q < NR) {
+            const int c = q / H, y = q - c * H;
+            int sy = y;
+            if (mode == 1) sy = y0 + aug_nearest(y, H, zh);
+            else if (mode == 2) sy = (y >= y0 && y < y0 + zh) ? aug_nearest(y - y0, zh, H) : -1;
+            src = sy < 0 ? -1 : c * H + sy;
+        }
+        s_src[tid] = src;
+    }
+    if (tid < AUG_ROWS) *(unsigned*)&srow[tid * LW + ZREL] = 0u;
+    // source columns a row needs, in units of V bytes
+    const int lo = (mode == 1 ? (flip ? W - x0 - zw : x0) : 0) / V;
+    const int hi = (mode == 1 ? (flip ? W - 1 - x0 : x0 + zw - 1) : W - 1) / V;
+    const int nsrc = hi - lo + 1, ndst = W / V;
+
+    for (int qb = q0; qb < q0 + AUG_CHUNK && qb < NR; qb += AUG_ROWS) {
+        const int nrows = aug_min(AUG_ROWS, NR - qb);
+        __syncthreads();                              // x map and row table written; the previous group's gather is done
+        {
+            int r = tid / nsrc, p = tid - r * nsrc;
+            const int dr = T / nsrc, dp = T - dr * nsrc;
+            while (r < nrows) {
+                const int src = s_src[qb - q0 + r];
+                if (src >= 0) {
+                    const int x = (lo + p) * V;
+                    const unsigned char* g = fin + (size_t)src * W + x;
+                    unsigned char* s = &srow[r * LW + aug_pos(x)];
+                    if constexpr (VEC) {
+                        const u32x4 v = *(const u32x4*)g;
+                        unsigned* s4 = (unsigned*)s;  // the skew keeps 4-byte, not 16-byte, alignment
+                        s4[0] = v.x; s4[1] = v.y; s4[2] = v.z; s4[3] = v.w;
+                    } else {
+                        *s = *g;
+                    }
+                }
+                r += dr; p += dp;
+                if (p >= nsrc) { p -= nsrc; r++; }
+            }
+        }
+        __syncthreads();
+        {
+            int r = tid / ndst, p = tid - r * ndst;
+            const int dr = T / ndst, dp = T - dr * ndst;
+            while (r < nrows) {
+                const bool zero = s_src[qb - q0 + r] < 0;
+                const unsigned char* s = &srow[r * LW];
+                unsigned char* g = fout + (size_t)(qb + r) * W + p * V;
+                if constexpr (VEC) {
+                    u32x4 v = {0u, 0u, 0u, 0u};
+                    if (!zero) {
+                        const u32x4 ma = *(const u32x4*)&xmap[p * 16], mb = *(const u32x4*)&xmap[p * 16 + 8];
+                        const unsigned m[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
+                        unsigned w[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const unsigned a = m[2 * k], b = m[2 * k + 1];
+                            w[k] = (unsigned)s[a & 0xffffu] | ((unsigned)s[a >> 16] << 8) | ((unsigned)s[b & 0xffffu] << 16) |
+                                   ((unsigned)s[b >> 16] << 24);
+                        }
+                        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+                    }
+                    *(u32x4*)g = v;
+                } else {
+                    *g = zero ? (unsigned char)0 : s[xmap[p]];
+                }
+                r += dr; p += dp;
+                if (p >= ndst) { p -= ndst; r++; }
+            }
+        }
+    }
+}
+
+// scale_ of the reference: returns whether the row survives (w > 0 and h > 0)
+__device__ __forceinline__ bool aug_scale(float& x, float& y, float& w, float& h, float m, float capx, float capy) {
+    const float x1 = fminf((x + w) * m, capx), y1 = fminf((y + h) * m, capy);
+    x = x * m;
+    y = y * m;
+    w = x1 - x;
+    h = y1 - y;
+    return w > 0.f && h > 0.f;
+}
+
+__global__ void __launch_bounds__(AUG_THREADS)
+augment_labels_kernel(const float* __restrict__ rows, const int* __restrict__ count, const float* __restrict__ table, int F, int B,
+                      int G, float* __restrict__ rows_out, int* __restrict__ count_out, float* __restrict__ yolox_out) {
+    const int f = blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (f >= F) return;
+    const float* tb = table + (size_t)(f % B) * AUG_LT;
+    const bool flip = tb[0] != 0.f;
+    const int mode = tb[1] == 1.f ? 1 : (tb[1] == 2.f ? 2 : 0);
+    const float wm1 = tb[2], zx0 = tb[3], zy0 = tb[4], hx = tb[5], hy = tb[6], m = tb[7], capx = tb[8], capy = tb[9];
+    const int n_in = count[f], n = aug_min(aug_max(n_in, 0), G);
+    const float* src = rows + (size_t)f * G * 7;
+    float* dst = rows_out + (size_t)f * G * 7;
+    float* yo = yolox_out ? yolox_out + (size_t)f * G * 5 : nullptr;
+    int kept = 0;
+    for (int i = 0; i < n; i++) {
+        const float* r = src + i * 7;
+        float x = r[1], y = r[2], w = r[3], h = r[4];
+        bool keep = true;
+        if (flip) x = (wm1 - x) - w;
+        if (mode == 1) {
+            const float cx0 = fminf(fmaxf(x, zx0), hx), cx1 = fminf(fmaxf(x + w, zx0), hx);
+            const float cy0 = fminf(fmaxf(y, zy0), hy), cy1 = fminf(fmaxf(y + h, zy0), hy);
+            x = cx0 - zx0;
+            y = cy0 - zy0;
+            w = cx1 - cx0;
+            h = cy1 - cy0;
+            keep = w > 0.f && h > 0.f;
+            if (keep) keep = aug_scale(x, y, w, h, m, capx, capy);
+        } else if (mode == 2) {
+            keep = aug_scale(x, y, w, h, m, capx, capy);
+            x = x + zx0;
+            y = y + zy0;
+        }
+        if (!keep) continue;
+        float* d = dst + kept * 7;
+        d[0] = r[0]; d[1] = x; d[2] = y; d[3] = w; d[4] = h; d[5] = r[5]; d[6] = r[6];
+        if (yo) {
+            float* o = yo + kept * 5;
+            o[0] = r[5]; o[1] = x + 0.5f * w; o[2] = y + 0.5f * h; o[3] = w; o[4] = h;
+        }
+        kept++;
+    }
+    for (int i = kept; i < G; i++) {
+        for (int k = 0; k < 7; k++) dst[i * 7 + k] = 0.f;
+        if (yo) for (int k = 0; k < 5; k++) yo[i * 5 + k] = 0.f;
+    }
+    count_out[f] = n_in < 0 ? -1 : kept;
+}
+
+}  // namespace rvt

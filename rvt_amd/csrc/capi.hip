@@ -11,3 +11,4 @@
 #include "capi_stage.hip"
 #include "capi_head.hip"
 #include "capi_train.hip"
+#include "capi_augment.hip"
