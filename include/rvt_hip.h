@@ -329,23 +329,27 @@ int rvt_lstm_scan_bwd(const void* x_all, const void* Hall, const void* Csave, co
  * Forward: x_all [T][M][C], Hall [T+1][M][C] (slot 0 = incoming h, filled by the caller; slots 1.. written), c0 fp32 [M][C] or
  * NULL (zeros, rnn.py:43-47), c_last fp32 [M][C].  For BPTT it saves the ACTIVATED gates (gsave) and a bf16 copy of the cell
  * states (Csave) in a private register-dump order; both buffers hold T * rvt_lstm_scan3_rows(C, M) * 4C / * C elements and are
- * NULL together for a no-grad forward.  Backward: reads them back (same M, same tuning), dH [T][M][C] = cotangent of Hall[1..]
+ * NULL together for a no-grad forward.  Backward: reads them back (same M, same rb), dH [T][M][C] = cotangent of Hall[1..]
  * (NULL = zeros), dc_last fp32 [M][C] (NULL = zeros); writes dx_all [T][M][C], dz_all [T][M][4C] (natural gate order: the operand
  * of rvt_lstm_wgrad), dh0 [M][C], dc0 fp32 [M][C]. */
 int rvt_lstm_scan3_supported(int dtype, int C);
-int rvt_lstm_scan3_rows(int C, int M);
+/* rb in {1, 2}: the forward walks tiles of 32 * rb tokens, and the dump order depends on it, so ONE value serves the buffer sizing,
+ * the forward and the reverse scan of a step.  rvt_lstm_scan3_rb(C) is the tuned value (RvtTuning.lstm_scan3_rb128 / _rb256); a stage
+ * takes it from its route record (RvtStageRoutes.lstm_scan3_rb), never from the tuning record a second time. */
+int rvt_lstm_scan3_rb(int C);
+int rvt_lstm_scan3_rows(int C, int M, int rb);
 int rvt_lstm_scan3_pack(const void* w, void* wp_fwd, void* wtp_bwd, int C, void* stream);
 int rvt_lstm_scan3_fwd(const void* x_all, void* Hall, const float* c0, float* c_last, void* Csave, const void* wp, const float* bias,
-                       void* gsave, int dtype, int M, int C, int T_steps, void* stream);
+                       void* gsave, int dtype, int M, int C, int T_steps, int rb, void* stream);
 int rvt_lstm_scan3_bwd(const void* gsave, const void* Csave, const float* c0, const void* dH, const float* dc_last, const void* wtp,
-                       void* dx_all, void* dz_all, void* dh0, float* dc0, int dtype, int M, int C, int T_steps, void* stream);
+                       void* dx_all, void* dz_all, void* dh0, float* dc0, int dtype, int M, int C, int T_steps, int rb, void* stream);
 
 /* ---- stage-major driver (rvt_stage_seq_fwd) -------------------------------------------------------------
  * One backbone stage (reference maxvit_rnn.py:169-182: down-sampling conv + LayerNorm, the window and grid attention blocks,
  * the ConvLSTM) over ALL T time steps of B sequences in ONE call, for the NO-GRAD forward: validation and streaming inference
- * (modules/detection.py:231-255 with T = 1 per call).  The kernel routing and the per-step ConvLSTM loop that rvt_amd/stage.py
- * runs in Python happen inside the library; it launches exactly the operators declared in this header, on `stream`.
- * (The training forward / backward keep their host loop in rvt_amd/stage.py: the saved-activation bookkeeping lives there.)
+ * (modules/detection.py:231-255 with T = 1 per call).  The driver asks rvt_stage_routes (below) for the stage's routes and runs the
+ * block loop and the ConvLSTM loop that rvt_amd/stage.py's host loop runs in Python; it launches exactly the operators declared in
+ * this header, on `stream`.  (The training forward / backward have a driver of their own further down: rvt_stage_seq_train_fwd.)
  * All pointers in the descriptors are DEVICE pointers except `blocks`, a HOST array of 2 * num_blocks records
  * (window block, grid block, window, grid, ...).  Unsupported here (call the operators instead): token masks, DWS-ConvLSTM. */
 typedef struct RvtBlockWeights {          /* one PartitionAttentionCl block, maxvit.py:193-270 */
@@ -378,14 +382,38 @@ size_t rvt_stage_seq_fwd_ws_bytes(const RvtStageDesc* desc, int T, int B);
 int rvt_stage_seq_fwd(const RvtStageDesc* desc, const void* inp, const void* h0, const float* c0, void* Hall, float* c_last,
                       void* ws, size_t ws_bytes, int T, int B, void* stream);
 
+/* ---- the routes of one stage ---------------------------------------------------------------------------------------------------
+ * Which kernels a stage runs, decided ONCE per forward by rvt_stage_routes from (tuning record, rvt_*_supported answers, shape) and
+ * carried with the saved activations: the backward of a training step reads the record its forward was planned with, never the
+ * tuning record again.  Consumers: rvt_stage_seq_fwd (plans internally), RvtStageTrain below, the host loop of rvt_amd/stage.py. */
+typedef struct RvtStageRoutes {
+    int attn_block;                       /* 1: fused attention half (rvt_attn_block_fwd / _bwd) */
+    int ln_linear;                        /* 1: norm1 + qkv in one launch (rvt_ln_linear_fwd); implies attn_block = 0 */
+    int mlp_route;                        /* 0: LayerNorm, fc1 + GELU / GELU', fc2 as separate launches; 1: recompute route (rvt_mlp_fwd keeps nothing);
+                                             2: rvt_mlp_fwd saving what an op-by-op style backward reads (host loop only; save = 1 only) */
+    int mlp_bwd_both;                     /* route 1: rvt_mlp_bwd_recompute_both instead of _dgrad + _wgrad */
+    int dgrad_ln_qkv, dgrad_ln_fc1;       /* 1: that input gradient + the LayerNorm backward behind it in one launch (rvt_linear_dgrad_ln) */
+    int lstm_route;                       /* 0: one launch per step; 1: the rvt_lstm_scan_ kernels, gates recomputed; 2: the same with saved gates; 3: the rvt_lstm_scan3_ kernels */
+    int lstm_scan_wgrad;                  /* route 1: ConvLSTM weight gradients inside the reverse scan */
+    int conv_dgrad4;                      /* 1: rvt_conv_dgrad4 for the input gradient of the down-sampling conv (where the host built its weight copy) */
+    int attn_preln;                       /* the first block's backward also carries the gradient through the down-sampling norm: rvt_attn_block_bwd_preln (attn_block = 1) or rvt_linear_dgrad_preln (dgrad_ln_qkv = 1) */
+    int mlp_store_pre;                    /* route 2: keep the pre-activation h alone; GELU / GELU' are applied on load by the backward */
+    int mlp_bwd_dgrad;                    /* route 2: both MLP input gradients + the norm2 backward in one launch (rvt_mlp_bwd_dgrad) */
+    int lstm_scan3_rb;                    /* route 3: the tile factor of forward, dump buffers and reverse scan (1 or 2); 0 otherwise */
+    int driver_covers;                    /* 1: the C-side driver of this direction runs these routes (no token mask, no DWS-ConvLSTM; training:
+                                             also RvtTuning.route_wgrad_stream = 0 and mlp_route != 2); 0: the host loop does */
+} RvtStageRoutes;
+/* save: the forward keeps activations for a backward.  has_dws / has_token_mask: the stage has a DWS-ConvLSTM / a token mask is applied. */
+int rvt_stage_routes(const RvtStageDesc* desc, int T, int B, int save, int has_dws, int has_token_mask, RvtStageRoutes* out);
+
 /* ---- training-side stage driver (rvt_stage_seq_bwd; round 6) ----------------------------------------------
  * The TRAINING forward and the BPTT backward of one stage (reference maxvit_rnn.py:169-182 under autograd, driven by
  * modules/detection.py:131-148) as ONE library call each: the per-operator launches that rvt_amd/stage.py issued from Python
- * (40 - 150 per stage and direction) are sequenced here.  Division of labour: the HOST decides the kernel routes (one place:
- * rvt_amd/stage.py) and owns every tensor that outlives the call - the activations kept for backward (RvtBlockSaved and the
- * stage-level pointers below) and the gradient buckets; the driver owns the order of launches and the backward's temporaries
+ * (40 - 150 per stage and direction) are sequenced here.  Division of labour: rvt_stage_routes decides the kernel routes; the HOST
+ * copies that record into `routes` and owns every tensor that outlives the call - the activations kept for backward (RvtBlockSaved and
+ * the stage-level pointers below) and the gradient buckets; the driver owns the order of launches and the backward's temporaries
  * (carved from `ws`).  Nothing is launched that the operator entry points above do not launch.  Not covered (the host keeps its
- * operator-by-operator loop): token masks, the DWS-ConvLSTM, the LDS-staged fused-MLP flavours that save GELU / GELU'. */
+ * operator-by-operator loop, rvt_amd/stage.py): whatever routes.driver_covers = 0 stands for. */
 typedef struct RvtBlockSaved {            /* activations of one block kept for backward; NULL = not kept on the chosen route */
     const void* xin;                      /* block input [M][C] (= previous block's xout, or the LayerNorm output of the down-sampling) */
     void* u;                              /* norm1(xin) (op-by-op attention with a norm1) */
@@ -404,16 +432,7 @@ typedef struct RvtBlockTrain {            /* backward-side operands and fp32 gra
 } RvtBlockTrain;
 typedef struct RvtStageTrain {
     int struct_bytes;                     /* sizeof(RvtStageTrain) */
-    /* routes, decided by the host */
-    int attn_block;                       /* 1: fused attention half (rvt_attn_block_fwd / _bwd) */
-    int ln_linear;                        /* 1: norm1 + qkv in one launch (rvt_ln_linear_fwd) */
-    int mlp_route;                        /* 0: LayerNorm, fc1 + GELU / GELU', fc2 as separate launches; 1: recompute route (rvt_mlp_fwd keeps nothing) */
-    int mlp_bwd_both;                     /* route 1: rvt_mlp_bwd_recompute_both instead of _dgrad + _wgrad */
-    int dgrad_ln_qkv, dgrad_ln_fc1;       /* 1: that input gradient + the LayerNorm backward behind it in one launch (rvt_linear_dgrad_ln) */
-    int lstm_route;                       /* 0: one launch per step; 1: the rvt_lstm_scan_ kernels, gates recomputed; 2: the same with saved gates; 3: the rvt_lstm_scan3_ kernels */
-    int lstm_scan_wgrad;                  /* routes 1: ConvLSTM weight gradients inside the reverse scan */
-    int conv_dgrad4;                      /* 1: rvt_conv_dgrad4 for the input gradient of the down-sampling conv */
-    int attn_preln;                       /* the first block's backward also carries the gradient through the down-sampling norm: rvt_attn_block_bwd_preln (attn_block = 1) or rvt_linear_dgrad_preln (op-by-op attention, where rvt_linear_dgrad_ln_supported(C, 3C)) */
+    RvtStageRoutes routes;                /* as rvt_stage_routes(.., save = 1, ..) filled it for the forward; the backward reads the same record */
     const RvtBlockSaved* saved;           /* HOST arrays, 2 * num_blocks entries each */
     const RvtBlockTrain* tb;
     void *y0, *x0;                        /* conv output, LayerNorm output (= saved[0].xin) */

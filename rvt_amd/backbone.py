@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, tuning
-from .stage import SideStream, StageGeom, stage_seq_backward, stage_seq_forward, use_lstm_scan
+from .stage import SideStream, StageGeom, stage_seq_backward, stage_seq_forward
 from .weights import ModelWeights, param_signature, param_versions, round8
 
 Tensor = torch.Tensor
@@ -385,7 +385,7 @@ class _BackboneSeqFn(torch.autograd.Function):
             # deferred weight gradients (tuning.route_wgrad_stream = 2): those of the stage above start now, beside this stage's reverse
             # scan; this stage queues its own iff the stage below scans per step (a chip-filling scan kernel leaves nothing to fill)
             side.flush()
-            side.deferring = side.defer_mode and si > 0 and not use_lstm_scan(dt, geoms[si - 1].C, mw.stages[si - 1].dws, T, True)
+            side.deferring = side.defer_mode and si > 0 and ctx.svs[si - 1].routes.lstm_route == 0
             dF, dC = gout[2 * si], gout[2 * si + 1]
             if si == ns - 1:
                 dH = None if dF is None else _to_cl(dF, dt)

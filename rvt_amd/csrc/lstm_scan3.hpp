@@ -1,4 +1,4 @@
-// ConvLSTM with the time loop inside the kernel for the WIDE stages (bf16, C = 256 / 512: stages 3 - 4 of RVT-Base, stage 4 of
+// ConvLSTM with the time loop inside the kernel for the WIDE stages (bf16, C = 128 / 256: stages 2 - 3 of RVT-Base, stages 3 - 4 of
 // RVT-Tiny) — reference models/layers/rnn.py:43-67 driven by the loop of modules/detection.py:131-148, and its BPTT.
 //
 // lstm_scan.hpp / lstm_scan2.hpp keep the cell's weights on chip (LDS or registers); at C >= 256 they are 1 - 4 MB and the

@@ -18,68 +18,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops, tuning
+from . import ops, stage_driver, tuning
 from .weights import StageGrads, StageWeights
 
-
-
-def use_fused_mlp(dtype, C: int, what: str) -> bool:
-    """Which MLP halves go through the fused kernels of csrc/mlp.hpp / mlp_chain.hpp.
-      'bwd_fused' (C = 64): the whole backward — recompute of LN2 / fc1 / GELU, both input-gradient products, LayerNorm
-          backward and the weight gradients (two launches) — from (dxout, xmid) alone; the forward then saves
-          nothing but the block input (3 + 2 rows of C per token through HBM for the MLP half instead of 32).
-      'fwd_train' / 'fwd_infer' / 'bwd' (C in {64,128}): fused forward (optionally saving GELU, GELU', LN2 out) and the
-          fused input-gradient chain.  Measured on MI355X (profiles/microbench_mlp.py, bf16, ms, fused vs op-by-op chain):
-          C=64 : training forward 3.00 / 3.72, inference forward 2.03 / 3.72, backward dgrad chain 2.31 / 3.51 -> fused
-          C=128: training forward 1.75 / 2.11, inference forward 1.53 / 2.11                                    -> fused
-                 backward dgrad chain 2.19 / 1.89 (one workgroup per CU: registers)                            -> chain
-    tuning.route_fused_mlp = 1 forces every supported case (used by the parity tests), 0 disables all;
-    tuning.route_mlp_bwd_fused = 0 disables only the everything-on-chip backward."""
-    mode = tuning.get('route_fused_mlp')
-    if what == 'bwd_fused':
-        return mode != 0 and tuning.get('route_mlp_bwd_fused') != 0 and ops.mlp_bwd_fused_supported(dtype, C)
-    if mode == 0 or not ops.mlp_fused_supported(dtype, C):
-        return False
-    if mode == 1:
-        return True
-    return C == 64 or (C == 128 and what.startswith('fwd'))
-
-
-def use_attn_block(dtype, C: int, dh: int, n_tok: int, training: bool = False) -> bool:
-    """Attention half of a block (norm1, qkv, partition attention, proj, LayerScale + residual) as ONE kernel per direction
-    (csrc/attn_block.hpp, one wave per partition) instead of LayerNorm + linear + attention core + linear (+ their
-    backward chain): where it is built (C = 64, dim_head 32, partitions of 33..96 tokens).  tuning.route_attn_block = 0 disables."""
-    # partitions of more than 64 tokens (Gen1: 8 x 10) have a fused forward only; a forward that keeps activations for a
-    # backward therefore takes the op-by-op chain there
-    if training and n_tok > 64:
-        return False
-    return tuning.get('route_attn_block') != 0 and ops.attn_block_supported(dtype, C, dh, n_tok)
-
-
-def use_lstm_scan(dtype, C: int, dws, T: int = 0, save: bool = True) -> bool:
-    """ConvLSTM with the time loop inside the kernel (csrc/lstm_scan.hpp) instead of one launch per step: only the 1x1-conv
-    cell (dws_conv False — every shipped config); by default where the weights stay resident in LDS (C <= 64), C = 128
-    (weights streamed from L2) with tuning.route_lstm_scan = 1 (all supported widths; the parity tests); 0 disables."""
-    mode = tuning.get('route_lstm_scan')
-    if mode == 0 or dws is not None or not ops.lstm_scan_supported(dtype, C):
-        return False
-    if mode == -1 and T == 1 and not save:
-        return False                     # one no-grad step (streaming inference): the per-step GEMM beats staging the scan's weights
-    return True if mode == 1 else (C <= 64 or ops.lstm_scan_saves_gates(dtype, C))
-
-
-def use_lstm_scan3(dtype, C: int, dws, T: int = 0, save: bool = True, M: int = 1 << 30) -> bool:
-    """ConvLSTM (bf16, C = 128 / 256) with the time loop in the kernel, the weights streamed from L2 in operand order and the gates
-    saved for the reverse scan (csrc/lstm_scan3.hpp): instead of 3 launches per step at C = 256 (weights too large for the chip),
-    instead of the register-resident-weight scan of lstm_scan.hpp at C = 128.
-    One no-grad step (streaming inference, T = 1) keeps the per-step GEMM: packing + streaming the weights buys nothing there."""
-    if dws is not None or not ops.lstm_scan3_supported(dtype, C):
-        return False
-    if C == 128 and M < 16384 and tuning.get('route_lstm_scan') != 0:
-        # few tokens per step (stage 3 of RVT-Tiny: 2560): the register-resident weights of lstm_scan.hpp win - 0.118 + 0.172 ms
-        # against 0.124 + 0.198; at 92160 tokens (stage 2 of RVT-Base) the streamed form does: 1.28 + 1.66 against 1.50 + 2.15
-        return False
-    return save or T > 1
 
 
 class SideStream:
@@ -186,12 +127,12 @@ class StageGeom:
 
 
 class StageSaved:
-    """Activations kept for backward (everything else is recomputed from these)."""
-    __slots__ = ('inp', 'y0', 'blocks', 'x_last', 'Hall', 'Call', 'gates', 'mask', 'xin_lstm', 'hconv', 'Csave', 'c0', 'scan3', 'train', '__weakref__')
+    """Activations kept for backward (everything else is recomputed from these), and the routes they were produced on."""
+    __slots__ = ('inp', 'y0', 'blocks', 'x_last', 'Hall', 'Call', 'gates', 'mask', 'xin_lstm', 'hconv', 'Csave', 'c0', 'routes', 'train', '__weakref__')
 
     def __init__(self):
         self.blocks: List[Dict[str, Tensor]] = []
-        self.scan3 = False
+        self.routes = None          # stage_driver.RvtStageRoutes of the forward: the ONLY thing the backward chooses its kernels by
         self.train = None           # set by the C-side training driver (rvt_amd/stage_driver.py: train_forward)
 
 
@@ -202,15 +143,17 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
     F_ = T * B
     H, W, C = g.H, g.W, g.C
     dt, dev = sw.conv_w.dtype, inp.device
-    if save and tuning.get('route_stage_driver_train') != 0:
+    u8 = inp.dtype == torch.uint8
+    call = stage_driver.StageCall(sw, g, dt, u8, inp.shape[-2] if u8 else 0, inp.shape[-1] if u8 else 0)
+    r = stage_driver.plan(sw, g, dt, T, B, save, token_mask, call)
+    if save and r.driver_covers and tuning.get('route_stage_driver_train') != 0:
         # the whole training forward of the stage as ONE library call (include/rvt_hip.h: rvt_stage_seq_train_fwd) where covered
-        from . import stage_driver
-        routes = stage_driver.train_routes(sw, g, dt, T, B, token_mask)
-        if routes is not None:
-            return stage_driver.train_forward(sw, g, inp, h0, c0, T, B, routes)
+        return stage_driver.train_forward(call, r, inp, h0, c0, T, B)
     sv = StageSaved() if save else None
+    if save:
+        sv.routes = r
 
-    if inp.dtype == torch.uint8:
+    if u8:
         # first stage on the loader's planes (T*B, Cin, h, w): cast + pad + conv + LayerNorm in one launch (csrc/stem.hpp)
         y0, x = ops.stem_fwd(inp, sw.conv_w, sw.ln_w, sw.ln_b, g.H_in, g.W_in, g.eps)
     else:
@@ -225,14 +168,14 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
 
     for pair in sw.blocks:
         for bw, window in ((pair[0], True), (pair[1], False)):
-            if use_attn_block(dt, C, g.dim_head, g.ph * g.pw, training=save):
+            if r.attn_block:
                 # maxvit.py:268 in one launch; backward recomputes q / k / v / P from the block input (nothing but `a`,
                 # the operand of the proj weight gradient, is kept)
                 xmid, a = ops.attn_block_fwd(x, bw['n1_w'], bw['n1_b'], bw['qkv_w'], bw['qkv_b'], bw['proj_w'], bw['proj_b'],
                                              bw['g1'], F_, H, W, C, g.dim_head, g.ph, g.pw, window, g.eps, want_a=save)
                 u = qkv = None
             else:
-                if ops.ln_linear_supported(dt, C, 3 * C):
+                if r.ln_linear:
                     # norm1 + qkv in one launch (csrc/ln_linear.hpp; C = 128); u is kept for the qkv weight gradient
                     u, qkv = ops.ln_linear_fwd(x, bw['n1_w'], bw['n1_b'], bw['qkv_w'], bw['qkv_b'], g.eps, want_u=save)
                     if bw['n1_w'] is None:
@@ -243,21 +186,17 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
                 a = ops.attn_fwd(qkv, F_, H, W, C, g.dim_head, g.ph, g.pw, window)    # maxvit.py:349-352
                 xmid = ops.linear_scale_res_fwd(a, bw['proj_w'], bw['proj_b'], bw['g1'], x)        # :353, :268
             v2 = None
-            hpre = False
-            if use_fused_mlp(dt, C, 'bwd_fused'):
+            if r.mlp_route == 1:
                 # the backward recomputes everything from xmid: inference-flavoured forward, nothing else kept (the no-grad
                 # forward takes the same kernel, so eval and training outputs are bit-identical)
                 xout, hg, hgp = ops.mlp_fwd(xmid, bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'], bw['fc2_w'], bw['fc2_b'],
                                             bw['g2'], g.eps, want_grad=False)
-            elif use_fused_mlp(dt, C, 'fwd_train' if save else 'fwd_infer'):
+            elif r.mlp_route == 2:
                 # training forward at C = 128: by default only the pre-activation h is kept (hg = h, hgp = None); the backward
                 # applies GELU on load in the fc2 weight gradient and GELU' in the epilogue of the fc2 input gradient
-                pre = save and tuning.get('route_mlp_store_pre') != 0 and not use_fused_mlp(dt, C, 'bwd')
-                r = ops.mlp_fwd(xmid, bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'], bw['fc2_w'], bw['fc2_b'], bw['g2'],
-                                g.eps, want_grad=save and not pre, want_v2=save, want_pre=pre)
-                xout, hg, hgp = r[:3]
-                hpre = pre
-                v2 = r[3] if save else None     # LN2(xmid), saved for the fc1 weight gradient
+                pre = bool(r.mlp_store_pre)
+                xout, hg, hgp, v2 = ops.mlp_fwd(xmid, bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'], bw['fc2_w'], bw['fc2_b'], bw['g2'],
+                                                g.eps, want_grad=not pre, want_v2=True, want_pre=pre)      # v2 = LN2(xmid), for the fc1 weight gradient
             else:
                 v2 = ops.layernorm_fwd(xmid, bw['n2_w'], bw['n2_b'], g.eps)
                 # MLP fc1 + exact GELU; GELU' is saved too so backward never re-evaluates erf (maxvit.py:100-112)
@@ -266,38 +205,36 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
             if save:
                 # the LayerNorm outputs are the B operands of the qkv / fc1 weight gradients: kept (1 row of C per token
                 # each, 288 GB of HBM) rather than recomputed — a recompute is a read + a write + the re-read
-                sv.blocks.append(dict(xin=x, qkv=qkv, a=a, xmid=xmid, hg=hg, hgp=hgp, u=u, v2=v2, hpre=hpre))
+                sv.blocks.append(dict(xin=x, qkv=qkv, a=a, xmid=xmid, hg=hg, hgp=hgp, u=u, v2=v2))
             x = xout
 
     Hall = torch.empty((T + 1, B, H, W, C), dtype=dt, device=dev)
     dws = sw.dws
     # a no-grad forward on the per-step route reads the incoming states where they are (streaming inference, T = 1: the two
     # state copies per stage were 5 % of the step); BPTT and the scan kernel want them in slot 0
-    scan3 = use_lstm_scan3(dt, C, dws, T, save, B * H * W)
-    direct0 = (not save) and h0 is not None and not scan3 and not use_lstm_scan(dt, C, dws, T, save) and h0.dtype == dt and h0.is_contiguous() \
+    direct0 = (not save) and h0 is not None and r.lstm_route == 0 and h0.dtype == dt and h0.is_contiguous() \
         and c0 is not None and c0.dtype == torch.float32 and c0.is_contiguous()
     if h0 is None:
         Hall[0].zero_()                                                           # rnn.py:43-47
     elif not direct0:
         Hall[0].copy_(h0)
-    if scan3:
+    if r.lstm_route == 3:
         # wide stage: all T steps in ONE launch, weights streamed in operand order, gates + cell states saved in dump order
         c_last = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-        rows = ops.lstm_scan3_rows(C, B * H * W)
+        rows = ops.lstm_scan3_rows(C, B * H * W, r.lstm_scan3_rb)
         Csave = torch.empty((T, rows, C), dtype=dt, device=dev) if save else None
         gsave = torch.empty((T, rows, 4 * C), dtype=dt, device=dev) if save else None
-        ops.lstm_scan3_fwd(x.view(T, B, H, W, C), Hall, c0, c_last, Csave, sw.scan3_packed(bwd=False), sw.lstm_bn, gsave)
+        ops.lstm_scan3_fwd(x.view(T, B, H, W, C), Hall, c0, c_last, Csave, sw.scan3_packed(bwd=False), sw.lstm_bn, gsave, r.lstm_scan3_rb)
         if save:
             sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, None, gsave
             sv.xin_lstm, sv.hconv, sv.Csave, sv.c0 = x, None, Csave, (None if c0 is None else c0.clone())
-            sv.scan3 = True
         return Hall, c_last, sv
-    if use_lstm_scan(dt, C, dws, T, save):
+    if r.lstm_route != 0:
         # all T steps in ONE launch: h / c stay on chip, BPTT keeps only a T-typed copy of the cell states
         c_last = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
         Csave = torch.empty((T, B, H, W, C), dtype=dt, device=dev) if save else None
         # C = 128 (bf16): weights in the register file; the gates are stored for a reverse scan that keeps W^T in registers
-        gsave = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev) if save and ops.lstm_scan_saves_gates(dt, C) else None
+        gsave = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev) if save and r.lstm_route == 2 else None
         ops.lstm_scan_fwd(x.view(T, B, H, W, C), Hall, c0, c_last, Csave, sw.lstm_wn, sw.lstm_bn, gates_out=gsave)
         if save:
             sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, None, gsave
@@ -354,9 +291,9 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
     dt, dev = sv.y0.dtype, sv.y0.device
     f32 = torch.float32
     G = sg.g
+    r = sv.routes                # what the forward was planned with: the tuning record is not consulted again
     if sv.train is not None:
         # BPTT + block / conv backward of the stage as ONE library call (rvt_stage_seq_bwd); the LayerScale fold / conv unpack follow
-        from . import stage_driver
         out = stage_driver.train_backward(sw, g, sv, dH, dc_last, T, B, need_input_grad, prev_cot, sg, pre)
         if finalize is not None:
             finalize()
@@ -367,20 +304,20 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
     dws = sw.dws
     lstm_wgrad_done = False
     dz = None
-    if sv.scan3:
+    assert (sv.gates is not None) == (r.lstm_route != 1) and (sv.Csave is not None) == (r.lstm_route != 0)
+    if r.lstm_route == 3:
         # reverse scan of a wide stage in ONE launch on the saved gates; dz goes to the weight-gradient GEMM below
         dh_rec = torch.empty((B, H, W, C), dtype=dt, device=dev)
         dc_rec = torch.empty((B, H, W, C), dtype=f32, device=dev)
         dz = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev)
         ops.lstm_scan3_bwd(sv.gates, sv.Csave, sv.c0, dH, None if dc_last is None else dc_last.to(f32).contiguous(),
-                           sw.scan3_packed(bwd=True), dx, dz, dh_rec, dc_rec)
-    elif sv.Csave is not None:
+                           sw.scan3_packed(bwd=True), dx, dz, dh_rec, dc_rec, r.lstm_scan3_rb)
+    elif r.lstm_route != 0:
         # reverse scan in ONE launch: gates recomputed from (x_t, h_{t-1}), dc / dh_rec in registers across t; where built
         # (bf16, C <= 64) the weight gradients are accumulated in the same kernel and dz never exists in HBM
         dh_rec = torch.empty((B, H, W, C), dtype=dt, device=dev)
         dc_rec = torch.empty((B, H, W, C), dtype=f32, device=dev)
-        lstm_wgrad_done = sv.gates is None and tuning.get('route_lstm_scan_wgrad') != 0 and \
-            ops.lstm_scan_wgrad_supported(dt, C, B * H * W)
+        lstm_wgrad_done = bool(r.lstm_scan_wgrad)
         if not lstm_wgrad_done:
             dz = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev)
         ops.lstm_scan_bwd(sv.xin_lstm.view(T, B, H, W, C), sv.Hall, sv.Csave, sv.c0, dH,
@@ -444,14 +381,15 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
             # MLP branch: xout = xmid + g2 * (gelu(hd) W2^T + b2).  The weight-gradient GEMM delivers the raw products
             # S2 = dxout^T g and cs2 = colsum(dxout); LayerScale is folded in by the finalize table launch.
             dn2w, dn2b = G(bp + 'norm2.weight'), G(bp + 'norm2.bias')
-            if s['hg'] is None:
+            assert (s['hg'] is None) == (r.mlp_route == 1) and (s['qkv'] is None) == bool(r.attn_block)
+            if r.mlp_route == 1:
                 # everything on chip: recompute, both input-gradient products, LayerNorm backward and the fc1 / fc2 weight
                 # gradients (accumulated in registers) in one kernel; nothing for the weight-gradient stream to do
                 # two launches, cut along the critical path: the input-gradient half here, the weight-gradient half (which
                 # needs all 2 x 64 x 256 accumulators) on the weight-gradient stream
                 # (round 4: ONE launch where the library supports it — the weight-gradient kernel hands dh to two waves that form
                 # dh W1, LayerNorm backward in the staging role; otherwise)
-                if ops.mlp_bwd_both_supported(dt, C):
+                if r.mlp_bwd_both:
                     dxmid = ops.mlp_bwd_recompute_both(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'], bw['fc2_wt'],
                                                        bw['fc1_wt'], dn2w, dn2b, G(bp + 'mlp.net.0.0.weight'),
                                                        G(bp + 'mlp.net.0.0.bias'), G(bp + 'S2'), G(bp + 'cs2'), g.eps)
@@ -465,13 +403,13 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                                                         bw['fc2_wt'], bw['fc1_wt'], dn2w, dn2b, g.eps)
             else:
                 def fc2_wgrad_fn(dx=dx, s=s, bp=bp):
-                    ops.linear_wgrad(dx, s['hg'], G(bp + 'S2'), gelu_in=s['hpre'], colsum_out=G(bp + 'cs2'))
+                    ops.linear_wgrad(dx, s['hg'], G(bp + 'S2'), gelu_in=bool(r.mlp_store_pre), colsum_out=G(bp + 'cs2'))
                 side.run(fc2_wgrad_fn, dx, s['hg'])
-                fused = use_fused_mlp(dt, C, 'bwd')
+                fused = bool(r.mlp_bwd_dgrad)
                 if fused:       # fc2 dgrad * gp, fc1 dgrad and LayerNorm-2 backward (+ residual) in one kernel
                     dhd, dxmid = ops.mlp_bwd_dgrad(dx, s['hgp'], s['xmid'], bw['n2_w'], bw['fc2_wt'], bw['fc1_wt'], dn2w,
                                                    dn2b, g.eps)
-                elif s['hpre']:
+                elif r.mlp_store_pre:
                     dhd = ops.linear_dgrad(dx, bw['fc2_wt'], gelu_pre=s['hg'])
                 else:
                     dhd = ops.linear_dgrad(dx, bw['fc2_wt'], mul=s['hgp'])
@@ -480,7 +418,7 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                     ops.linear_wgrad(dhd, v2, G(bp + 'mlp.net.0.0.weight'), colsum_out=G(bp + 'mlp.net.0.0.bias'))
                 side.run(fc1_wgrad_fn, dhd, s['xmid'])
                 if not fused:
-                    if ops.linear_dgrad_ln_supported(dt, C, 4 * C):     # fc1 input gradient + norm2 backward + residual: one launch
+                    if r.dgrad_ln_fc1:     # fc1 input gradient + norm2 backward + residual: one launch
                         dxmid = ops.linear_dgrad_ln(dhd, bw['fc1_w'], s['xmid'], dx, bw['n2_w'], dn2w, dn2b, g.eps)
                     else:
                         dv2 = ops.linear_dgrad(dhd, bw['fc1_wt'])
@@ -491,10 +429,10 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
             def proj_wgrad_fn(dxmid=dxmid, s=s, bp=bp):
                 ops.linear_wgrad(dxmid, s['a'], G(bp + 'S1'), colsum_out=G(bp + 'cs1'))
             side.run(proj_wgrad_fn, dxmid, s['a'])
-            if s['qkv'] is None:
+            if r.attn_block:
                 # fused: proj / attention / qkv input gradients and the norm1 backward in one launch (from the block input)
                 has_n1 = bw['n1_w'] is not None
-                if bi_flat == 0 and not has_n1 and sv.mask is None and tuning.get('route_attn_preln') != 0:
+                if bi_flat == 0 and r.attn_preln:
                     # the stage's first block: its input is the down-sampling norm's output, and nothing sits between them -
                     # the same launch carries the gradient through that norm (dy0 instead of dx)
                     dy0_fused, dqkv = ops.attn_block_bwd_preln(s['xin'], sv.y0, dxmid, sw.ln_w, bw['qkv_w'], bw['qkv_b'], bw['proj_wt'],
@@ -520,15 +458,14 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
             def qkv_wgrad_fn(dqkv=dqkv, s=s, bp=bp):
                 ops.linear_wgrad(dqkv, s['u'], G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
             side.run(qkv_wgrad_fn, dqkv, s['xin'])
-            if bw['n1_w'] is None and bi_flat == 0 and sv.mask is None and tuning.get('route_attn_preln') != 0 and \
-                    ops.linear_dgrad_ln_supported(dt, C, 3 * C):
+            if bi_flat == 0 and r.attn_preln:
                 # the stage's first block: qkv input gradient + residual cotangent carried through the down-sampling norm (one launch)
                 dy0_fused = ops.linear_dgrad_preln(dqkv, bw['qkv_w'], sv.y0, dxmid, sw.ln_w, G(pre + 'downsample_cf2cl.norm.weight'),
                                                    G(pre + 'downsample_cf2cl.norm.bias'), g.eps)
                 dx = None
             elif bw['n1_w'] is None:
                 dx = ops.linear_dgrad(dqkv, bw['qkv_wt'], add=dxmid)
-            elif ops.linear_dgrad_ln_supported(dt, C, 3 * C):           # qkv input gradient + norm1 backward + residual: one launch
+            elif r.dgrad_ln_qkv:           # qkv input gradient + norm1 backward + residual: one launch
                 dx = ops.linear_dgrad_ln(dqkv, bw['qkv_w'], s['xin'], dxmid, bw['n1_w'], G(bp + 'norm1.weight'),
                                          G(bp + 'norm1.bias'), g.eps)
             else:
@@ -555,8 +492,7 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
     side.run(conv_wgrad_fn, sv.inp, dy0)
     d_in = None
     if need_input_grad:
-        if sw.conv_wd4 is not None and tuning.get('route_conv_dgrad4') != 0 and \
-                ops.conv_dgrad4_supported(dt, g.H_in, g.W_in, g.Cin, C, g.k, g.stride, g.pad, F_):
+        if r.conv_dgrad4:
             d_in = ops.conv_dgrad4(dy0, sw.conv_wd4, prev_cot, g.H_in, g.W_in, g.Cin)      # one launch (2 x 2 pixel blocks)
         else:
             d_in = ops.conv_dgrad(dy0, sw.conv_wd, prev_cot, g.H_in, g.W_in, g.Cin, g.k, g.stride, g.pad)

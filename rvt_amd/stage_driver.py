@@ -1,9 +1,13 @@
-"""Binding of the C-side stage driver (include/rvt_hip.h: rvt_stage_seq_fwd) — the no-grad forward of one stage over a whole
-sequence as ONE library call (validation / streaming inference, reference modules/detection.py:231-255).
+"""Binding of the C-side stage drivers (include/rvt_hip.h) and of the route planner they share with the host loop.
 
-rvt_amd/stage.py stays the host loop of the TRAINING forward / backward (it owns the saved-activation bookkeeping); this module
-builds the descriptor records the library reads and calls it.  Python only allocates: the output slab, the final cell state and a
-grow-only workspace per stream."""
+  * plan(): the routes of one stage, decided ONCE per forward by the library (rvt_stage_routes) and kept with the saved activations
+    (StageSaved.routes), so that the backward runs what the forward prepared for;
+  * stage_seq_fwd(): the no-grad forward of one stage over a whole sequence as ONE library call (validation / streaming inference,
+    reference modules/detection.py:231-255);
+  * train_forward() / train_backward(): the training forward and the BPTT backward as one call each, where routes.driver_covers.
+
+rvt_amd/stage.py is the operator-by-operator host loop for everything else (token masks, DWS-ConvLSTM, the second weight-gradient
+stream, the saving fused-MLP flavour).  Python only allocates: outputs, saved activations and a grow-only workspace per stream."""
 from __future__ import annotations
 
 import ctypes
@@ -26,11 +30,6 @@ class RvtStageDesc(ctypes.Structure):
                 ('stride', _i), ('pad', _i), ('ph', _i), ('pw', _i), ('dim_head', _i), ('num_blocks', _i), ('eps', _f),
                 ('inp_u8', _i), ('h_raw', _i), ('w_raw', _i), ('conv_w', _vp), ('ln_w', _vp), ('ln_b', _vp),
                 ('blocks', ctypes.POINTER(RvtBlockWeights)), ('lstm_w', _vp), ('lstm_b', _vp), ('lstm_wn', _vp), ('lstm_bn', _vp)]
-
-
-def supported(sw, token_mask) -> bool:
-    """What the driver covers: the 1x1-conv ConvLSTM of every shipped config, no token masks."""
-    return token_mask is None and sw.dws is None
 
 
 class StageCall:
@@ -62,41 +61,48 @@ class StageCall:
     def ws_bytes(self, T: int, B: int) -> int:
         n = self._ws_bytes.get((T, B))
         if n is None:
-            n = int(_lib().rvt_stage_seq_fwd_ws_bytes(ctypes.byref(self.desc), T, B))
+            n = int(L.get_lib().rvt_stage_seq_fwd_ws_bytes(ctypes.byref(self.desc), T, B))
             self._ws_bytes[(T, B)] = n
         return n
 
 
-_bound = None
-
-
-def _lib():
-    global _bound
-    lib = L.get_lib()
-    if _bound is not lib:
-        lib.rvt_stage_seq_fwd_ws_bytes.restype = ctypes.c_size_t
-        lib.rvt_stage_seq_fwd_ws_bytes.argtypes = [_vp, _i, _i]
-        lib.rvt_stage_seq_fwd.restype = _i
-        lib.rvt_stage_seq_fwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _i, _i, _vp]
-        _bound = lib
-    return lib
-
-
 _WS = {}
+
+
+def _workspace(kind: str, like: torch.Tensor, n: int):
+    """(stream handle, grow-only byte workspace of at least n bytes for `kind` on that stream)."""
+    st, dev = L.stream_of(like), like.device
+    key = (kind, dev.type, dev.index, 0 if st is None else int(st))
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _WS[key] = torch.empty(n, dtype=torch.uint8, device=dev)
+    return st, ws
+
+
+class RvtStageRoutes(ctypes.Structure):
+    """Mirror of `struct RvtStageRoutes` (include/rvt_hip.h): which kernels a stage runs."""
+    _fields_ = [(n, _i) for n in ('attn_block', 'ln_linear', 'mlp_route', 'mlp_bwd_both', 'dgrad_ln_qkv', 'dgrad_ln_fc1', 'lstm_route',
+                                  'lstm_scan_wgrad', 'conv_dgrad4', 'attn_preln', 'mlp_store_pre', 'mlp_bwd_dgrad', 'lstm_scan3_rb',
+                                  'driver_covers')]
+
+
+def plan(sw, g, dt, T: int, B: int, save: bool, token_mask, call: Optional[StageCall] = None) -> RvtStageRoutes:
+    """The routes of one stage forward (and of its backward when save).  `call`: the stage's descriptor where the caller has one."""
+    call = call or StageCall(sw, g, dt, False, 0, 0)
+    r = RvtStageRoutes()
+    lib = L.get_lib()
+    if lib.rvt_stage_routes(ctypes.byref(call.desc), T, B, int(save), int(sw.dws is not None), int(token_mask is not None), ctypes.byref(r)) != 0:
+        raise RuntimeError(f'rvt_stage_routes failed: {lib.rvt_last_error().decode()}')
+    r.conv_dgrad4 = int(r.conv_dgrad4 and sw.conv_wd4 is not None)      # (the packed weight copy exists only for stages with an input gradient)
+    return r
 
 
 def stage_seq_fwd(call: StageCall, inp: torch.Tensor, h0: Optional[torch.Tensor], c0: Optional[torch.Tensor], T: int, B: int) \
         -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (Hall (T+1,B,H,W,C) in the compute dtype — slot 0 scratch, slots 1..T = h_t —, c_last (B,H,W,C) fp32)."""
     g, dt, dev = call.g, call.dtype, inp.device
-    lib = _lib()
-    st = L.stream_of(inp)
-    n = call.ws_bytes(T, B)
-    key = (dev.type, dev.index, 0 if st is None else int(st))
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(n, dtype=torch.uint8, device=dev)
-        _WS[key] = ws
+    lib = L.get_lib()
+    st, ws = _workspace('fwd', inp, call.ws_bytes(T, B))
     Hall = torch.empty((T + 1, B, g.H, g.W, g.C), dtype=dt, device=dev)
     c_last = torch.empty((B, g.H, g.W, g.C), dtype=torch.float32, device=dev)
     if h0 is not None:
@@ -109,8 +115,8 @@ def stage_seq_fwd(call: StageCall, inp: torch.Tensor, h0: Optional[torch.Tensor]
 
 
 # ---- training-side driver (round 6; include/rvt_hip.h: rvt_stage_seq_train_fwd / rvt_stage_seq_bwd, csrc/capi_train.hip) ----------------
-# The host decides the routes (the predicates of rvt_amd/stage.py - ONE place) and owns every tensor that outlives a call; the
-# library sequences the launches.  `StageSaved` is filled exactly as the Python host loop fills it, so either backward can consume it.
+# plan() decides the routes; the host owns every tensor that outlives a call; the library sequences the launches.  `StageSaved` is filled
+# exactly as the Python host loop fills it, so either backward can consume it.
 class RvtBlockSaved(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ('xin', 'u', 'qkv', 'a', 'xmid', 'v2', 'hg', 'hgp', 'xout')]
 
@@ -121,28 +127,10 @@ class RvtBlockTrain(ctypes.Structure):
 
 
 class RvtStageTrain(ctypes.Structure):
-    _fields_ = [('struct_bytes', _i)] + [(n, _i) for n in ('attn_block', 'ln_linear', 'mlp_route', 'mlp_bwd_both', 'dgrad_ln_qkv',
-                                                          'dgrad_ln_fc1', 'lstm_route', 'lstm_scan_wgrad', 'conv_dgrad4', 'attn_preln')] + \
+    _fields_ = [('struct_bytes', _i), ('routes', RvtStageRoutes)] + \
                [('saved', ctypes.POINTER(RvtBlockSaved)), ('tb', ctypes.POINTER(RvtBlockTrain))] + \
                [(n, _vp) for n in ('y0', 'x0', 'Hall', 'c_last', 'Csave', 'gates', 'Call', 'c0_saved', 'lstm_wp3', 'lstm_wtp3', 'lstm_wt',
                                    'conv_wd4', 'conv_wd', 'd_lstm_w', 'd_lstm_b', 'd_ln_w', 'd_ln_b', 'd_raw_conv')]
-
-
-_tbound = None
-
-
-def _tlib():
-    global _tbound
-    lib = L.get_lib()
-    if _tbound is not lib:
-        lib.rvt_stage_seq_train_fwd.restype = _i
-        lib.rvt_stage_seq_train_fwd.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _vp]
-        lib.rvt_stage_seq_bwd_ws_bytes.restype = ctypes.c_size_t
-        lib.rvt_stage_seq_bwd_ws_bytes.argtypes = [_vp, _vp, _i, _i]
-        lib.rvt_stage_seq_bwd.restype = _i
-        lib.rvt_stage_seq_bwd.argtypes = [_vp] * 10 + [ctypes.c_size_t, _i, _i, _vp]
-        _tbound = lib
-    return lib
 
 
 class TrainCall:
@@ -150,55 +138,19 @@ class TrainCall:
     __slots__ = ('call', 'tr', 'saved_arr', 'tb_arr', 'inp', 'keep')
 
 
-def train_routes(sw, g, dt, T: int, B: int, token_mask) -> Optional[dict]:
-    """The routes stage_seq_forward / stage_seq_backward would take, or None where the C driver does not cover them."""
-    from . import ops, tuning
-    from .stage import use_attn_block, use_fused_mlp, use_lstm_scan, use_lstm_scan3
-    if token_mask is not None or sw.dws is not None or tuning.get('route_wgrad_stream') != 0:
-        return None
-    C = g.C
-    r = dict(attn_block=int(use_attn_block(dt, C, g.dim_head, g.ph * g.pw, training=True)))
-    r['ln_linear'] = int(not r['attn_block'] and ops.ln_linear_supported(dt, C, 3 * C))
-    if use_fused_mlp(dt, C, 'bwd_fused'):
-        r['mlp_route'] = 1
-    elif use_fused_mlp(dt, C, 'fwd_train'):
-        return None                          # LDS-staged fused MLP that saves GELU / GELU': host loop
-    else:
-        r['mlp_route'] = 0
-    r['mlp_bwd_both'] = int(r['mlp_route'] == 1 and ops.mlp_bwd_both_supported(dt, C))
-    r['dgrad_ln_qkv'] = int(ops.linear_dgrad_ln_supported(dt, C, 3 * C))
-    r['dgrad_ln_fc1'] = int(ops.linear_dgrad_ln_supported(dt, C, 4 * C))
-    Ms = B * g.H * g.W
-    if use_lstm_scan3(dt, C, sw.dws, T, True, Ms):
-        r['lstm_route'] = 3
-    elif use_lstm_scan(dt, C, sw.dws, T, True):
-        r['lstm_route'] = 2 if ops.lstm_scan_saves_gates(dt, C) else 1
-    else:
-        r['lstm_route'] = 0
-    r['lstm_scan_wgrad'] = int(r['lstm_route'] == 1 and tuning.get('route_lstm_scan_wgrad') != 0 and ops.lstm_scan_wgrad_supported(dt, C, Ms))
-    r['conv_dgrad4'] = int(sw.conv_wd4 is not None and tuning.get('route_conv_dgrad4') != 0 and
-                           ops.conv_dgrad4_supported(dt, g.H_in, g.W_in, g.Cin, C, g.k, g.stride, g.pad, T * B))
-    # (the first block of a stage never has a norm1: maxvit_rnn.py:153 `skip_first_norm`; no token mask on this route)
-    r['attn_preln'] = int((r['attn_block'] or ops.linear_dgrad_ln_supported(dt, C, 3 * C)) and tuning.get('route_attn_preln') != 0 and
-                          sw.blocks[0][0]['n1_w'] is None)
-    return r
-
-
-def train_forward(sw, g, inp: torch.Tensor, h0, c0, T: int, B: int, routes: dict):
+def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0, c0, T: int, B: int):
     """Training forward of one stage in ONE library call.  Returns (Hall, c_last, StageSaved) like stage.stage_seq_forward."""
     from . import ops
     from .stage import StageSaved
+    sw, g = call.sw, call.g
     dt, dev = sw.conv_w.dtype, inp.device
     H, W, C = g.H, g.W, g.C
     F_ = T * B
     E = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)
-    u8 = inp.dtype == torch.uint8
-    call = StageCall(sw, g, dt, u8, inp.shape[-2] if u8 else 0, inp.shape[-1] if u8 else 0)
     tr = RvtStageTrain()
-    tr.struct_bytes = ctypes.sizeof(RvtStageTrain)
-    for k, v in routes.items():
-        setattr(tr, k, v)
+    tr.struct_bytes, tr.routes = ctypes.sizeof(RvtStageTrain), routes
     sv = StageSaved()
+    sv.routes = routes
     y0, x0 = E(F_, H, W, C), E(F_, H, W, C)
     sv.inp, sv.y0, sv.mask = inp, y0, None
     nb = 2 * g.num_blocks
@@ -209,15 +161,15 @@ def train_forward(sw, g, inp: torch.Tensor, h0, c0, T: int, B: int, routes: dict
         for bw in pair:
             has_n1 = bw['n1_w'] is not None
             s = dict(xin=x, qkv=None, a=E(F_, H, W, C), xmid=E(F_, H, W, C), hg=None, hgp=None, u=None, v2=None, hpre=False)
-            if not routes['attn_block']:
+            if not routes.attn_block:
                 s['qkv'] = E(F_, H, W, 3 * C)
                 s['u'] = E(F_, H, W, C) if has_n1 else x
-            if routes['mlp_route'] == 0:
+            if routes.mlp_route == 0:
                 s['v2'], s['hg'], s['hgp'] = E(F_, H, W, C), E(F_, H, W, 4 * C), E(F_, H, W, 4 * C)
             xout = E(F_, H, W, C)
             b = saved_arr[i]
             b.xin, b.a, b.xmid, b.xout = L.ptr(x), L.ptr(s['a']), L.ptr(s['xmid']), L.ptr(xout)
-            b.qkv, b.u = L.ptr(s['qkv']), (L.ptr(s['u']) if (has_n1 and not routes['attn_block']) else None)
+            b.qkv, b.u = L.ptr(s['qkv']), (L.ptr(s['u']) if (has_n1 and not routes.attn_block) else None)
             b.v2, b.hg, b.hgp = L.ptr(s['v2']), L.ptr(s['hg']), L.ptr(s['hgp'])
             sv.blocks.append(s)
             x = xout
@@ -228,10 +180,10 @@ def train_forward(sw, g, inp: torch.Tensor, h0, c0, T: int, B: int, routes: dict
     else:
         Hall[0].copy_(h0)
     c_last = E(B, H, W, C, dtype=torch.float32)
-    lr = routes['lstm_route']
+    lr = routes.lstm_route
     Csave = gates = Call = None
     if lr == 3:
-        rows = ops.lstm_scan3_rows(C, B * H * W)
+        rows = ops.lstm_scan3_rows(C, B * H * W, routes.lstm_scan3_rb)
         Csave, gates = E(T, rows, C), E(T, rows, 4 * C)
         tr.lstm_wp3 = L.ptr(sw.scan3_packed(bwd=False))
     elif lr in (1, 2):
@@ -247,20 +199,17 @@ def train_forward(sw, g, inp: torch.Tensor, h0, c0, T: int, B: int, routes: dict
     tr.saved = ctypes.cast(saved_arr, ctypes.POINTER(RvtBlockSaved))
     tr.y0, tr.x0, tr.Hall, tr.c_last = L.ptr(y0), L.ptr(x0), L.ptr(Hall), L.ptr(c_last)
     tr.Csave, tr.gates, tr.Call = L.ptr(Csave), L.ptr(gates), L.ptr(Call)
-    lib = _tlib()
+    lib = L.get_lib()
     rc = lib.rvt_stage_seq_train_fwd(ctypes.byref(call.desc), ctypes.byref(tr), L.ptr(inp), L.ptr(c0) if lr != 0 else None, T, B, L.stream_of(inp))
     if rc != 0:
         raise RuntimeError(f'rvt_stage_seq_train_fwd failed: {lib.rvt_last_error().decode()}')
     sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, Call, gates
     sv.xin_lstm, sv.hconv, sv.Csave = x, None, Csave
     sv.c0 = None if (c0 is None or lr == 0) else c0.clone()      # (scan routes: the state the forward saw; RNNStates resets states in place)
-    sv.scan3 = lr == 3
     tc = TrainCall()
     tc.call, tc.tr, tc.saved_arr, tc.tb_arr, tc.inp, tc.keep = call, tr, saved_arr, None, inp, (y0, x0)
     sv.train = tc
-    if lr == 0:
-        c_last = c_last      # (copied out of Call[T] by the library: BPTT keeps the T+1-slot array)
-    return Hall, c_last, sv
+    return Hall, c_last, sv       # (per-step route: c_last was copied out of Call[T] by the library, BPTT keeps the T+1-slot array)
 
 
 def train_backward(sw, g, sv, dH, dc_last, T: int, B: int, need_input_grad: bool, prev_cot, sg, pre: str):
@@ -290,25 +239,19 @@ def train_backward(sw, g, sv, dH, dc_last, T: int, B: int, need_input_grad: bool
     tr.tb = ctypes.cast(tb_arr, ctypes.POINTER(RvtBlockTrain))
     tr.c0_saved = L.ptr(sv.c0)
     tr.lstm_wt, tr.conv_wd4, tr.conv_wd = L.ptr(sw.lstm_wt), L.ptr(sw.conv_wd4), L.ptr(getattr(sw, 'conv_wd', None))
-    if tr.lstm_route == 3:
+    if tr.routes.lstm_route == 3:
         tr.lstm_wtp3 = L.ptr(sw.scan3_packed(bwd=True))
     tr.d_lstm_w, tr.d_lstm_b = L.ptr(G(pre + 'lstm.conv1x1.weight')), L.ptr(G(pre + 'lstm.conv1x1.bias'))
     tr.d_ln_w, tr.d_ln_b = L.ptr(G(pre + 'downsample_cf2cl.norm.weight')), L.ptr(G(pre + 'downsample_cf2cl.norm.bias'))
     tr.d_raw_conv = L.ptr(G('raw/conv'))
-    if dH is None and tr.lstm_route == 0:
+    if dH is None and tr.routes.lstm_route == 0:
         dH = torch.zeros((T, B, H, W, C), dtype=dt, device=dev)
     dcl = None if dc_last is None else dc_last.to(torch.float32).contiguous()
     dh0 = torch.empty((B, H, W, C), dtype=dt, device=dev)
     dc0 = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
     d_in = torch.empty((T * B, g.H_in, g.W_in, g.Cin), dtype=dt, device=dev) if need_input_grad else None
-    lib = _tlib()
-    st = L.stream_of(sv.y0)
-    n = int(lib.rvt_stage_seq_bwd_ws_bytes(ctypes.byref(call.desc), ctypes.byref(tr), T, B))
-    key = ('train', dev.type, dev.index, 0 if st is None else int(st))
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(n, dtype=torch.uint8, device=dev)
-        _WS[key] = ws
+    lib = L.get_lib()
+    st, ws = _workspace('train', sv.y0, int(lib.rvt_stage_seq_bwd_ws_bytes(ctypes.byref(call.desc), ctypes.byref(tr), T, B)))
     rc = lib.rvt_stage_seq_bwd(ctypes.byref(call.desc), ctypes.byref(tr), L.ptr(tc.inp), L.ptr(dH), L.ptr(dcl), L.ptr(prev_cot), L.ptr(d_in),
                                L.ptr(dh0), L.ptr(dc0), L.ptr(ws), ws.numel(), T, B, st)
     if rc != 0:

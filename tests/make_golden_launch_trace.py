@@ -1,0 +1,163 @@
+"""Launch traces of the backbone's Python host loop: which entry points of include/rvt_hip.h a step calls, in which order,
+with which integer / float arguments and which pointers NULL.  A refactor of the host code must leave every trace unchanged.
+
+    python -m tests.make_golden_launch_trace --backend emu        (CPU emulator build of the kernel sources)
+    python -m tests.make_golden_launch_trace --backend hip        (MI355X, production route)
+
+rewrites the cases of that backend in tests/golden/launch_trace.json (per case: launch count, {name: count} histogram, SHA-256
+of the canonical sequence).  The recorder only wraps `rvt_amd._lib.call` and reads `_lib._SIGS`, so it runs unchanged on any
+revision; the golden is recorded on the revision BEFORE a change and tests/test_launch_trace.py replays it on the one after.
+The host loop is forced (route_stage_driver = route_stage_driver_train = 0): the C-side drivers issue their launches inside one
+library call, and tests/test_stage_driver.py ties them to the host loop bit for bit.
+
+One normalisation: `rb`, the tile factor rvt_lstm_scan3_fwd / _bwd take as their last argument before the stream (absent when
+the golden was recorded: the library read it from the tuning record), is taken out of the tuple and returned separately."""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+
+import torch
+
+from rvt_amd import RNNDetector, _lib, backbone_config, tuning
+from tests import casegen
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_trace.json')
+MODES = ('train', 'nograd', 'stream')
+HOST_LOOP = dict(route_stage_driver=0, route_stage_driver_train=0)
+_SCAN3_ARGS = {'rvt_lstm_scan3_fwd': 13, 'rvt_lstm_scan3_bwd': 15}      # argument counts without `rb`
+
+# ---- emulator cases: (casegen name, dtype) x tuning on top of TEST_GEOMETRY x mode ----
+EMU_MODELS = [('micro', 'f32'), ('micro', 'bf16'), ('micro_mask', 'f32'), ('micro_dws_xh', 'f32'), ('micro_dws_hidden', 'f32'),
+              ('micro_dh24', 'f32')]
+EMU_TUNINGS = {'test_geometry': {}, 'fused_mlp': dict(route_fused_mlp=1),
+               'op_by_op': dict(route_lstm_scan=0, route_fused_mlp=0, route_attn_block=0)}
+# ---- MI355X cases on the production route: (size, dataset, dtype, T, B, extra tuning) x mode ----
+OP_BY_OP = dict(route_fused_mlp=0, route_mlp_bwd_fused=0, route_attn_block=0, route_lstm_scan=0, route_lstm_scan_wgrad=0, lstm_scan3=0,
+                mlp_stream=0, ln_linear=0, mlp_chain=0, dgrad_ln=0, route_conv_dgrad4=0, conv_wgrad_tn=0, attn_staged=0, stem=0,
+                ppgemm=0)                                # = tests/test_production_route.py::OP_BY_OP (asserted by the test)
+HIP_MODELS = {'base_b2': ('base', 'gen4', 'bf16', 3, 2, {}), 'base_b8': ('base', 'gen4', 'bf16', 3, 8, {}),
+              'tiny_gen1_b8': ('tiny', 'gen1', 'bf16', 3, 8, {}), 'base_f32_b1': ('base', 'gen4', 'f32', 2, 1, {}),
+              'base_b2_op_by_op': ('base', 'gen4', 'bf16', 3, 2, OP_BY_OP)}
+DTYPES = {'f32': torch.float32, 'bf16': torch.bfloat16}
+
+
+def emu_cases():
+    return [(f'emu/{n}/{d}/{t}/{m}', n, d, t, m) for n, d in EMU_MODELS for t in EMU_TUNINGS for m in MODES]
+
+
+def hip_cases():
+    return [(f'hip/{k}/{m}', k, m) for k in HIP_MODELS for m in MODES]
+
+
+def canonical(name, args):
+    """(entry of the canonical sequence, rb or None)."""
+    sig = _lib._SIGS[name]
+    assert len(sig) == len(args), (name, len(sig), len(args))
+    out = [name]
+    for ty, a in zip(sig, args):
+        if ty is ctypes.c_void_p:
+            out.append(int(a is not None and int(a) != 0))
+        elif ty is ctypes.c_float:
+            out.append(repr(float(a)))
+        else:
+            out.append(int(a))
+    rb = None
+    if name in _SCAN3_ARGS and len(args) == _SCAN3_ARGS[name] + 1:
+        rb = out.pop(-2)
+    return out, rb
+
+
+def record(fn):
+    """Run fn() with every library launch recorded.  Returns (canonical sequence, [(name, C, rb)] of the lstm_scan3 launches)."""
+    seq, rbs = [], []
+    orig = _lib.call
+
+    def rec(name, *args):
+        entry, rb = canonical(name, args)
+        seq.append(entry)
+        if rb is not None:
+            rbs.append((name, int(args[-4]), rb))        # (.., dtype, M, C, T_steps, rb, stream)
+        return orig(name, *args)
+    _lib.call = rec
+    try:
+        fn()
+    finally:
+        _lib.call = orig
+    return seq, rbs
+
+
+def summary(seq):
+    hist = {}
+    for e in seq:
+        hist[e[0]] = hist.get(e[0], 0) + 1
+    return dict(count=len(seq), hist=dict(sorted(hist.items())), sha256=hashlib.sha256(json.dumps(seq).encode()).hexdigest())
+
+
+def run_mode(m, xs, masks, mode):
+    T = xs.shape[0]
+    if mode == 'train':
+        feats, _ = m.forward_sequence(xs, None, masks)
+        sum(feats[s].float().sum() for s in (1, 2, 3, 4)).backward()
+    elif mode == 'nograd':
+        with torch.no_grad():
+            m.forward_sequence(xs, None, masks)
+    else:
+        states = None
+        with torch.no_grad():
+            for t in range(T):
+                _, states = m(xs[t], states, None if masks is None else masks[t])
+
+
+def trace_emu(name, dt, tun, mode, dev=torch.device('cpu')):
+    """Caller has installed the emulator library and TEST_GEOMETRY (tests/conftest.py does; main() below does)."""
+    from tests.test_backbone import build_model
+    with tuning.override(**HOST_LOOP, **EMU_TUNINGS[tun]):
+        m = build_model(name, dev, DTYPES[dt])
+        xs = torch.from_numpy(casegen.make_inputs(name)).to(dev)
+        masks = torch.from_numpy(casegen.make_token_masks(name)).to(dev) if casegen.case_cfg(name)['enable_masking'] else None
+        return record(lambda: run_mode(m, xs, masks, mode))
+
+
+def trace_hip(key, mode, dev=torch.device('cuda', 0)):
+    """Caller is on the production route (tuning.production())."""
+    size, dataset, dt, T, B, extra = HIP_MODELS[key]
+    with tuning.override(**HOST_LOOP, **extra):
+        torch.manual_seed(0)
+        m = RNNDetector(backbone_config(size, dataset), compute_dtype=DTYPES[dt]).to(dev)
+        hw = (360, 640) if dataset == 'gen4' else (240, 304)
+        g = torch.Generator(device=dev).manual_seed(3)
+        xs = torch.randint(0, 11, (1 if mode == 'stream' else T, B, 20, *hw), generator=g, dtype=torch.uint8, device=dev)
+        out = record(lambda: run_mode(m, xs, None, mode))
+        torch.cuda.synchronize()
+        return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--backend', required=True, choices=['emu', 'hip'])
+    ap.add_argument('--out', default=GOLDEN)
+    a = ap.parse_args()
+    gold = json.load(open(GOLDEN)) if os.path.exists(GOLDEN) else {}
+    gold = {k: v for k, v in gold.items() if not k.startswith(a.backend + '/')}
+    if a.backend == 'emu':
+        from tests.backends import emu_library
+        _lib._install_test_library(emu_library())
+        tuning.use(**tuning.TEST_GEOMETRY)
+        for key, n, d, t, mode in emu_cases():
+            gold[key] = summary(trace_emu(n, d, t, mode)[0])
+            print(key, gold[key]['count'], gold[key]['sha256'][:12], flush=True)
+    else:
+        tuning.production()
+        for key, k, mode in hip_cases():
+            gold[key] = summary(trace_hip(k, mode)[0])
+            print(key, gold[key]['count'], gold[key]['sha256'][:12], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(dict(sorted(gold.items())), f, indent=1)
+        f.write('\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -171,26 +171,27 @@ def _scan3_run(dev, C, M, T, zero_state, rb):
     dc_last = None if zero_state else rnd((M, C), dev, torch.float32, 7)
     with tn.override(lstm_scan3_rb256=rb, lstm_scan3_rb128=rb):
         assert ops.lstm_scan3_supported(dt, C)
-        rows = ops.lstm_scan3_rows(C, M)
-        assert rows >= M and rows % (32 * rb) == 0
-        wp, wtp = ops.lstm_scan3_pack(w)
-        Hall = torch.empty(T + 1, M, C, dtype=dt, device=dev)
-        Hall[0].copy_(h0)
-        c_last = torch.empty(M, C, dtype=torch.float32, device=dev)
-        Csave = torch.empty(T, rows, C, dtype=dt, device=dev)
-        gsave = torch.empty(T, rows, 4 * C, dtype=dt, device=dev)
-        ops.lstm_scan3_fwd(x, Hall, c0, c_last, Csave, wp, b, gsave)
-        # no-grad flavour: same numbers, nothing saved
-        Hall2 = torch.empty_like(Hall)
-        Hall2[0].copy_(h0)
-        c_last2 = torch.empty_like(c_last)
-        ops.lstm_scan3_fwd(x, Hall2, c0, c_last2, None, wp, b, None)
-        assert torch.equal(Hall2.cpu(), Hall.cpu()) and torch.equal(c_last2.cpu(), c_last.cpu())
-        dx = torch.empty(T, M, C, dtype=dt, device=dev)
-        dz = torch.empty(T, M, 4 * C, dtype=dt, device=dev)
-        dh0 = torch.empty(M, C, dtype=dt, device=dev)
-        dc0 = torch.empty(M, C, dtype=torch.float32, device=dev)
-        ops.lstm_scan3_bwd(gsave, Csave, c0, dH, dc_last, wtp, dx, dz, dh0, dc0)
+        assert ops.lstm_scan3_rb(C) == rb                       # the tuned tile factor; from here on it is carried by hand
+    rows = ops.lstm_scan3_rows(C, M, rb)
+    assert rows >= M and rows % (32 * rb) == 0
+    wp, wtp = ops.lstm_scan3_pack(w)
+    Hall = torch.empty(T + 1, M, C, dtype=dt, device=dev)
+    Hall[0].copy_(h0)
+    c_last = torch.empty(M, C, dtype=torch.float32, device=dev)
+    Csave = torch.empty(T, rows, C, dtype=dt, device=dev)
+    gsave = torch.empty(T, rows, 4 * C, dtype=dt, device=dev)
+    ops.lstm_scan3_fwd(x, Hall, c0, c_last, Csave, wp, b, gsave, rb)
+    # no-grad flavour: same numbers, nothing saved
+    Hall2 = torch.empty_like(Hall)
+    Hall2[0].copy_(h0)
+    c_last2 = torch.empty_like(c_last)
+    ops.lstm_scan3_fwd(x, Hall2, c0, c_last2, None, wp, b, None, rb)
+    assert torch.equal(Hall2.cpu(), Hall.cpu()) and torch.equal(c_last2.cpu(), c_last.cpu())
+    dx = torch.empty(T, M, C, dtype=dt, device=dev)
+    dz = torch.empty(T, M, 4 * C, dtype=dt, device=dev)
+    dh0 = torch.empty(M, C, dtype=dt, device=dev)
+    dc0 = torch.empty(M, C, dtype=torch.float32, device=dev)
+    ops.lstm_scan3_bwd(gsave, Csave, c0, dH, dc_last, wtp, dx, dz, dh0, dc0, rb)
     return dict(x=x, h0=h0, c0=c0, w=w, b=b, dH=dH, dc_last=dc_last, Hall=Hall, c_last=c_last, dx=dx, dz=dz, dh0=dh0, dc0=dc0)
 
 
