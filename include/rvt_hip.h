@@ -22,6 +22,7 @@
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
  *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
+ *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *   Operator level — every other entry below: one launch each, what the stage driver sequences and what the Python mirror
  *       (rvt_amd/stage.py, the training backward) calls directly.  Stable and tested one by one (tests/test_kernels.py), but a host
@@ -605,6 +606,42 @@ int rvt_stacked_histogram(const long long* x, const long long* y, const long lon
 int rvt_augment_planes(const void* in, void* out, const int* table, int F, int B, int C, int H, int W, void* stream);
 int rvt_augment_labels(const float* rows, const int* count, const float* table, int F, int B, int G, float* rows_out, int* count_out,
                        float* yolox_out, void* stream);
+
+/* Prophesee / COCO mAP evaluation of detections on the device (rvt_amd/csrc/cocoeval.hpp; host mirror rvt_amd/evaluation.py).
+ * Replaces utils/evaluation/prophesee/ (filter_boxes, evaluate_list, coco_eval.py) and the COCOeval core it calls (evaluateImg,
+ * accumulate; bbox mode, iscrowd false, maxDets 100): no per-frame copy to the host, no Python loop.  Neither call synchronises
+ * with the host; both replay in a hipGraph.
+ *
+ * The match entry: one launch for F frames, one wave per (frame, category).
+ *   det [F][max_det][7] fp32 and count [F] int32 exactly as the post-processing entry returns them (x1 y1 x2 y2 obj class_conf
+ *   class_pred; det_xywh != 0: columns 0..3 are x y w h).  A frame uses its first min(count, max_det) rows; count > max_det adds
+ *   one to the truncated-frames counter.  labels [F][G][7] fp32 (t x y w h class_id class_confidence) and label_count [F] int32
+ *   (<= 0: no labels) as the label augmentation entry lays them out; t_us [F] int64, the frame's timestamp in microseconds.
+ *   Filter (fp32, no fused multiply-add), for labels and detections alike: a box stays iff t_us > 500000 and
+ *   w*w + h*h >= min_diag*min_diag and w >= min_side and h >= min_side; a detection's w, h are x2 - x1, y2 - y1, its score is
+ *   class_conf.  A frame is an image iff one of its labels stays; other frames write no record and count nothing.
+ *   Per category: the detections that stay, by descending score (the earlier row first on an exact tie), the first 100; IoU in
+ *   double on the widened fp32 x y w h; for each of the 10 thresholds iou_thrs (device, double) and 4 area ranges (all, < 32^2,
+ *   32^2..96^2, > 96^2 of the fp32 product w*h) the greedy matching of COCOeval.evaluateImg.
+ *   rec_key / rec_matched / rec_ignored int64 [F][rec_stride], rec_stride >= min(max_det, 100 * num_classes): the frame's
+ *   records category by category in score order.  key = category << 32 | ~(order-preserving bits of the score), so ascending keys
+ *   are (category, descending score); bit 4*t + a of matched / ignored is dtMatches != 0 / dtIgnore at threshold t, range a.
+ *   Unused slots get key 0x7fffffffffffffff.
+ *   counters int32 [96], ADDED to (zero them to start an evaluation): [4k + a] ground truth of category k not ignored in range a,
+ *   [64 + k] records of category k, [80] images, [81] images with a detection that stays, [82] truncated frames.
+ *   Supported: 1 <= max_det <= 1024, 1 <= G <= 128, 1 <= num_classes <= 16; anything else returns non-zero with the last error
+ *   set before any launch.
+ *
+ * The accumulate entry: perm int64 [n_slots] = the record slots ordered by (key, slot) (a stable sort of rec_key),
+ *   rec_thrs double [101] on the device -> precision double [10][101][num_classes][4], COCOeval.accumulate's table at maxDets 100:
+ *   -1 where the cell has no non-ignored ground truth.  ws: the ws_bytes query's size (0 = unsupported), contents need not survive. */
+int rvt_coco_match(const float* det, const int* count, const float* labels, const int* label_count, const long long* t_us, int F,
+                   int max_det, int G, int num_classes, int det_xywh, float min_diag, float min_side, const double* iou_thrs,
+                   long long* rec_key, long long* rec_matched, long long* rec_ignored, int rec_stride, int* counters, void* stream);
+size_t rvt_coco_accumulate_ws_bytes(long long n_slots, int num_classes);
+int rvt_coco_accumulate(const long long* perm, const long long* rec_matched, const long long* rec_ignored, long long n_slots,
+                        int num_classes, const int* counters, const double* rec_thrs, double* precision, void* ws, size_t ws_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }

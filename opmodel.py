@@ -200,6 +200,12 @@ def model(name: str, a) -> Optional[Tuple[float, float]]:
     if name == 'rvt_augment_labels':                             # rows + count in, rows + count (+ yolox) out
         F, B, G = a[3:6]
         return 0.0, 2.0 * F * (G * 7 * 4 + 4) + (F * G * 5 * 4 if P(8) else 0) + 48.0 * B
+    if name == 'rvt_coco_match':                                 # det + count, label rows + count, timestamps in; the frame's record slots out
+        F, max_det, G, nc, stride = a[5], a[6], a[7], a[8], a[16]
+        return 0.0, 1.0 * F * (max_det * 7 * 4 + 4 + G * 7 * 4 + 4 + 8) + 24.0 * F * stride + 80.0
+    if name == 'rvt_coco_accumulate':                            # permutation + the two mask planes read twice (count, emit); table out
+        n, nc = a[3], a[4]
+        return 0.0, 2.0 * 24 * n + 10 * 101 * nc * 4 * 8.0
     return None
 
 
