@@ -24,6 +24,7 @@
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
+ *       rvt_optim_step                                 value clip + AdamW + OneCycle schedule of every parameter, one call per step
  *   Operator level — every other entry below: one launch each, what the stage driver sequences and what the Python mirror
  *       (rvt_amd/stage.py, the training backward) calls directly.  Stable and tested one by one (tests/test_kernels.py), but a host
  *       that only runs the model needs none of them; the `*_supported` / `*_ws_*` queries say which fused forms exist for a shape.
@@ -606,6 +607,30 @@ int rvt_stacked_histogram(const long long* x, const long long* y, const long lon
 int rvt_augment_planes(const void* in, void* out, const int* table, int F, int B, int C, int H, int W, void* stream);
 int rvt_augment_labels(const float* rows, const int* count, const float* table, int F, int B, int G, float* rows_out, int* count_out,
                        float* yolox_out, void* stream);
+
+/* The optimizer step on the device (rvt_amd/csrc/optim.hpp; host mirror rvt_amd/optim.py): gradient clipping by value, AdamW
+ * (decoupled weight decay, no amsgrad) and the OneCycle learning-rate schedule of every parameter of every parameter group in one
+ * call (reference modules/detection.py:360-392 and the trainer's gradient_clip_val by value).  Two tables in DEVICE memory, built
+ * once by the host, 8-byte aligned:
+ *   chunks [n_chunks] of 40 bytes, one per piece of at most 4096 consecutive elements of one parameter (fp32, contiguous):
+ *     float* p;  const float* g;  float* exp_avg;  float* exp_avg_sq;  int32 n (1..4096);  int32 group (0..n_groups-1)
+ *     pieces of one tensor start 4096 elements apart; a tensor of at most 4096 elements is one entry.  A chunk whose four
+ *     pointers are 16-byte aligned moves in 16-byte accesses, any other element by element.
+ *   groups [n_groups] of 80 bytes, ten doubles:
+ *     beta1, beta2, eps, weight_decay, clip (< 0 = no clipping), lr_init, lr_max, lr_final, warm_end, last
+ *     warm_end = float(pct_start * total_steps) - 1 and last = total_steps - 1 are schedule POSITIONS (warm_end may be fractional);
+ *     a constant learning rate is lr_init = lr_max = lr_final = lr, warm_end = last = 0.
+ *   step: int64 on the device, the optimizer steps done so far.  The call uses k = *step + 1 in every workgroup and leaves
+ *     *step = k behind (a trailing one-thread launch of the same call), so a captured graph replays with nothing written by the host.
+ * In double, per workgroup:  pos = k - 1;  lr = (lr_max - lr_init) * (pos / warm_end) + lr_init for pos <= warm_end,
+ *   (lr_final - lr_max) * ((pos - warm_end) / (last - warm_end)) + lr_max for pos <= last, lr_final beyond (torch's OneCycleLR,
+ *   three_phase=False, linear, raises there);  bc1 = 1 - beta1^k;  bc2 = 1 - beta2^k.
+ * In fp32, per element, one rounded operation each (the constants computed in double and rounded once):
+ *     g = clamp(g, -clip, clip)   (the stored gradient is NOT modified, unlike clip_grad_value_)
+ *     p = p * (1 - lr * weight_decay);  m = m + (1 - beta1) * (g - m);  v = beta2 * v + ((1 - beta2) * g) * g
+ *     p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))
+ * max_blocks: grid cap, 0 = the default (2048 workgroups; chunks beyond are walked grid-stride). */
+int rvt_optim_step(const void* chunks, int n_chunks, const void* groups, int n_groups, long long* step, int max_blocks, void* stream);
 
 /* Prophesee / COCO mAP evaluation of detections on the device (rvt_amd/csrc/cocoeval.hpp; host mirror rvt_amd/evaluation.py).
  * Replaces utils/evaluation/prophesee/ (filter_boxes, evaluate_list, coco_eval.py) and the COCOeval core it calls (evaluateImg,

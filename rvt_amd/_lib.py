@@ -87,6 +87,7 @@ _SIGS = {
     'rvt_augment_labels': [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     'rvt_coco_match': [_vp] * 5 + [_i] * 5 + [_f, _f] + [_vp] * 4 + [_i, _vp, _vp],
     'rvt_coco_accumulate': [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    'rvt_optim_step': [_vp, _i, _vp, _i, _vp, _i, _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ['rvt_last_error', 'rvt_is_emulator', 'rvt_wgrad_workspace_floats',
                                'rvt_mlp_fused_supported', 'rvt_lstm_scan_supported', 'rvt_mlp_bwd_fused_supported',
