@@ -482,31 +482,33 @@ int rvt_gather_frames(const void* src, const int* idx, void* dst, int n_sel, siz
 /* ---- YOLOX PAFPN building block (reference models/detection/yolox/models/network_blocks.py:29-53) ----
  * BaseConv = Conv2d(bias=False) -> BatchNorm2d(eps 1e-5, momentum 0.1) -> SiLU on channels-last maps x[rows = N*H*W][C].  The conv
  * is rvt_conv_fwd / rvt_conv_dgrad / rvt_conv_wgrad; these are the row-wise kernels around it (csrc/bnact.hpp).  act: 0 none, 1 SiLU.
- *   rvt_bn_stats:          sum[C] += column sums of x, sumsq[C] += column sums of x^2 (fp32; zero them first; under data parallelism
- *                          these two vectors are what SyncBatchNorm all-reduces, train.py:133)
- *   rvt_bn_finalize:       training: mean = sum / rows, var = sumsq / rows - mean^2 (biased), running statistics updated in place with
- *                          `momentum` (unbiased variance) when non-NULL; eval: mean / var = the running statistics.  Writes
+ *   rvt_bn_stats:          stats[2][C] in fp64 (zero it first): stats[0] += column sums of x, stats[1] += column sums of x^2.  fp64 because
+ *                          var = E[x^2] - mean^2 taken in fp32 cancels when |mean| >> std; under data parallelism these two vectors
+ *                          are what SyncBatchNorm all-reduces, train.py:133
+ *   rvt_bn_finalize:       training: mean = stats[0] / rows, var = stats[1] / rows - mean^2 (biased, in fp64), running statistics
+ *                          updated in place with `momentum` (unbiased variance) when non-NULL; eval (stats may be NULL): mean / var =
+ *                          the running statistics.  Writes
  *                          scale = gamma * rstd, shift = beta - mean * scale and (nullable) mean_out / rstd_out for the backward.
  *   rvt_bn_act_fwd:        y = act(x * scale + shift)            (y may alias x)
- *   rvt_bn_act_bwd_stats:  dz = dy * act'(x * scale + shift);  dsum[C] += sum dz (= dbeta), dxsum[C] += sum dz * xhat (= dgamma)
+ *   rvt_bn_act_bwd_stats:  dz = dy * act'(x * scale + shift);  dsum[C] += sum dz (= dbeta), dxsum[C] += sum dz * xhat (= dgamma), fp64 like
+ *                          every column sum here (thousands of workgroups' partial sums meet in one word per channel)
  *   rvt_bn_act_bwd_apply:  dx = scale * (dz - dsum / rows - xhat * dxsum / rows)      (training-mode BatchNorm backward) */
 /* Inference: Conv2d(bias=False) + BatchNorm2d (running statistics) + activation in ONE launch — scale / shift from rvt_bn_finalize
  * (training = 0) applied to the fp32 accumulator in the GEMM epilogue; act 0 = none, 1 = SiLU.  in / w / out as rvt_conv_fwd. */
 int rvt_conv_bn_act_fwd(const void* in, const void* w, const float* scale, const float* shift, void* out, int dtype, int F, int H, int W,
                         int Cin, int Cout, int k, int stride, int pad, int act, void* stream);
-int rvt_bn_stats(const void* x, float* sum, float* sumsq, int dtype, int rows, int C, void* stream);
-int rvt_bn_finalize(const float* sum, const float* sumsq, int rows, const float* gamma, const float* beta, float eps, float momentum,
-                    float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* scale, float* shift, int C,
-                    int training, void* stream);
+int rvt_bn_stats(const void* x, double* stats, int dtype, int rows, int C, void* stream);
+int rvt_bn_finalize(const double* stats, int rows, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                    float* running_var, float* mean_out, float* rstd_out, float* scale, float* shift, int C, int training, void* stream);
 int rvt_bn_act_fwd(const void* x, const float* scale, const float* shift, void* y, int dtype, int rows, int C, int act, void* stream);
 /* rvt_bn_finalize (training) + rvt_bn_act_fwd in ONE launch: count = rows the sums cover (the global count under synchronised BatchNorm) */
-int rvt_bn_train_act_fwd(const void* x, const float* sum, const float* sumsq, int count, const float* gamma, const float* beta, float eps,
-                         float momentum, float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* scale_out,
-                         float* shift_out, void* y, int dtype, int rows, int C, int act, void* stream);
+int rvt_bn_train_act_fwd(const void* x, const double* stats, int count, const float* gamma, const float* beta, float eps, float momentum,
+                         float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* scale_out, float* shift_out,
+                         void* y, int dtype, int rows, int C, int act, void* stream);
 int rvt_bn_act_bwd_stats(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* rstd,
-                         float* dsum, float* dxsum, int dtype, int rows, int C, int act, void* stream);
+                         double* dsum, double* dxsum, int dtype, int rows, int C, int act, void* stream);
 int rvt_bn_act_bwd_apply(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* rstd,
-                         const float* dsum, const float* dxsum, void* dx, int dtype, int rows, int C, int act, void* stream);
+                         const double* dsum, const double* dxsum, void* dx, int dtype, int rows, int C, int act, void* stream);
 
 /* YOLOX head tail on [B][A][5 + num_classes] fp32 prediction tensors (rvt_amd/csrc/simota.hpp; host mirror rvt_amd/head.py).
  * Replaces models/detection/yolox/models/yolo_head.py:236-290 (decode) and :291-606 (get_losses / get_assignments /

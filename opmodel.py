@@ -170,7 +170,7 @@ def model(name: str, a) -> Optional[Tuple[float, float]]:
         return 0.0, 1.0 * M * C * e
     # ---- detection tail (rows f2 / f3): BatchNorm + SiLU row kernels around the PAFPN / head convolutions, decode, SimOTA + losses
     if name == 'rvt_bn_stats':                                   # one read of the conv output
-        e, rows, C = _elt(a[3]), a[4], a[5]
+        e, rows, C = _elt(a[2]), a[3], a[4]
         return 0.0, 1.0 * rows * C * e
     if name == 'rvt_bn_act_fwd':                                 # read + write
         e, rows, C = _elt(a[4]), a[5], a[6]
@@ -182,7 +182,7 @@ def model(name: str, a) -> Optional[Tuple[float, float]]:
         e, rows, C = _elt(a[9]), a[10], a[11]
         return 0.0, 3.0 * rows * C * e
     if name == 'rvt_bn_finalize':
-        return 0.0, 40.0 * a[13]
+        return 0.0, 48.0 * a[12]                                 # two fp64 sums in; running statistics, four fp32 vectors out
     if name in ('rvt_yolox_decode', 'rvt_yolox_decode_bwd'):     # the level's two prediction maps <-> [B][A][5+nc] fp32 rows
         o = 2 if name == 'rvt_yolox_decode' else 5
         ld_ro, ld_cls, e, B, H, W, _st, nc = a[o], a[o + 1], _elt(a[o + 2]), *a[o + 3:o + 8]

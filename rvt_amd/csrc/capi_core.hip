@@ -233,20 +233,21 @@ int rvt_gather_frames(const void* src, const int* idx, void* dst, int n_sel, siz
 }
 
 // ---------------------------------------------------------------- BatchNorm2d + SiLU of the PAFPN's BaseConv units (bnact.hpp)
-int rvt_bn_stats(const void* x, float* sum, float* sumsq, int dtype, int rows, int C, void* stream) {
+int rvt_bn_stats(const void* x, double* stats, int dtype, int rows, int C, void* stream) {
     RVT_CHECK(C % 8 == 0 && C >= 8 && C <= 1024 && rows >= 1, "bn_stats: C=%d must be a multiple of 8 in [8, 1024]", C);
+    RVT_CHECK(x && stats, "bn_stats: null argument");
     const int Gp = pow2_ge(C / 8), nrl = 256 / Gp;
     const int grid = imin(1024, imax(1, (rows + nrl * 8 - 1) / (nrl * 8)));
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, sum, sumsq, rows, C, Gp));
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, stats, rows, C, Gp));
     return check_launch("bn_stats");
 }
-int rvt_bn_finalize(const float* sum, const float* sumsq, int rows, const float* gamma, const float* beta, float eps, float momentum,
+int rvt_bn_finalize(const double* stats, int rows, const float* gamma, const float* beta, float eps, float momentum,
                     float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* scale, float* shift, int C,
                     int training, void* stream) {
     RVT_CHECK(C >= 1 && gamma && beta && scale && shift, "bn_finalize: bad arguments");
-    RVT_CHECK(training ? (sum && sumsq && rows >= 1) : (running_mean && running_var), "bn_finalize: training needs sums, eval needs running statistics");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sum, sumsq, (float)rows, gamma, beta, eps, momentum,
-                       running_mean, running_var, mean_out, rstd_out, scale, shift, C, training);
+    RVT_CHECK(training ? (stats && rows >= 1) : (running_mean && running_var), "bn_finalize: training needs sums, eval needs running statistics");
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, (double)rows, gamma, beta, eps,
+                       momentum, running_mean, running_var, mean_out, rstd_out, scale, shift, C, training);
     return check_launch("bn_finalize");
 }
 // grid of the row-streaming element-wise kernels: 256 / Gp rows per workgroup pass, ~8 passes per workgroup, at most 4096 workgroups
@@ -258,20 +259,21 @@ int rvt_bn_act_fwd(const void* x, const float* scale, const float* shift, void* 
                                              shift, (T*)y, rows, C, Gp, act));
     return check_launch("bn_act_fwd");
 }
-int rvt_bn_train_act_fwd(const void* x, const float* sum, const float* sumsq, int count, const float* gamma, const float* beta, float eps,
-                         float momentum, float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* scale_out,
-                         float* shift_out, void* y, int dtype, int rows, int C, int act, void* stream) {
+int rvt_bn_train_act_fwd(const void* x, const double* stats, int count, const float* gamma, const float* beta, float eps, float momentum,
+                         float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* scale_out, float* shift_out,
+                         void* y, int dtype, int rows, int C, int act, void* stream) {
     RVT_CHECK(C % 8 == 0 && C >= 8 && C <= 2048 && rows >= 1 && count >= 1 && (act == 0 || act == 1), "bn_train_act_fwd: bad shape / activation");
-    RVT_CHECK(x && sum && sumsq && gamma && beta && mean_out && rstd_out && scale_out && shift_out && y, "bn_train_act_fwd: null argument");
+    RVT_CHECK(x && stats && gamma && beta && mean_out && rstd_out && scale_out && shift_out && y, "bn_train_act_fwd: null argument");
     const int Gp = pow2_ge(C / 8);
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_train_act_fwd_kernel<T>), dim3(bn_row_grid(rows, Gp)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
-                                             sum, sumsq, (float)count, gamma, beta, eps, momentum, running_mean, running_var, mean_out, rstd_out,
-                                             scale_out, shift_out, (T*)y, rows, C, Gp, act));
+                                             stats, (double)count, gamma, beta, eps, momentum, running_mean, running_var, mean_out,
+                                             rstd_out, scale_out, shift_out, (T*)y, rows, C, Gp, act));
     return check_launch("bn_train_act_fwd");
 }
 int rvt_bn_act_bwd_stats(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* rstd,
-                         float* dsum, float* dxsum, int dtype, int rows, int C, int act, void* stream) {
+                         double* dsum, double* dxsum, int dtype, int rows, int C, int act, void* stream) {
     RVT_CHECK(C % 8 == 0 && C >= 8 && C <= 1024 && rows >= 1, "bn_act_bwd_stats: C=%d must be a multiple of 8 in [8, 1024]", C);
+    RVT_CHECK(act == 0 || act == 1, "bn_act_bwd_stats: activation %d (0 none, 1 SiLU)", act);
     const int Gp = pow2_ge(C / 8), nrl = 256 / Gp;
     const int grid = imin(1024, imax(1, (rows + nrl * 8 - 1) / (nrl * 8)));
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_bwd_stats_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)x,
@@ -279,11 +281,11 @@ int rvt_bn_act_bwd_stats(const void* dy, const void* x, const float* scale, cons
     return check_launch("bn_act_bwd_stats");
 }
 int rvt_bn_act_bwd_apply(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* rstd,
-                         const float* dsum, const float* dxsum, void* dx, int dtype, int rows, int C, int act, void* stream) {
-    RVT_CHECK(C % 8 == 0 && C >= 8 && C <= 2048 && rows >= 1, "bn_act_bwd_apply: bad shape");
+                         const double* dsum, const double* dxsum, void* dx, int dtype, int rows, int C, int act, void* stream) {
+    RVT_CHECK(C % 8 == 0 && C >= 8 && C <= 2048 && rows >= 1 && (act == 0 || act == 1), "bn_act_bwd_apply: bad shape / activation");
     const int Gp = pow2_ge(C / 8);
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T>), dim3(bn_row_grid(rows, Gp)), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
-                                             (const T*)x, scale, shift, mean, rstd, dsum, dxsum, (T*)dx, rows, C, Gp, 1.0f / (float)rows, act));
+                                             (const T*)x, scale, shift, mean, rstd, dsum, dxsum, (T*)dx, rows, C, Gp, 1.0 / (double)rows, act));
     return check_launch("bn_act_bwd_apply");
 }
 

@@ -52,18 +52,21 @@ class _BaseConvFn(torch.autograd.Function):
         rows = y0.numel() // Cout
         f32 = torch.float32
         st = L.stream_of(y0)
-        stats = pk.stats if pk is not None and training else torch.zeros(2, Cout, dtype=f32, device=dev)   # (the pack zeroes its arena once per forward)
+        # [sum x | sum x^2] in fp64  (the pack zeroes its arena once per forward)
+        stats = pk.stats if pk is not None and training else torch.zeros(2, Cout, dtype=torch.float64, device=dev)
         ctx.pk = pk
         count = rows
         if training:
-            L.call('rvt_bn_stats', L.ptr(y0), L.ptr(stats[0]), L.ptr(stats[1]), L.dtype_code(dt), rows, Cout, st)
+            L.call('rvt_bn_stats', L.ptr(y0), L.ptr(stats), L.dtype_code(dt), rows, Cout, st)
             if sync:
                 # ONE exchange of [sum x | sum x^2 | rows] (the 2 C + 1 values torch's SyncBatchNorm gathers); the global row count comes
                 # back to the host because the finalize kernel takes it by value (ranks may hold different numbers of labelled frames)
-                packed = torch.cat([stats.reshape(-1), torch.tensor([float(rows)], device=dev)])
+                packed = torch.cat([stats.reshape(-1), torch.tensor([float(rows)], dtype=torch.float64, device=dev)])
                 _bn_reduce(packed)
                 stats.copy_(packed[:2 * Cout].view(2, Cout))
                 count = int(packed[2 * Cout].item())
+            if count == 1:                                                                # (what nn.BatchNorm2d's training forward raises)
+                raise ValueError(f'Expected more than 1 value per channel when training, got input size {[N, Cout, *y0.shape[1:3]]}')
         fin = torch.empty(4, Cout, dtype=f32, device=dev)                                 # mean, rstd, scale, shift
         bn = mod.bn
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
@@ -75,13 +78,13 @@ class _BaseConvFn(torch.autograd.Function):
         mom = 0.0 if bn.momentum is None else float(bn.momentum)
         rm, rv = L.ptr(bn.running_mean), L.ptr(bn.running_var)
         if training:                                                                      # finalize + activation in one launch
-            L.call('rvt_bn_train_act_fwd', L.ptr(y0), L.ptr(stats[0]), L.ptr(stats[1]), count, L.ptr(g32), L.ptr(b32), float(bn.eps), mom,
+            L.call('rvt_bn_train_act_fwd', L.ptr(y0), L.ptr(stats), count, L.ptr(g32), L.ptr(b32), float(bn.eps), mom,
                    rm, rv, L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(y), L.dtype_code(dt), rows, Cout,
                    BN_ACT_SILU, st)
             if bn.track_running_stats and pk is None:                                     # (with a ConvPack: one batched increment per forward)
                 bn.num_batches_tracked += 1
         else:
-            L.call('rvt_bn_finalize', L.ptr(stats[0]), L.ptr(stats[1]), count, L.ptr(g32), L.ptr(b32), float(bn.eps), mom, rm, rv,
+            L.call('rvt_bn_finalize', L.ptr(stats), count, L.ptr(g32), L.ptr(b32), float(bn.eps), mom, rm, rv,
                    L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), Cout, 0, st)
             L.call('rvt_bn_act_fwd', L.ptr(y0), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(y), L.dtype_code(dt), rows, Cout, BN_ACT_SILU, st)
         ctx.save_for_backward(x, w, y0, fin)
@@ -99,7 +102,7 @@ class _BaseConvFn(torch.autograd.Function):
         rows = y0.numel() // Cout
         dy = dy.contiguous()
         st = L.stream_of(dy)
-        ds = torch.zeros(2, Cout, dtype=torch.float32, device=dev)                        # sum dz (= dbeta), sum dz * xhat (= dgamma)
+        ds = torch.zeros(2, Cout, dtype=torch.float64, device=dev)                        # sum dz (= dbeta), sum dz * xhat (= dgamma)
         L.call('rvt_bn_act_bwd_stats', L.ptr(dy), L.ptr(y0), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(ds[0]),
                L.ptr(ds[1]), L.dtype_code(dt), rows, Cout, BN_ACT_SILU, st)
         ds_local = ds
@@ -198,7 +201,7 @@ class ConvPack:
                 for c in self.convs:
                     bn, Cout = c.bn, c.out_channels
                     fin = torch.empty(4, Cout, dtype=torch.float32, device=bn.weight.device)
-                    L.call('rvt_bn_finalize', None, None, 1, L.ptr(bn.weight.detach().float().contiguous()),
+                    L.call('rvt_bn_finalize', None, 1, L.ptr(bn.weight.detach().float().contiguous()),
                            L.ptr(bn.bias.detach().float().contiguous()), float(bn.eps), 0.0, L.ptr(bn.running_mean), L.ptr(bn.running_var),
                            L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), Cout, 0, L.stream_of(fin))
                     c._pk.fin = fin
@@ -214,10 +217,10 @@ class ConvPack:
                 arT.n = ar32.n = 0
             tab = weights._Table(weights.PACK_DT, 1024)
             for c in self.convs:                         # statistics first: one contiguous region to zero per forward
-                st = ar32.take(2, c.out_channels)
+                st = ar32.take(2, 2 * c.out_channels)         # two fp64 vectors
                 if second:
                     c._pk = _Packed()
-                    c._pk.stats, c._pk.dtype, c._pk.cin, c._pk.fin, c._pk.dwp_clean = st, dtype, c.in_channels, None, False
+                    c._pk.stats, c._pk.dtype, c._pk.cin, c._pk.fin, c._pk.dwp_clean = st.view(torch.float64), dtype, c.in_channels, None, False
             ar32_stats = ar32.n
             for c in self.convs:
                 Cout, Cin, k, s, pad = c.out_channels, c.in_channels, c.ksize, c.stride, c.pad

@@ -179,6 +179,92 @@ def test_fpn_syncbn_world2_gloo(tmp_path):
     assert r.returncode == 0 and r.stdout.count('OK') == 2, r.stdout[-2000:] + r.stderr[-3000:]
 
 
+SYNCBN_UNEQUAL_WORKER = r'''
+# One BaseConv (k = 3, Cin 16, Cout 24) under synchronised BatchNorm with UNEQUAL shares: rank 0 holds one sample of a batch of three,
+# rank 1 the other two, so the global count is not rows * world and the backward rescales the reduced sums by rows / count.
+# Reference: fp64 conv2d + batch_norm + silu of the full batch, computed here.
+import os, sys, torch, torch.distributed as dist, torch.nn.functional as F
+root = sys.argv[1]
+sys.path.insert(0, root)
+from rvt_amd import _lib, tuning, fpn
+from tests.backends import emu_library
+from tests.test_fpn import _rel
+tuning.use(**tuning.TEST_GEOMETRY)
+_lib._install_test_library(emu_library())
+rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
+dist.init_process_group('gloo')
+torch.set_num_threads(2)
+g = torch.Generator().manual_seed(11)
+N, H, W, Cin, Cout = 3, 6, 7, 16, 24
+x = torch.randn(N, H, W, Cin, generator=g) + 0.5
+cot = torch.randn(N, H, W, Cout, generator=g)
+m = fpn.BaseConv(Cin, Cout, 3, 1)
+with torch.no_grad():
+    m.conv.weight.copy_(0.2 * torch.randn(Cout, Cin, 3, 3, generator=g))
+    m.bn.weight.copy_(0.5 + torch.rand(Cout, generator=g))
+    m.bn.bias.copy_(0.1 * torch.randn(Cout, generator=g))
+    m.bn.running_mean.copy_(0.3 * torch.randn(Cout, generator=g))
+    m.bn.running_var.copy_(0.5 + torch.rand(Cout, generator=g))
+p64 = {k: v.detach().double().clone().requires_grad_(v.requires_grad) for k, v in m.state_dict(keep_vars=True).items()}
+x64 = x.double().permute(0, 3, 1, 2).requires_grad_(True)
+y64 = F.silu(F.batch_norm(F.conv2d(x64, p64['conv.weight'], None, 1, 1), p64['bn.running_mean'], p64['bn.running_var'],
+                          p64['bn.weight'], p64['bn.bias'], True, 0.1, 1e-5))
+y64.backward(cot.double().permute(0, 3, 1, 2))
+lo, hi = (0, 1) if rank == 0 else (1, 3)
+m.train()
+xl = x[lo:hi].clone().requires_grad_(True)
+y = m(xl)
+(y * cot[lo:hi]).sum().backward()
+errs = dict(out=_rel(y.detach().numpy(), y64.detach().permute(0, 2, 3, 1)[lo:hi].numpy()),
+            dx=_rel(xl.grad.numpy(), x64.grad.permute(0, 2, 3, 1)[lo:hi].numpy()))
+for k, p in m.named_parameters():
+    gsum = p.grad.clone()
+    dist.all_reduce(gsum)
+    errs[k] = _rel(gsum.numpy(), p64[k].grad.numpy())
+for k in ('running_mean', 'running_var'):
+    errs[k] = _rel(getattr(m.bn, k).numpy(), p64['bn.' + k].detach().numpy())
+assert int(m.bn.num_batches_tracked) == 1
+print('errs', rank, ' '.join(f'{k}={v:.2e}' for k, v in errs.items()))
+assert all(v <= 1e-3 for v in errs.values()), errs
+dist.destroy_process_group()
+print('OK', rank)
+'''
+
+
+def test_baseconv_syncbn_unequal_shares_world2_gloo(tmp_path):
+    """count != rows * world: every rank must divide the all-reduced backward sums by the GLOBAL count (the rescale ds * rows / count
+    in _BaseConvFn.backward) and normalise with the global statistics.  Local outputs and input gradients against the slices of the
+    fp64 full-batch reference, rank-summed parameter gradients and the running statistics against the reference's, all at this
+    file's fp32 bar of 1e-3.  Measured on the emulator: worst 4.3e-7 (out 4.2e-7, dx 4.3e-7, parameter gradients <= 2.8e-7, running
+    statistics <= 5.6e-8)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / 'w.py'
+    script.write_text(SYNCBN_UNEQUAL_WORKER)
+    r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
+                        '--master-port', '29751', str(script), root], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.count('OK') == 2, r.stdout[-2000:] + r.stderr[-3000:]
+    print(r.stdout)
+
+
+def test_baseconv_training_needs_more_than_one_value_per_channel(backend):
+    """nn.BatchNorm2d refuses a training forward with one value per channel (the variance of one number); so does BaseConv, instead
+    of normalising with variance 0.  Eval mode takes the same input."""
+    dev = backend
+    m = F_.BaseConv(8, 16, 1, 1).to(dev)
+    x = torch.randn(1, 1, 1, 8, device=dev)
+    with pytest.raises(ValueError, match='more than 1 value per channel'):
+        torch.nn.BatchNorm2d(16).train()(torch.randn(1, 16, 1, 1))
+    m.train()
+    with pytest.raises(ValueError, match='more than 1 value per channel'):
+        m(x)
+    assert int(m.bn.num_batches_tracked) == 0 and bool((m.bn.running_mean == 0).all())
+    assert tuple(m.train()(torch.randn(2, 1, 1, 8, device=dev)).shape) == (2, 1, 1, 16)
+    assert tuple(m.eval()(x).shape) == (1, 1, 1, 16)
+
+
 @pytest.mark.parametrize('dtype,tol', [(torch.float32, 1e-5), (torch.bfloat16, 3e-2)])
 def test_fpn_eval_fused_conv_bn_silu_matches_unfused(backend, dtype, tol):
     """Inference takes ONE launch per BaseConv (BatchNorm affine + SiLU in the convolution's epilogue, rvt_conv_bn_act_fwd); an input that

@@ -529,7 +529,11 @@ CONV_CASES = [  # F, H, W, Cin, Cout, k, s, p
     (1, 6, 10, 72, 136, 3, 2, 1),
     (2, 8, 32, 16, 32, 3, 2, 1),      # output width 16: the weight gradient's unit-linear im2col path, Cout <= 64 (transposed product)
     (1, 16, 64, 20, 72, 7, 4, 3),     # ... same with the stem geometry and Cout > 64 (direct product)
+    (2, 5, 7, 24, 48, 1, 1, 0),       # the PAFPN's own geometry at widths that are no power of two: lateral / CSP 1 x 1,
+    (1, 6, 10, 48, 24, 3, 1, 1),      # ... 3 x 3 stride 1,
+    (2, 9, 11, 96, 96, 3, 2, 1),      # ... bottom-up 3 x 3 stride 2 on odd extents
 ]
+PAFPN_CONV_CASES = CONV_CASES[-3:]
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -554,6 +558,28 @@ def test_conv(backend, dt, case):
         add = rnd((Fr, H, W, Cin), backend, dt, 4)
         din = ops.conv_dgrad(dy, weights.pack_conv_dgrad(w.float(), s, p, dt), add, H, W, Cin, k, s, p)
         close(din, xr.grad.permute(0, 2, 3, 1) + f64(add), dt, 'conv_dgrad')
+
+
+@pytest.mark.parametrize('act', [1, 0])
+@pytest.mark.parametrize('dt', DTYPES)
+@pytest.mark.parametrize('case', PAFPN_CONV_CASES)
+def test_conv_bn_act_fwd(backend, dt, case, act):
+    """The inference epilogue (conv + BatchNorm affine from the running statistics + SiLU in one launch) against fp64 conv2d, then
+    the affine, then silu; scale / shift come from rvt_bn_finalize(training = 0) as in rvt_amd/fpn.py."""
+    from rvt_amd import _lib as L
+    Fr, H, W, Cin, Cout, k, s, p = case
+    x = rnd((Fr, H, W, Cin), backend, dt, 1)
+    w = rnd((Cout, Cin, k, k), backend, torch.float32, 2, 0.2).to(dt)
+    g = torch.Generator().manual_seed(5)
+    gamma, beta = (0.5 + torch.rand(Cout, generator=g)).to(backend), (0.1 * torch.randn(Cout, generator=g)).to(backend)
+    rm, rv = (0.5 * torch.randn(Cout, generator=g)).to(backend), (0.5 + 2.0 * torch.rand(Cout, generator=g)).to(backend)
+    fin = torch.empty(4, Cout, device=backend)
+    L.call('rvt_bn_finalize', None, 1, L.ptr(gamma), L.ptr(beta), 1e-5, 0.0, L.ptr(rm), L.ptr(rv), L.ptr(fin[0]), L.ptr(fin[1]),
+           L.ptr(fin[2]), L.ptr(fin[3]), Cout, 0, L.stream_of(fin))
+    y = ops.conv_bn_act_fwd(x, weights.pack_conv_fwd(w.float(), Cin, dt), fin[2], fin[3], k, s, p, act)
+    scale = f64(gamma) / torch.sqrt(f64(rv) + 1e-5)
+    z = F.conv2d(f64(x).permute(0, 3, 1, 2), f64(w), None, s, p).permute(0, 2, 3, 1) * scale + (f64(beta) - f64(rm) * scale)
+    close(y, F.silu(z) if act else z, dt, f'conv_bn_act_fwd act={act}')
 
 
 STEM_CASES = [  # F, Cin, h, w, H, W  (uint8 planes h x w, zero padded to the model resolution H x W)
