@@ -19,6 +19,7 @@
  *       rvt_last_error, rvt_tuning_defaults / rvt_get_tuning / rvt_set_tuning          one record of launch geometry + routing
  *       rvt_stage_seq_fwd (+ _ws_bytes)                one call per backbone stage and sequence (no-grad forward)
  *       rvt_stacked_histogram                          event stream -> input tensor (row f4)
+ *       rvt_event_sequence (+ _ws_bytes)               B raw event streams -> a whole (T, B, 2*bins, H', W') window sequence, slicing + half-scale
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
  *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
@@ -577,6 +578,38 @@ int rvt_layerscale_grad_table(const void* descs, int n_desc, int total_blocks, v
 int rvt_stacked_histogram(const long long* x, const long long* y, const long long* pol, const long long* time,
                           size_t n_events, int bins, int H, int W, int count_cutoff, int fastmode, unsigned* scratch,
                           unsigned char* out, void* stream);
+
+/* Raw event streams -> a whole sequence of stacked-histogram windows (rvt_amd/csrc/evseq.hpp; host mirror
+ * rvt_amd.representations.EventSequenceBuilder).  Replaces the window loop of scripts/genx/preprocess_dataset.py:480-534: two
+ * searchsorted over the timestamps, one StackedHistogram.construct per window and, for the 1 Mpx sensor, the half-scale
+ * nearest-exact interpolate of the full-size histogram.  Bit-exact with that composition for any event order.
+ *
+ * streams: table of B rows of 48 bytes in DEVICE memory, 8-byte aligned:
+ *     const void* x;  const void* y;  const void* p;  const int64* t;  int64 n;  const int64* ts_end
+ *   x, y, p: n coordinates / polarities each, all of coord_bytes = 2 (int16), 4 (int32) or 8 (int64) bytes, one width per call;
+ *   t: n timestamps in microseconds, NON-DECREASING (the reference reader's timestamp repair is the caller's); n is read on the
+ *   device, so a captured graph replays after the host rewrote events and n in place, up to the buffers' capacity;
+ *   ts_end: the T window end timestamps of that sample (rows may share one array).
+ * Window w of sample b:  end = searchsorted(t, ts_end[w], side='right');  window_us > 0: start = searchsorted(t, ts_end[w] -
+ *   window_us, side='left');  window_events > 0: start = max(end - window_events, 0).  Exactly one of the two is positive.
+ *   bounds int64 [B][T][2] receives (start, end).  Windows may overlap and may be empty (an all-zero image).
+ * Per window, with t0 = t[start], t1 = t[end-1]:  t_idx = min(floorf((float)(t - t0) / (float)max(t1 - t0, 1) * bins), bins - 1)
+ *   (fp32, correctly rounded, no contraction: the rule of the per-window entry above), polarity < 0 counts as 0, events with
+ *   polarity > 1 or a coordinate outside the H x W sensor are skipped.  downsample_by_2: events with even x or even y are dropped
+ *   and the rest counted at (y >> 1, x >> 1) of an H/2 x W/2 image, which IS interpolate(scale_factor=0.5, mode='nearest-exact')
+ *   of the full-size histogram (source pixel 2i + 1), without ever forming it.  Then the accumulator wrap (uint8 if fastmode
+ *   else int16 and clamp(min=0)) and min(count_cutoff), as above.
+ * out uint8 [T][B][2*bins][H'][W'] (H' = H/2, W' = W/2 when down-sampling): window w of sample b at out + (w*B + b) * 2*bins*H'*W'.
+ *   Any byte alignment; nothing outside those B*T images is written.
+ * scratch: the ws_bytes query's size for windows_in_flight images of 32-bit counters, 16-byte aligned.  It must be ALL ZERO on entry
+ *   and is left all zero (the narrowing pass clears what it has read: no memset per call).  The B*T windows go through in
+ *   chunks of windows_in_flight: one count and one narrowing launch per chunk, after one launch for all bounds.
+ * count_blocks: workgroups per window of the count launch (they stride over the window; the grid cannot depend on bounds that
+ *   live on the device); 0 = sized by the library (about 2048 over a chunk, 8..256 per window). */
+size_t rvt_event_sequence_ws_bytes(int bins, int H, int W, int downsample_by_2, int windows_in_flight);
+int rvt_event_sequence(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
+                       int H, int W, int downsample_by_2, int count_cutoff, int fastmode, long long* bounds, void* scratch,
+                       int windows_in_flight, int count_blocks, unsigned char* out, void* stream);
 
 /* Spatial training augmentation (rvt_amd/csrc/augment.hpp; data/utils/augmentor.py RandomSpatialAugmentorGenX and
  * data/genx_utils/labels.py): horizontal flip, then zoom-in or zoom-out, of a batch of sequences and of their box labels.

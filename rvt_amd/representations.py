@@ -4,10 +4,30 @@ Mirror of the reference ``StackedHistogram`` (data/utils/representations.py:36-1
 ``construct(x, y, pol, time) -> uint8 (2*bins, H, W)``, ``get_shape`` / dtype helpers — computed by one HIP scatter
 kernel + one clamp/narrow pass (rvt_stacked_histogram, rvt_amd/csrc/events.hpp) instead of ``put_(accumulate=True)``.
 Integer work: bit-identical to the reference, including its accumulator wrap-around for hot pixels.
+
+``EventSequenceBuilder`` is the batched producer: B raw event streams in, the whole ``(T, B, 2*bins, H', W')`` uint8 sequence
+out (rvt_event_sequence, rvt_amd/csrc/evseq.hpp), with the reference's window slicing (scripts/genx/preprocess_dataset.py:
+480-534: ``searchsorted`` side='right' / 'left' in duration mode, ``max(end - N, 0)`` in count mode) and its half-scale
+``nearest-exact`` down-sampling of the 1 Mpx sensor done on the device.  Half-scale nearest-exact picks source pixel 2i + 1, so
+only events with odd x AND odd y reach the output: the builder drops the other three quarters before the atomic and counts
+straight into H/2 x W/2, never forming the full-size image.  Bit-identical to ``construct`` per window + ``interpolate``.
+
+  * ``build(streams, ts_end_us, out=None, bounds_out=None) -> (planes, bounds)``: streams = B tuples ``(x, y, p, t)`` of 1-D
+    device tensors (``t`` int64 microseconds; ``x, y, p`` all int16, all int32 or all int64: 14 B per event in the compact form),
+    ts_end_us int64 ``[T]`` or ``[B][T]``.  ``out`` may be any contiguous uint8 ``(T, B, C, H', W')`` tensor, e.g. a view into
+    the buffer a graphed step reads or the input of ``augment_planes``; bounds int64 ``[B][T][2]`` = (start, end) indices.
+  * ``make_table`` / ``write_table`` / ``build_from_table``: the pieces, for callers that keep their buffers.  The table rows
+    hold ADDRESSES and the event counts, which the kernels read on the device: capture ``build_from_table`` in a hipGraph,
+    then rewrite events and window ends in place, ``write_table`` the new counts (up to the buffers' capacity), and replay.
+  * Polarity < 0 counts as 0, as the reference's reader clips it (preprocess_dataset.py:181).
+
+Out of scope: ``MixedDensityEventStack``; reading H5 files; the reader's timestamp repair (``_correct_time``): ``t`` must be
+non-decreasing, which is the caller's to guarantee (the searches and the bin rule assume it, as the reference does).
+There is no PyTorch fallback: a missing kernel raises.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -57,3 +77,143 @@ class StackedHistogram:
         L.call('rvt_stacked_histogram', L.ptr(x), L.ptr(y), L.ptr(pol), L.ptr(time), x.numel(), self.bins, self.height,
                self.width, self.count_cutoff, int(self.fastmode), L.ptr(self._scratch), L.ptr(out), L.stream_of(out))
         return out
+
+
+_COORD_BYTES = {torch.int16: 2, torch.int32: 4, torch.int64: 8}
+TABLE_COLS = 6                       # include/rvt_hip.h: x, y, p, t, n, ts_end per stream, 8 bytes each
+DEFAULT_WINDOWS_IN_FLIGHT = 8        # scratch images per chunk (profiles/evseq_bench.txt)
+Stream = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
+
+
+class EventTable:
+    """The device stream table of one batch plus what it points at (the rows hold addresses: the tensors must stay alive)."""
+
+    def __init__(self, dev: torch.Tensor, streams: List[Stream], ts_end: torch.Tensor, B: int, T: int, coord_bytes: int, capacity: int):
+        self.dev, self.streams, self.ts_end, self.B, self.T, self.coord_bytes, self.capacity = dev, streams, ts_end, B, T, coord_bytes, capacity
+
+
+class EventSequenceBuilder:
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int] = None, fastmode: bool = True,
+                 downsample_by_2: bool = False, window_us: Optional[int] = None, window_events: Optional[int] = None,
+                 max_windows_in_flight: Optional[int] = None):
+        if bins < 1 or height < 1 or width < 1:
+            raise ValueError(f'bins={bins}, height={height}, width={width} must be positive')
+        if (window_us is None) == (window_events is None):                 # preprocess_dataset.py: exactly one of the two
+            raise ValueError(f'exactly one of window_us={window_us} and window_events={window_events} must be given')
+        if (window_us if window_us is not None else window_events) < 1:
+            raise ValueError(f'window_us={window_us} / window_events={window_events} must be positive')
+        if downsample_by_2 and (height < 2 or width < 2):
+            raise ValueError(f'downsample_by_2 needs height={height} and width={width} >= 2')
+        if count_cutoff is not None and count_cutoff < 1:
+            raise ValueError(f'count_cutoff={count_cutoff} must be >= 1')
+        if max_windows_in_flight is not None and not 1 <= max_windows_in_flight <= 65535:
+            raise ValueError(f'max_windows_in_flight={max_windows_in_flight} outside 1..65535')
+        self.bins, self.height, self.width = bins, height, width
+        self.count_cutoff = 255 if count_cutoff is None else min(count_cutoff, 255)
+        self.fastmode, self.downsample_by_2 = bool(fastmode), bool(downsample_by_2)
+        self.window_us, self.window_events = window_us, window_events
+        self.max_windows_in_flight = max_windows_in_flight
+        self._scratch = None
+
+    def get_shape(self) -> Tuple[int, int, int]:
+        """(2*bins, H', W') of one window, after the down-sampling."""
+        if self.downsample_by_2:
+            return 2 * self.bins, self.height // 2, self.width // 2
+        return 2 * self.bins, self.height, self.width
+
+    # ---- the stream table
+    def _host_table(self, streams: Sequence[Stream], ts_end: torch.Tensor, counts: Optional[Sequence[int]]):
+        streams = [tuple(s) for s in streams]
+        B = len(streams)
+        if B < 1:
+            raise ValueError('streams is empty')
+        dev, cdt = ts_end.device, None
+        rows = np.zeros((B, TABLE_COLS), dtype=np.int64)
+        capacity = 0
+        for b, s in enumerate(streams):
+            if len(s) != 4 or not all(torch.is_tensor(a) for a in s):
+                raise TypeError(f'streams[{b}] must be a tuple (x, y, p, t) of tensors')
+            x, y, p, t = s
+            if t.dtype != torch.int64:
+                raise TypeError(f'streams[{b}]: t must be int64 microseconds, got {t.dtype}')
+            cdt = x.dtype if cdt is None else cdt
+            if cdt not in _COORD_BYTES or any(a.dtype != cdt for a in (x, y, p)):
+                raise TypeError(f'streams[{b}]: x, y, p must share one of int16 / int32 / int64 across the batch, '
+                                f'got {x.dtype}, {y.dtype}, {p.dtype} (batch: {cdt})')
+            for a in s:
+                if a.dim() != 1 or a.numel() != t.numel() or a.device != dev:
+                    raise ValueError(f'streams[{b}]: x, y, p, t must be 1-D tensors of one length on {dev}, got {tuple(a.shape)} on {a.device}')
+            n = t.numel() if counts is None else int(counts[b])
+            if not 0 <= n <= t.numel():
+                raise ValueError(f'counts[{b}]={n} outside the buffers\' capacity 0..{t.numel()}')
+            te = ts_end if ts_end.dim() == 1 else ts_end[b]
+            rows[b] = (L.ptr(x), L.ptr(y), L.ptr(p), L.ptr(t), n, te.data_ptr())
+            capacity = max(capacity, t.numel())
+        return streams, rows, _COORD_BYTES[cdt], capacity
+
+    @staticmethod
+    def _check_ts_end(ts_end_us: torch.Tensor, B: int) -> torch.Tensor:
+        if not torch.is_tensor(ts_end_us) or ts_end_us.dtype != torch.int64:
+            raise TypeError(f'ts_end_us must be an int64 tensor, got {getattr(ts_end_us, "dtype", type(ts_end_us))}')
+        if not (ts_end_us.dim() == 1 or (ts_end_us.dim() == 2 and ts_end_us.shape[0] == B)) or ts_end_us.shape[-1] < 1:
+            raise ValueError(f'ts_end_us must be [T] or [B={B}][T] with T >= 1, got {tuple(ts_end_us.shape)}')
+        if not ts_end_us.is_contiguous():
+            raise ValueError('ts_end_us must be contiguous')
+        return ts_end_us
+
+    def make_table(self, streams: Sequence[Stream], ts_end_us: torch.Tensor, counts: Optional[Sequence[int]] = None) -> EventTable:
+        """The device table of B streams.  counts[b]: events of stream b in use (default: the whole tensors)."""
+        ts_end = self._check_ts_end(ts_end_us, len(streams))
+        streams, rows, cb, cap = self._host_table(streams, ts_end, counts)
+        return EventTable(torch.from_numpy(rows).to(ts_end.device), streams, ts_end, len(streams), int(ts_end.shape[-1]), cb, cap)
+
+    def write_table(self, table: EventTable, streams: Optional[Sequence[Stream]] = None, ts_end_us: Optional[torch.Tensor] = None,
+                    counts: Optional[Sequence[int]] = None) -> None:
+        """Rewrite an existing device table in place (same address: a captured graph replays with the new streams / counts).
+        streams / ts_end_us default to the table's own tensors, i.e. only the counts change."""
+        streams = table.streams if streams is None else streams
+        ts_end = table.ts_end if ts_end_us is None else self._check_ts_end(ts_end_us, len(streams))
+        streams, rows, cb, cap = self._host_table(streams, ts_end, counts)
+        if len(streams) != table.B or int(ts_end.shape[-1]) != table.T or cb != table.coord_bytes:
+            raise ValueError(f'the table was made for B={table.B}, T={table.T}, {table.coord_bytes}-byte coordinates')
+        table.dev.copy_(torch.from_numpy(rows))
+        table.streams, table.ts_end, table.capacity = streams, ts_end, max(cap, table.capacity)
+
+    # ---- the build
+    def windows_in_flight(self, windows: int) -> int:
+        return min(windows, self.max_windows_in_flight or DEFAULT_WINDOWS_IN_FLIGHT)
+
+    def workspace(self, device, windows: int) -> torch.Tensor:
+        """The zeroed scratch images (the call keeps them zero); allocate ahead of a graph capture by calling this once."""
+        C, H, W = self.get_shape()
+        need = L.get_lib().rvt_event_sequence_ws_bytes(self.bins, self.height, self.width, int(self.downsample_by_2),
+                                                       self.windows_in_flight(windows)) // 4
+        if self._scratch is None or self._scratch.device != torch.device(device) or self._scratch.numel() < need:
+            self._scratch = torch.zeros(need, dtype=torch.int32, device=device)
+        return self._scratch
+
+    def build_from_table(self, table: EventTable, out: Optional[torch.Tensor] = None, bounds_out: Optional[torch.Tensor] = None):
+        B, T = table.B, table.T
+        dev = table.dev.device
+        shape = (T, B) + self.get_shape()
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f'out must be contiguous uint8 {shape} on {dev}, got {out.dtype} {tuple(out.shape)}')
+        if bounds_out is None:
+            bounds_out = torch.empty(B, T, 2, dtype=torch.int64, device=dev)
+        elif tuple(bounds_out.shape) != (B, T, 2) or bounds_out.dtype != torch.int64 or bounds_out.device != dev or not bounds_out.is_contiguous():
+            raise ValueError(f'bounds_out must be contiguous int64 {(B, T, 2)} on {dev}, got {bounds_out.dtype} {tuple(bounds_out.shape)}')
+        scratch = self.workspace(dev, B * T)
+        # workgroups per window: the grid cannot follow bounds that live on the device, but never needs more than the capacity gives
+        count_blocks = max(1, min(256, -(-table.capacity // 8192)))
+        L.call('rvt_event_sequence', L.ptr(table.dev), B, T, table.coord_bytes, self.window_us or 0, self.window_events or 0, self.bins,
+               self.height, self.width, int(self.downsample_by_2), self.count_cutoff, int(self.fastmode), L.ptr(bounds_out),
+               L.ptr(scratch), self.windows_in_flight(B * T), count_blocks, L.ptr(out), L.stream_of(out))
+        return out, bounds_out
+
+    def build(self, streams: Sequence[Stream], ts_end_us: torch.Tensor, out: Optional[torch.Tensor] = None,
+              bounds_out: Optional[torch.Tensor] = None):
+        """streams: B tuples (x, y, p, t) of device tensors; ts_end_us int64 [T] or [B][T] -> (planes uint8 (T, B, C, H', W'),
+        bounds int64 [B][T][2])."""
+        return self.build_from_table(self.make_table(streams, ts_end_us), out, bounds_out)
