@@ -20,6 +20,8 @@
  *       rvt_stage_seq_fwd (+ _ws_bytes)                one call per backbone stage and sequence (no-grad forward)
  *       rvt_stacked_histogram                          event stream -> input tensor (row f4)
  *       rvt_event_sequence (+ _ws_bytes)               B raw event streams -> a whole (T, B, 2*bins, H', W') window sequence, slicing + half-scale
+ *       rvt_mixed_density_stack                        event stream -> the int8 (bins, H, W) mixed-density stack of one window
+ *       rvt_event_sequence_mixed (+ _ws_bytes)         B raw event streams -> a whole int8 (T, B, bins, H', W') mixed-density sequence
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
  *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
@@ -113,9 +115,10 @@ double rvt_probe_mfma(float* scratch, int iters, int workgroups, void* stream);
 size_t rvt_wgrad_workspace_floats(int dtype, int out_rows, int out_cols, int tokens, int want_colsum);
 
 /* Event-tensor cast + zero pad (modules/detection.py:133-134, utils/padding.py:29-44) fused with the
- * NCHW -> channels-last repack: src [F][Cin][h][w] (uint8 if src_u8 else float32) ->
+ * NCHW -> channels-last repack: src [F][Cin][h][w] (src_kind 0: float32, 1: uint8, 2: int8, the planes of the mixed-density
+ * stack, which the loader otherwise widens to float32 first: data/genx_utils/sequence_base.py:97-98) ->
  * dst [F][H][W][Cp] (dtype), zero padded to H>=h, W>=w, Cp>=Cin. */
-int rvt_prepack_input(const void* src, int src_u8, void* dst, int dtype, int F, int Cin, int h, int w,
+int rvt_prepack_input(const void* src, int src_kind, void* dst, int dtype, int F, int Cin, int h, int w,
                       int H, int W, int Cp, void* stream);
 
 /* Down-sampling conv (maxvit.py:160-168,175; bias-free): in [F][H][W][Cin], w [Cout][k*k*Cin]
@@ -610,6 +613,35 @@ size_t rvt_event_sequence_ws_bytes(int bins, int H, int W, int downsample_by_2, 
 int rvt_event_sequence(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
                        int H, int W, int downsample_by_2, int count_cutoff, int fastmode, long long* bounds, void* scratch,
                        int windows_in_flight, int count_blocks, unsigned char* out, void* stream);
+
+/* The reference's second representation, MixedDensityEventStack (data/utils/representations.py:130-218, selected by
+ * scripts/genx/conf_preprocess/representation/mixeddensity_stack.yaml, built in scripts/genx/preprocess_dataset.py:663-679), on the
+ * kernels of the sequence entry above (rvt_amd/csrc/evseq.hpp; host mirrors rvt_amd.representations.MixedDensityEventStack and
+ * EventSequenceBuilder(representation='mixed_density')).  Per window, with t0 / t1 its first / last timestamp:
+ *     tn  = clamp((float)(t - t0) / (float)max(t1 - t0, 1), 1e-6f, (float)(1 - 1e-6))        (fp32, one correctly rounded division)
+ *     bin = max(bins + e, 0), e = the unbiased binary exponent of tn = floor(log2(tn))         (representations.py:205-208)
+ *     img[bin][y][x] += polarity ? +1 : -1;   out[b] = int8(sum of img[0..b]) (low 8 bits, two's complement: the reference's int8
+ *     accumulator wrap and the wrap of its cumsum_channel);   count_cutoff >= 0: clamp to [-count_cutoff, count_cutoff] (<= 127);
+ *     count_cutoff < 0: no clamp.
+ *   The exponent IS the floor of the reference's bins - log(tn) / log(1/2).  The reference evaluates that quotient in fp32; it
+ *   agrees with the exponent for every event of a window whose span t1 - t0 is at most 2^20 us (every duration the reference ships
+ *   is 50 ms), so the output is bit-identical there.  On longer windows the reference itself puts an event whose tn lies a few
+ *   ulps below a power of two one bin too high (span 2^24, offset 8388606: reference bin 9 of 10, exact bin 8); this library
+ *   returns the exact bin.  Polarity < 0 counts as 0; events with polarity > 1 or a coordinate outside the sensor are skipped.
+ *
+ * rvt_mixed_density_stack: one window; x, y, pol, time int64 [n_events], time non-decreasing (MixedDensityEventStack.construct).
+ *   out int8 [bins][H][W], any byte alignment.  scratch: bins*H*W int32, 16-byte aligned, ALL ZERO on entry and left all zero.
+ * rvt_event_sequence_mixed: the arguments, stream table, window rule, bounds, chunking and scratch contract of rvt_event_sequence
+ *   (no fastmode), scratch sized by rvt_event_sequence_mixed_ws_bytes (half the histogram's: bins planes, not 2*bins).
+ *   downsample_by_2 is downsample_ev_repr (preprocess_dataset.py:467-477: +128, nearest-exact at half scale, -128), i.e. the odd
+ *   pixels of the full-size stack; sum, wrap and clamp are per pixel and commute with that selection.
+ *   out int8 [T][B][bins][H'][W']: window w of sample b at out + (w*B + b) * bins*H'*W'; nothing else is written. */
+int rvt_mixed_density_stack(const long long* x, const long long* y, const long long* pol, const long long* time, size_t n_events,
+                            int bins, int H, int W, int count_cutoff, int* scratch, signed char* out, void* stream);
+size_t rvt_event_sequence_mixed_ws_bytes(int bins, int H, int W, int downsample_by_2, int windows_in_flight);
+int rvt_event_sequence_mixed(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
+                             int H, int W, int downsample_by_2, int count_cutoff, long long* bounds, void* scratch,
+                             int windows_in_flight, int count_blocks, signed char* out, void* stream);
 
 /* Spatial training augmentation (rvt_amd/csrc/augment.hpp; data/utils/augmentor.py RandomSpatialAugmentorGenX and
  * data/genx_utils/labels.py): horizontal flip, then zoom-in or zoom-out, of a batch of sequences and of their box labels.

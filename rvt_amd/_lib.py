@@ -89,6 +89,8 @@ _SIGS = {
     'rvt_coco_accumulate': [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _sz, _vp],
     'rvt_optim_step': [_vp, _i, _vp, _i, _vp, _i, _vp],
     'rvt_event_sequence': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong] + [_i] * 6 + [_vp, _vp, _i, _i, _vp, _vp],
+    'rvt_mixed_density_stack': [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp],
+    'rvt_event_sequence_mixed': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ['rvt_last_error', 'rvt_is_emulator', 'rvt_wgrad_workspace_floats',
                                'rvt_mlp_fused_supported', 'rvt_lstm_scan_supported', 'rvt_mlp_bwd_fused_supported',
@@ -96,7 +98,8 @@ EXPORTS = sorted(list(_SIGS) + ['rvt_last_error', 'rvt_is_emulator', 'rvt_wgrad_
                                'rvt_lstm_scan_saves_gates', 'rvt_stem_supported', 'rvt_stem_wgrad_ws_floats', 'rvt_conv_dgrad4_supported',
                                'rvt_linear_dgrad_ln_supported', 'rvt_ln_linear_supported', 'rvt_tuning_defaults', 'rvt_get_tuning', 'rvt_set_tuning', 'rvt_probe_mfma',
                                'rvt_stage_seq_fwd_ws_bytes', 'rvt_lstm_scan3_supported', 'rvt_lstm_scan3_rows', 'rvt_lstm_scan3_rb', 'rvt_stage_seq_bwd_ws_bytes', 'rvt_simota_ws_bytes', 'rvt_mlp_bwd_both_supported',
-                               'rvt_yolox_postprocess_ws_bytes', 'rvt_coco_accumulate_ws_bytes', 'rvt_event_sequence_ws_bytes'])
+                               'rvt_yolox_postprocess_ws_bytes', 'rvt_coco_accumulate_ws_bytes', 'rvt_event_sequence_ws_bytes',
+                               'rvt_event_sequence_mixed_ws_bytes'])
 
 
 def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
@@ -154,6 +157,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.rvt_coco_accumulate_ws_bytes.argtypes = [ctypes.c_longlong, _i]
     lib.rvt_event_sequence_ws_bytes.restype = ctypes.c_size_t
     lib.rvt_event_sequence_ws_bytes.argtypes = [_i] * 5
+    lib.rvt_event_sequence_mixed_ws_bytes.restype = ctypes.c_size_t
+    lib.rvt_event_sequence_mixed_ws_bytes.argtypes = [_i] * 5
     lib.rvt_probe_mfma.restype = ctypes.c_double
     lib.rvt_probe_mfma.argtypes = [_vp, _i, _i, _vp]
     lib.rvt_tuning_defaults.restype = None

@@ -199,7 +199,7 @@ class RNNDetector(nn.Module):
 
     def forward_sequence(self, xs: Union[Tensor, Sequence[Tensor]], prev_states: Optional[LstmStates] = None,
                          token_masks: Optional[Tensor] = None):
-        """xs: (T,B,Cin,h,w) uint8/float or a list of T (B,Cin,h,w) tensors (the reference's EV_REPR list).
+        """xs: (T,B,Cin,h,w) uint8/int8/float or a list of T (B,Cin,h,w) tensors (the reference's EV_REPR list).
         Returns ({stage: (T,B,C,H,W)}, [(h,c)]*4); h = features of the last step, c fp32."""
         if not torch.is_tensor(xs):
             xs = torch.stack(list(xs), 0)
@@ -243,7 +243,7 @@ class RNNDetector(nn.Module):
         if token_masks is not None or any(sw.dws is not None for sw in mw.stages):
             return None
         src = xs.reshape(T * B, Cin, h, w)
-        if src.dtype not in (torch.uint8, torch.float32):
+        if src.dtype not in (torch.uint8, torch.int8, torch.float32):
             src = src.float()
         u8 = src.dtype == torch.uint8
         if u8:
@@ -312,7 +312,7 @@ class _BackboneSeqFn(torch.autograd.Function):
         geoms = mod.stage_geoms(Hm, Wm)
         need_grad = bool(grad_enabled) and any(ctx.needs_input_grad[4:])
         src = xs.reshape(T * B, Cin, h, w)
-        if src.dtype not in (torch.uint8, torch.float32):
+        if src.dtype not in (torch.uint8, torch.int8, torch.float32):
             src = src.float()
         g0 = geoms[0]
         if ops.stem_supported(src, dt, g0.C, g0.k, g0.stride, g0.pad):

@@ -86,18 +86,22 @@ int rvt_set_tuning(const RvtTuning* t) {
     return 0;
 }
 
-int rvt_prepack_input(const void* src, int src_u8, void* dst, int dtype, int F, int Cin, int h, int w, int H, int W,
+int rvt_prepack_input(const void* src, int src_kind, void* dst, int dtype, int F, int Cin, int h, int w, int H, int W,
                       int Cp, void* stream) {
     RVT_CHECK(Cp % 8 == 0 && Cp >= Cin && H >= h && W >= w, "prepack: bad shape Cp=%d Cin=%d", Cp, Cin);
+    RVT_CHECK(src_kind >= 0 && src_kind <= 2, "prepack: src_kind=%d is not 0 (float32), 1 (uint8) or 2 (int8)", src_kind);
     hipStream_t st = (hipStream_t)stream;
     RVT_CHECK(Cin <= 32, "prepack: Cin=%d > 32 staged channels", Cin);
-    const int seg = src_u8 ? PrepackSeg<unsigned char>::value : PrepackSeg<float>::value;
+    const int seg = src_kind ? PrepackSeg<unsigned char>::value : PrepackSeg<float>::value;
     size_t items = (size_t)F * H * ((W + seg - 1) / seg);
     int grid = (int)(items < 16384 ? (items < 1 ? 1 : items) : 16384);
     DISPATCH_DTYPE(dtype, {
-        if (src_u8)
+        if (src_kind == 1)
             hipLaunchKernelGGL((prepack_kernel<T, unsigned char>), dim3(grid), dim3(256), 0, st,
                                (const unsigned char*)src, (T*)dst, F, Cin, h, w, H, W, Cp);
+        else if (src_kind == 2)
+            hipLaunchKernelGGL((prepack_kernel<T, signed char>), dim3(grid), dim3(256), 0, st,
+                               (const signed char*)src, (T*)dst, F, Cin, h, w, H, W, Cp);
         else
             hipLaunchKernelGGL((prepack_kernel<T, float>), dim3(grid), dim3(256), 0, st, (const float*)src, (T*)dst, F,
                                Cin, h, w, H, W, Cp);

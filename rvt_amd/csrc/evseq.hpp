@@ -17,6 +17,17 @@
 // count n of every stream is read on the device too), so grid y is the window and a fixed number of workgroups stride over
 // [start, end).  Event loads are 16-byte vectors over groups of 8 events aligned to absolute index 8k (windows start anywhere:
 // the head and tail of at most 7 events each are peeled), when the four base pointers are 16-byte aligned; element loads else.
+//
+// The same skeleton builds the reference's second representation, MixedDensityEventStack (data/utils/representations.py:130-218;
+// EVSEQ_MIXED below): bounds and the load / peel loop are shared, the cell rule and the narrowing pass differ.
+//   count:    tn = clamp(float32(t - t0) / float32(max(t1 - t0, 1)), 1e-6f, float32(1 - 1e-6));  bin = max(bins + e, 0) with e the
+//             unbiased binary exponent of tn, which IS floor(bins - log(tn) / log(1/2)) as tn < 1 (no logarithm: exact for every
+//             span, and equal to the reference's fp32 log quotient wherever that one is right, i.e. spans up to 2^20 us);
+//             atomicAdd(+1 / -1) for polarity 1 / 0 into an int32 image [bins][H'][W']
+//   finalize: per pixel the running sum over the bin axis (the reference's cumsum_channel), the int8 wrap (low 8 bits: one wrap
+//             at the end equals the reference's wrap after the scatter and again after the sum, arithmetic modulo 256), the
+//             clamp to [-cutoff, cutoff] when there is a cutoff, int8 out; 16 pixels per lane and one 16-byte store per bin
+// The per-pixel sum, wrap and clamp commute with the half-scale selection of odd pixels, so `ds` works as above.
 #pragma once
 #include "common.hpp"
 
@@ -45,6 +56,7 @@ typedef u32x4 u32x4_a4 __attribute__((aligned(4)));          // dword-aligned 16
 #endif
 
 constexpr int EVSEQ_THREADS = 256;
+constexpr int EVSEQ_HIST = 0, EVSEQ_MIXED = 1;               // the representation a count kernel is instantiated for
 
 // ---------------------------------------------------------------------------------------------------------- window bounds
 __global__ void __launch_bounds__(EVSEQ_THREADS)
@@ -103,10 +115,36 @@ __device__ __forceinline__ long long evseq_cell_of(int xi, int yi, int pi, long 
     return (long long)((((size_t)pi * bins + ti) * Ho + yi) * Wo + xi);
 }
 
+// MixedDensityEventStack: the bin of one timestamp (see the head of this file)
+__device__ __forceinline__ int evseq_md_bin(long long ti64, long long t0, float den, int bins) {
+    float tn = (float)(ti64 - t0) / den;          // correctly rounded fp32 division, as torch's
+    const float lo = 1e-6f, hi = (float)(1.0 - 1e-6);
+    tn = tn < lo ? lo : (tn > hi ? hi : tn);
+    const int e = (int)((__builtin_bit_cast(unsigned, tn) >> 23) & 0xffu) - 127;         // tn >= 1e-6 is a normal number
+    return bins + e > 0 ? bins + e : 0;
+}
+
+// the scratch cell of one event in the [bins][Ho][Wo] image of the mixed-density stack, or -1 when the event does not count
+__device__ __forceinline__ long long evseq_md_cell_of(int xi, int yi, int pi, long long ti64, long long t0, float den, int bins, int H,
+                                                      int W, int ds, int Ho, int Wo) {
+    if (xi < 0 || xi >= W || yi < 0 || yi >= H || pi > 1) return -1;
+    if (ds) {
+        if (!(xi & 1) || !(yi & 1)) return -1;
+        xi >>= 1; yi >>= 1;
+    }
+    return (long long)((((size_t)evseq_md_bin(ti64, t0, den, bins)) * Ho + yi) * Wo + xi);
+}
+
+template <int REP>
 __device__ __forceinline__ void evseq_count_one(int xi, int yi, int pi, long long ti64, long long t0, float den, int bins, int H, int W,
                                                 int ds, int Ho, int Wo, unsigned* __restrict__ img) {
-    const long long c = evseq_cell_of(xi, yi, pi, ti64, t0, den, bins, H, W, ds, Ho, Wo);
-    if (c >= 0) atomicAdd(img + c, 1u);
+    if constexpr (REP == EVSEQ_MIXED) {
+        const long long c = evseq_md_cell_of(xi, yi, pi, ti64, t0, den, bins, H, W, ds, Ho, Wo);
+        if (c >= 0) atomicAdd(reinterpret_cast<int*>(img) + c, pi > 0 ? 1 : -1);          // polarity < 0 counts as 0, as above
+    } else {
+        const long long c = evseq_cell_of(xi, yi, pi, ti64, t0, den, bins, H, W, ds, Ho, Wo);
+        if (c >= 0) atomicAdd(img + c, 1u);
+    }
 }
 
 // 8 consecutive elements starting at an index that is a multiple of 8 of a 16-byte aligned array: 16-byte loads
@@ -122,8 +160,8 @@ template <class CT> __device__ __forceinline__ void evseq_load8(const EVSEQ_GLOB
 }
 
 // grid (blocks per window, windows of this chunk).  Window g = g0 + blockIdx.y is time step g / B of sample g % B and counts
-// into scratch image blockIdx.y (slot_cells apart).
-template <class CT> __global__ void __launch_bounds__(EVSEQ_THREADS)
+// into scratch image blockIdx.y (slot_cells apart).  REP selects the cell rule; loads and peeling are the same for both.
+template <class CT, int REP> __global__ void __launch_bounds__(EVSEQ_THREADS)
 evseq_count_kernel(const EvStream* __restrict__ table, const long long* __restrict__ bounds, int g0, int B, int T, int bins, int H,
                    int W, int ds, size_t slot_cells, unsigned* __restrict__ scratch) {
     const int g = g0 + blockIdx.y;
@@ -163,6 +201,7 @@ evseq_count_kernel(const EvStream* __restrict__ table, const long long* __restri
                 tv[2 * k] = tq[0]; tv[2 * k + 1] = tq[1];
             }
 #ifdef EVSEQ_AGGREGATE
+            static_assert(REP == EVSEQ_HIST, "EVSEQ_AGGREGATE is a variant of the stacked-histogram count only");
             long long cur = -1;
             unsigned cnt = 0;
 #pragma unroll
@@ -175,20 +214,20 @@ evseq_count_kernel(const EvStream* __restrict__ table, const long long* __restri
             if (cur >= 0) atomicAdd(img + cur, cnt);
 #else
 #pragma unroll
-            for (int k = 0; k < 8; k++) evseq_count_one(xv[k], yv[k], pv[k], tv[k], t0, den, bins, H, W, ds, Ho, Wo, img);
+            for (int k = 0; k < 8; k++) evseq_count_one<REP>(xv[k], yv[k], pv[k], tv[k], t0, den, bins, H, W, ds, Ho, Wo, img);
 #endif
         }
         if (blockIdx.x == 0 && threadIdx.x < 16) {              // peeled head [start, a0) and tail [a1, end): at most 7 events each
             const long long i = threadIdx.x < 8 ? start + threadIdx.x : a1 + (threadIdx.x - 8);
             const long long lim = threadIdx.x < 8 ? a0 : end;
             if (i < lim)
-                evseq_count_one(evseq_narrow<CT>(x[i]), evseq_narrow<CT>(y[i]), evseq_narrow<CT>(pol[i]), time[i], t0, den, bins, H, W, ds,
-                                Ho, Wo, img);
+                evseq_count_one<REP>(evseq_narrow<CT>(x[i]), evseq_narrow<CT>(y[i]), evseq_narrow<CT>(pol[i]), time[i], t0, den, bins, H, W,
+                                     ds, Ho, Wo, img);
         }
     } else {
         for (long long i = start + (long long)blockIdx.x * EVSEQ_THREADS + threadIdx.x; i < end; i += (long long)gridDim.x * EVSEQ_THREADS)
-            evseq_count_one(evseq_narrow<CT>(x[i]), evseq_narrow<CT>(y[i]), evseq_narrow<CT>(pol[i]), time[i], t0, den, bins, H, W, ds, Ho,
-                            Wo, img);
+            evseq_count_one<REP>(evseq_narrow<CT>(x[i]), evseq_narrow<CT>(y[i]), evseq_narrow<CT>(pol[i]), time[i], t0, den, bins, H, W, ds,
+                                 Ho, Wo, img);
     }
 }
 
@@ -231,6 +270,82 @@ evseq_finalize_kernel(unsigned* __restrict__ scratch, unsigned char* __restrict_
             dst[i] = (unsigned char)evseq_cell(img[i], cutoff, fastmode);
             img[i] = 0u;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------- mixed-density stack
+// one window given as four int64 arrays (rvt_mixed_density_stack): the cell rule above at full size into one image
+__global__ void __launch_bounds__(EVSEQ_THREADS)
+evseq_md_window_kernel(const long long* __restrict__ x, const long long* __restrict__ y, const long long* __restrict__ pol,
+                       const long long* __restrict__ time, size_t n, int bins, int H, int W, unsigned* __restrict__ img) {
+    const long long t0 = time[0], t1 = time[n - 1];
+    const float den = (float)((t1 - t0) > 1 ? (t1 - t0) : 1);
+    for (size_t i = (size_t)blockIdx.x * EVSEQ_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * EVSEQ_THREADS)
+        evseq_count_one<EVSEQ_MIXED>(evseq_narrow<long long>(x[i]), evseq_narrow<long long>(y[i]), evseq_narrow<long long>(pol[i]), time[i],
+                                     t0, den, bins, H, W, 0, H, W, img);
+}
+
+// running sum (modulo 2^32) -> the reference's int8 value: wrap, then the clamp when there is a cutoff (cutoff < 0: none)
+__device__ __forceinline__ unsigned evseq_md_value(unsigned run, int cutoff) {
+    int v = (int)(signed char)(run & 0xffu);
+    if (cutoff >= 0) { v = v < -cutoff ? -cutoff : v; v = v > cutoff ? cutoff : v; }
+    return (unsigned)v & 0xffu;
+}
+
+// one pixel through all its bins, cell by cell
+__device__ __forceinline__ void evseq_md_pixel(unsigned* __restrict__ img, signed char* __restrict__ dst, size_t i, size_t plane, int bins,
+                                               int cutoff) {
+    unsigned run = 0u;
+    for (int b = 0; b < bins; b++) {
+        const size_t c = (size_t)b * plane + i;
+        run += img[c];
+        img[c] = 0u;
+        dst[c] = (signed char)evseq_md_value(run, cutoff);
+    }
+}
+
+// grid (blocks per window, windows of this chunk): scratch image blockIdx.y [bins][plane] -> out + (g0 + blockIdx.y) * bins * plane,
+// and the image is left zero.  A lane owns 16 consecutive pixels and walks the bins with their running sums in registers.  The
+// 16-byte stores need every plane's piece aligned, i.e. plane % 16 == 0 and a start behind `head` peeled pixels; the peeled
+// pixels (at most 15 at either end) and every pixel of a plane size off that grid (7 x 10, ...) go one pixel per lane.
+__global__ void __launch_bounds__(EVSEQ_THREADS)
+evseq_md_finalize_kernel(unsigned* __restrict__ scratch, signed char* __restrict__ out, int g0, int bins, size_t plane, size_t slot_cells,
+                         int cutoff) {
+    unsigned* __restrict__ img = scratch + (size_t)blockIdx.y * slot_cells;
+    signed char* __restrict__ dst = out + (size_t)(g0 + blockIdx.y) * bins * plane;
+    const size_t lane = (size_t)blockIdx.x * EVSEQ_THREADS + threadIdx.x, lanes = (size_t)gridDim.x * EVSEQ_THREADS;
+    if (plane & 15) {
+        for (size_t i = lane; i < plane; i += lanes) evseq_md_pixel(img, dst, i, plane, bins, cutoff);
+        return;
+    }
+    size_t head = (size_t)((16 - ((uintptr_t)dst & 15)) & 15);
+    head = head < plane ? head : plane;
+    const size_t nvec = (plane - head) >> 4;
+    for (size_t q = lane; q < nvec; q += lanes) {
+        const size_t i = head + 16 * q;
+        unsigned run[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) run[k] = 0u;
+        for (int b = 0; b < bins; b++) {
+            unsigned* __restrict__ cell = img + (size_t)b * plane + i;
+            u32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const u32x4 c = *reinterpret_cast<const u32x4_a4*>(cell + 4 * k);
+                *reinterpret_cast<u32x4_a4*>(cell + 4 * k) = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 4; j++) run[4 * k + j] += c[j];
+                o[k] = evseq_md_value(run[4 * k], cutoff) | (evseq_md_value(run[4 * k + 1], cutoff) << 8) |
+                       (evseq_md_value(run[4 * k + 2], cutoff) << 16) | (evseq_md_value(run[4 * k + 3], cutoff) << 24);
+            }
+            *reinterpret_cast<u32x4*>(dst + (size_t)b * plane + i) = o;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 32) {
+        const size_t body_end = head + 16 * nvec;
+        const size_t i = threadIdx.x < 16 ? (size_t)threadIdx.x : body_end + (threadIdx.x - 16);
+        const size_t lim = threadIdx.x < 16 ? head : plane;
+        if (i < lim) evseq_md_pixel(img, dst, i, plane, bins, cutoff);
     }
 }
 

@@ -166,11 +166,11 @@ colsum_kernel(const T* __restrict__ x, float* __restrict__ out, int rows, int N,
 }
 
 // ---- event-tensor prepack (reference modules/detection.py:133-134 cast + utils/padding.py:29-44) ----
-// src: [F][Cin][h][w] uint8 or float, unpadded.  dst: [F][H][W][Cp] T, zero padded bottom/right and in channels.
+// src: [F][Cin][h][w] uint8, int8 or float, unpadded.  dst: [F][H][W][Cp] T, zero padded bottom/right and in channels.
 // A workgroup transposes one piece (PrepackSeg pixels) of an image row through LDS: plane-major source rows come in as
-// whole contiguous segments (uint8 as 4-byte words when the geometry allows), channel-last pixels go out as
+// whole contiguous segments (uint8 / int8 as 4-byte words when the geometry allows), channel-last pixels go out as
 // consecutive 16-byte chunks — both sides of the transpose touch memory in full cache lines.
-// pixels per work item: a whole 640-pixel row for uint8 planes (20 KiB of LDS; measured 1.58 ms vs 2.30 at 128 pixels on the
+// pixels per work item: a whole 640-pixel row for uint8 / int8 planes (20 KiB of LDS; measured 1.58 ms vs 2.30 at 128 pixels on the
 // 1 Mpx batch), 128 for float planes (LDS)
 template <class S> struct PrepackSeg { static constexpr int value = sizeof(S) == 1 ? 640 : 128; };
 template <class T, class S>

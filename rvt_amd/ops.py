@@ -34,13 +34,16 @@ def _wgrad_ws(like: Tensor, out_rows: int, out_cols: int, tokens: int, want_cols
     return ws
 
 
+_PREPACK_KIND = {torch.float32: 0, torch.uint8: 1, torch.int8: 2}      # include/rvt_hip.h: src_kind
+
+
 def prepack_input(src: Tensor, H: int, W: int, Cp: int, dtype: torch.dtype, out: Optional[Tensor] = None) -> Tensor:
-    """(F,Cin,h,w) uint8/float32 -> (F,H,W,Cp) `dtype`, zero padded (cast+pad of modules/detection.py:133-134)."""
-    assert src.dim() == 4 and src.dtype in (torch.uint8, torch.float32)
+    """(F,Cin,h,w) uint8/int8/float32 -> (F,H,W,Cp) `dtype`, zero padded (cast+pad of modules/detection.py:133-134)."""
+    assert src.dim() == 4 and src.dtype in _PREPACK_KIND
     src = src.contiguous()
     F_, Cin, h, w = src.shape
     dst = _out(src, (F_, H, W, Cp), dtype, out)
-    L.call('rvt_prepack_input', L.ptr(src), int(src.dtype == torch.uint8), L.ptr(dst), L.dtype_code(dtype),
+    L.call('rvt_prepack_input', L.ptr(src), _PREPACK_KIND[src.dtype], L.ptr(dst), L.dtype_code(dtype),
            F_, Cin, h, w, H, W, Cp, L.stream_of(src))
     return dst
 

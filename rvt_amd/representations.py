@@ -1,4 +1,4 @@
-"""Event representation on the device: the producer of the uint8 event tensors the backbone consumes.
+"""Event representations on the device: the producers of the event tensors the backbone consumes.
 
 Mirror of the reference ``StackedHistogram`` (data/utils/representations.py:36-117): same constructor arguments, same
 ``construct(x, y, pol, time) -> uint8 (2*bins, H, W)``, ``get_shape`` / dtype helpers — computed by one HIP scatter
@@ -21,7 +21,21 @@ straight into H/2 x W/2, never forming the full-size image.  Bit-identical to ``
     then rewrite events and window ends in place, ``write_table`` the new counts (up to the buffers' capacity), and replay.
   * Polarity < 0 counts as 0, as the reference's reader clips it (preprocess_dataset.py:181).
 
-Out of scope: ``MixedDensityEventStack``; reading H5 files; the reader's timestamp repair (``_correct_time``): ``t`` must be
+``MixedDensityEventStack`` mirrors the reference's second representation (data/utils/representations.py:130-218): same
+constructor, ``construct(x, y, pol, time) -> int8 (bins, H, W)`` (rvt_mixed_density_stack), and
+``EventSequenceBuilder(..., representation='mixed_density')`` builds the whole int8 ``(T, B, bins, H', W')`` sequence
+(rvt_event_sequence_mixed) with the same table, bounds, workspace and graph-capture contract; half-scale is the reference's
+``downsample_ev_repr`` (preprocess_dataset.py:467-477), i.e. the odd pixels again.  Polarity 1 / 0 adds +1 / -1 to bin
+``floor(clamp(bins - log(tn) / log(1/2), min=0))`` of its pixel, ``tn`` the fp32 normalised time clamped to [1e-6, 1 - 1e-6];
+then the prefix sum over the bins, the int8 wrap and, when ``count_cutoff`` (0..127) is given, the clamp to +-cutoff.
+The device takes the bin from the binary exponent of ``tn`` (``bins + floor(log2(tn))``, no logarithm), which is the exact
+value of that expression.  Span contract: the output is bit-identical to the reference wherever a window's span
+``t[-1] - t[0]`` is at most 2^20 us (every duration-mode configuration the reference ships uses 50 ms).  From 2^22 us upward
+the reference's own fp32 ``log`` quotient rounds to an integer for events a few ulps below a power of two and puts them one
+bin too high (span 2^24, offset 8 388 606: reference bin 9, exact bin 8); the device returns the mathematically exact bin there.
+int8 planes go straight into ``RNNDetector.forward`` / ``forward_sequence`` (no float32 copy).
+
+Out of scope: reading H5 files; the reader's timestamp repair (``_correct_time``): ``t`` must be
 non-decreasing, which is the caller's to guarantee (the searches and the bin rule assume it, as the reference does).
 There is no PyTorch fallback: a missing kernel raises.
 """
@@ -79,7 +93,50 @@ class StackedHistogram:
         return out
 
 
+class MixedDensityEventStack:
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int] = None, allow_compilation: bool = False):
+        assert bins >= 1 and height >= 1 and width >= 1       # representations.py:133-138
+        self.bins, self.height, self.width = bins, height, width
+        self.count_cutoff = count_cutoff
+        if count_cutoff is not None:                          # representations.py:140-142; None = no clamp
+            assert isinstance(count_cutoff, int)
+            assert 0 <= count_cutoff <= 2 ** 7 - 1
+        self.allow_compilation = allow_compilation            # the reference's torch.compile switch: nothing to compile here
+        self._scratch = None
+
+    @staticmethod
+    def get_numpy_dtype() -> np.dtype:
+        return np.dtype('int8')
+
+    @staticmethod
+    def get_torch_dtype() -> torch.dtype:
+        return torch.int8
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return torch.int8
+
+    def get_shape(self) -> Tuple[int, int, int]:
+        return self.bins, self.height, self.width
+
+    def construct(self, x: torch.Tensor, y: torch.Tensor, pol: torch.Tensor, time: torch.Tensor) -> torch.Tensor:
+        dev = x.device
+        assert y.device == pol.device == time.device == dev
+        for t in (x, y, pol, time):
+            assert not torch.is_floating_point(t) and not torch.is_complex(t)      # representations.py:167-170
+        assert x.numel() == y.numel() == pol.numel() == time.numel()
+        if self._scratch is None or self._scratch.device != dev:
+            # zeroed once: the narrowing pass clears what it reads, so the image is clean again after every call
+            self._scratch = torch.zeros(self.bins * self.height * self.width, dtype=torch.int32, device=dev)
+        out = torch.empty(self.get_shape(), dtype=torch.int8, device=dev)
+        x, y, pol, time = (t.to(torch.int64).contiguous() for t in (x, y, pol, time))
+        L.call('rvt_mixed_density_stack', L.ptr(x), L.ptr(y), L.ptr(pol), L.ptr(time), x.numel(), self.bins, self.height, self.width,
+               -1 if self.count_cutoff is None else self.count_cutoff, L.ptr(self._scratch), L.ptr(out), L.stream_of(out))
+        return out
+
+
 _COORD_BYTES = {torch.int16: 2, torch.int32: 4, torch.int64: 8}
+REPRESENTATIONS = ('stacked_histogram', 'mixed_density')
 TABLE_COLS = 6                       # include/rvt_hip.h: x, y, p, t, n, ts_end per stream, 8 bytes each
 DEFAULT_WINDOWS_IN_FLIGHT = 8        # scratch images per chunk (profiles/evseq_bench.txt)
 Stream = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
@@ -95,7 +152,10 @@ class EventTable:
 class EventSequenceBuilder:
     def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int] = None, fastmode: bool = True,
                  downsample_by_2: bool = False, window_us: Optional[int] = None, window_events: Optional[int] = None,
-                 max_windows_in_flight: Optional[int] = None):
+                 max_windows_in_flight: Optional[int] = None, representation: str = 'stacked_histogram'):
+        if representation not in REPRESENTATIONS:
+            raise ValueError(f'representation={representation!r} is not one of {REPRESENTATIONS}')
+        mixed = representation == 'mixed_density'
         if bins < 1 or height < 1 or width < 1:
             raise ValueError(f'bins={bins}, height={height}, width={width} must be positive')
         if (window_us is None) == (window_events is None):                 # preprocess_dataset.py: exactly one of the two
@@ -104,22 +164,33 @@ class EventSequenceBuilder:
             raise ValueError(f'window_us={window_us} / window_events={window_events} must be positive')
         if downsample_by_2 and (height < 2 or width < 2):
             raise ValueError(f'downsample_by_2 needs height={height} and width={width} >= 2')
-        if count_cutoff is not None and count_cutoff < 1:
+        if mixed:
+            if fastmode is not True:
+                raise ValueError(f'fastmode={fastmode} belongs to the stacked histogram: the mixed-density stack has no such mode')
+            if count_cutoff is not None and not 0 <= count_cutoff <= 127:     # representations.py:140-142
+                raise ValueError(f'count_cutoff={count_cutoff} must be None or 0..127 for the mixed-density stack')
+        elif count_cutoff is not None and count_cutoff < 1:
             raise ValueError(f'count_cutoff={count_cutoff} must be >= 1')
         if max_windows_in_flight is not None and not 1 <= max_windows_in_flight <= 65535:
             raise ValueError(f'max_windows_in_flight={max_windows_in_flight} outside 1..65535')
         self.bins, self.height, self.width = bins, height, width
-        self.count_cutoff = 255 if count_cutoff is None else min(count_cutoff, 255)
+        self.representation, self.mixed = representation, mixed
+        if mixed:
+            self.count_cutoff = -1 if count_cutoff is None else int(count_cutoff)       # the C side's "no clamp"
+        else:
+            self.count_cutoff = 255 if count_cutoff is None else min(count_cutoff, 255)
+        self.dtype = torch.int8 if mixed else torch.uint8
         self.fastmode, self.downsample_by_2 = bool(fastmode), bool(downsample_by_2)
         self.window_us, self.window_events = window_us, window_events
         self.max_windows_in_flight = max_windows_in_flight
         self._scratch = None
 
     def get_shape(self) -> Tuple[int, int, int]:
-        """(2*bins, H', W') of one window, after the down-sampling."""
+        """(2*bins, H', W') of one window, after the down-sampling; (bins, H', W') for the mixed-density stack."""
+        C = self.bins if self.mixed else 2 * self.bins
         if self.downsample_by_2:
-            return 2 * self.bins, self.height // 2, self.width // 2
-        return 2 * self.bins, self.height, self.width
+            return C, self.height // 2, self.width // 2
+        return C, self.height, self.width
 
     # ---- the stream table
     def _host_table(self, streams: Sequence[Stream], ts_end: torch.Tensor, counts: Optional[Sequence[int]]):
@@ -186,8 +257,9 @@ class EventSequenceBuilder:
     def workspace(self, device, windows: int) -> torch.Tensor:
         """The zeroed scratch images (the call keeps them zero); allocate ahead of a graph capture by calling this once."""
         C, H, W = self.get_shape()
-        need = L.get_lib().rvt_event_sequence_ws_bytes(self.bins, self.height, self.width, int(self.downsample_by_2),
-                                                       self.windows_in_flight(windows)) // 4
+        lib = L.get_lib()
+        ws_bytes = lib.rvt_event_sequence_mixed_ws_bytes if self.mixed else lib.rvt_event_sequence_ws_bytes
+        need = ws_bytes(self.bins, self.height, self.width, int(self.downsample_by_2), self.windows_in_flight(windows)) // 4
         if self._scratch is None or self._scratch.device != torch.device(device) or self._scratch.numel() < need:
             self._scratch = torch.zeros(need, dtype=torch.int32, device=device)
         return self._scratch
@@ -197,9 +269,9 @@ class EventSequenceBuilder:
         dev = table.dev.device
         shape = (T, B) + self.get_shape()
         if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-            raise ValueError(f'out must be contiguous uint8 {shape} on {dev}, got {out.dtype} {tuple(out.shape)}')
+            out = torch.empty(shape, dtype=self.dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != self.dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError(f'out must be contiguous {str(self.dtype)[6:]} {shape} on {dev}, got {out.dtype} {tuple(out.shape)}')
         if bounds_out is None:
             bounds_out = torch.empty(B, T, 2, dtype=torch.int64, device=dev)
         elif tuple(bounds_out.shape) != (B, T, 2) or bounds_out.dtype != torch.int64 or bounds_out.device != dev or not bounds_out.is_contiguous():
@@ -207,6 +279,11 @@ class EventSequenceBuilder:
         scratch = self.workspace(dev, B * T)
         # workgroups per window: the grid cannot follow bounds that live on the device, but never needs more than the capacity gives
         count_blocks = max(1, min(256, -(-table.capacity // 8192)))
+        if self.mixed:
+            L.call('rvt_event_sequence_mixed', L.ptr(table.dev), B, T, table.coord_bytes, self.window_us or 0, self.window_events or 0,
+                   self.bins, self.height, self.width, int(self.downsample_by_2), self.count_cutoff, L.ptr(bounds_out), L.ptr(scratch),
+                   self.windows_in_flight(B * T), count_blocks, L.ptr(out), L.stream_of(out))
+            return out, bounds_out
         L.call('rvt_event_sequence', L.ptr(table.dev), B, T, table.coord_bytes, self.window_us or 0, self.window_events or 0, self.bins,
                self.height, self.width, int(self.downsample_by_2), self.count_cutoff, int(self.fastmode), L.ptr(bounds_out),
                L.ptr(scratch), self.windows_in_flight(B * T), count_blocks, L.ptr(out), L.stream_of(out))
@@ -215,5 +292,5 @@ class EventSequenceBuilder:
     def build(self, streams: Sequence[Stream], ts_end_us: torch.Tensor, out: Optional[torch.Tensor] = None,
               bounds_out: Optional[torch.Tensor] = None):
         """streams: B tuples (x, y, p, t) of device tensors; ts_end_us int64 [T] or [B][T] -> (planes uint8 (T, B, C, H', W'),
-        bounds int64 [B][T][2])."""
+        bounds int64 [B][T][2]); int8 planes for the mixed-density stack."""
         return self.build_from_table(self.make_table(streams, ts_end_us), out, bounds_out)
