@@ -24,6 +24,7 @@
  *       rvt_event_sequence_mixed (+ _ws_bytes)         B raw event streams -> a whole int8 (T, B, bins, H', W') mixed-density sequence
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
  *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
+ *       rvt_yolox_detect (+ _ws_bytes)                 head maps -> decode + score filter + batched NMS, one launch
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
@@ -558,6 +559,23 @@ int rvt_simota_loss(const float* pred_train, const float* labels, const int* lev
 size_t rvt_yolox_postprocess_ws_bytes(int B, int A, int num_classes);
 int rvt_yolox_postprocess(const float* pred, int B, int A, int num_classes, float conf_thre, float nms_thre, int class_agnostic,
                           int max_det, float* det, int* count, int* anchor_idx, void* ws, size_t ws_bytes, void* stream);
+
+/* The eval-mode detection tail in ONE launch: head maps in, padded detections out (rvt_amd/csrc/nms.hpp, yolox_detect_kernel; host
+ * mirror rvt_amd/postprocess.py: detect_padded).  Writes exactly what rvt_yolox_decode into pred_infer for every level followed by
+ * rvt_yolox_postprocess writes, bit for bit, without the [B][A][5+nc] fp32 tensor between them.
+ *   reg_obj[l] / cls[l] (HOST arrays of L device pointers, read during the call): level l's maps [B*H*W][ld_ro] and [B*H*W][ld_cls]
+ *   of `dtype` (fp32 or bf16) as rvt_yolox_decode takes them; level_hw / level_stride as rvt_simota_loss takes them, 1 <= L <= 8,
+ *   the levels must add up to A.  The level table and the pointers travel by value in the kernel arguments.
+ *   Score: sigmoid of the objectness logit times the max over the SIGMOIDS of the class logits (lowest class on an exact tie of the
+ *   sigmoid values), one fp32 multiply.  The box is decoded for the candidates only, with the decode kernel's expressions:
+ *   (reg + grid) * stride for the centre, expf(reg) * stride for the extent.  conf_thre .. anchor_idx, the ordering rules, det /
+ *   count / anchor_idx and the supported ranges are those of rvt_yolox_postprocess; more than 8 levels, a null map, ld_ro < 5 or
+ *   ld_cls < num_classes also return non-zero with the last error set before any launch.  Allocates nothing, never synchronises:
+ *   capturable.  ws: the ws_bytes query's size (the same 52 bytes per anchor and image), contents need not survive the call. */
+size_t rvt_yolox_detect_ws_bytes(int B, int A, int num_classes);
+int rvt_yolox_detect(const void* const* reg_obj, const void* const* cls, int ld_ro, int ld_cls, int dtype, const int* level_hw,
+                     const int* level_stride, int L, int B, int A, int num_classes, float conf_thre, float nms_thre, int class_agnostic,
+                     int max_det, float* det, int* count, int* anchor_idx, void* ws, size_t ws_bytes, void* stream);
 
 /* Zero state rows of samples with mask[b] != 0 (modules/utils/detection.py:96-113).
  * st is [B][per_sample] of float32 (is_f32) or `dtype`. */

@@ -194,6 +194,9 @@ def model(name: str, a) -> Optional[Tuple[float, float]]:
     if name == 'rvt_yolox_postprocess':                          # pred in, det / count / anchor_idx out, the workspace written and read back
         B, A, nc, max_det = a[1], a[2], a[3], a[7]
         return 0.0, 1.0 * B * A * (5 + nc) * 4 + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if P(10) else 0) + 2.0 * 52 * B * A
+    if name == 'rvt_yolox_detect':                               # the levels' maps read once (A rows per image over all levels), det / count /
+        ld_ro, ld_cls, e, B, A, max_det = a[2], a[3], _elt(a[4]), a[8], a[9], a[14]          # anchor_idx out, the workspace written and read back
+        return 0.0, 1.0 * B * A * (ld_ro + ld_cls) * e + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if P(17) else 0) + 2.0 * 52 * B * A
     if name == 'rvt_augment_planes':                             # uint8 planes in and out; the per-sample windows live in the device table,
         F, B, C, H, W = a[3:8]                                   # so this is the bound of a flip: every byte read once, written once
         return 0.0, 2.0 * F * C * H * W + 32.0 * B
@@ -246,6 +249,9 @@ def executed(name: str, a) -> Optional[float]:
     if name == 'rvt_yolox_postprocess':                          # vector (not MFMA) work, data dependent: the all-pairs bound of the greedy
         B, A = a[1], a[2]                                        # NMS, 12 flops per IoU test (4 min/max, 3 sub, 2 max, mul, add, div)
         return 12.0 * B * A * (A - 1) / 2
+    if name == 'rvt_yolox_detect':                               # the same NMS bound, plus one sigmoid (exp, add, divide: 3) per class and
+        B, A, nc = a[8], a[9], a[10]                             # objectness logit of every anchor
+        return 12.0 * B * A * (A - 1) / 2 + 3.0 * B * A * (1 + nc)
     if name == 'rvt_lstm_scan_bwd' and not P(16):
         M, C, T = a[18], a[19], a[20]
         return fl + 16.0 * M * C * C * T

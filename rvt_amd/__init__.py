@@ -1,6 +1,7 @@
 """rvt_amd — MI355X (gfx950)-native recurrent-vision-transformer backbone (hot path of uzh-rpg/RVT)."""
 from .backbone import RNNDetector, RNNDetectorStage, build_recurrent_backbone  # noqa: F401
 from .config import AttrDict, backbone_config, modify_backbone_config  # noqa: F401
+from .detector import YoloXDetector  # noqa: F401,E402  (backbone + PAFPN + head: the reference's detector class, native)
 from .postprocess import postprocess, postprocess_padded  # noqa: F401,E402  (detection post-processing: score filter + batched NMS)
 from .evaluation import DetectionEvaluator, PropheseeEvaluator  # noqa: F401,E402  (Prophesee / COCO mAP of the detections, on the device)
 from . import optim  # noqa: F401,E402  (optimizer step on the device: value clip + AdamW + OneCycleLR in one launch)

@@ -83,6 +83,7 @@ _SIGS = {
     'rvt_yolox_decode_bwd': [_vp] * 5 + [_i] * 10 + [_vp],
     'rvt_simota_loss': [_vp] * 4 + [_i] * 5 + [_vp] * 5 + [ctypes.c_size_t, _vp],
     'rvt_yolox_postprocess': [_vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    'rvt_yolox_detect': [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     'rvt_augment_planes': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'rvt_augment_labels': [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     'rvt_coco_match': [_vp] * 5 + [_i] * 5 + [_f, _f] + [_vp] * 4 + [_i, _vp, _vp],
@@ -99,7 +100,7 @@ EXPORTS = sorted(list(_SIGS) + ['rvt_last_error', 'rvt_is_emulator', 'rvt_wgrad_
                                'rvt_linear_dgrad_ln_supported', 'rvt_ln_linear_supported', 'rvt_tuning_defaults', 'rvt_get_tuning', 'rvt_set_tuning', 'rvt_probe_mfma',
                                'rvt_stage_seq_fwd_ws_bytes', 'rvt_lstm_scan3_supported', 'rvt_lstm_scan3_rows', 'rvt_lstm_scan3_rb', 'rvt_stage_seq_bwd_ws_bytes', 'rvt_simota_ws_bytes', 'rvt_mlp_bwd_both_supported',
                                'rvt_yolox_postprocess_ws_bytes', 'rvt_coco_accumulate_ws_bytes', 'rvt_event_sequence_ws_bytes',
-                               'rvt_event_sequence_mixed_ws_bytes'])
+                               'rvt_event_sequence_mixed_ws_bytes', 'rvt_yolox_detect_ws_bytes'])
 
 
 def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
@@ -153,6 +154,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.rvt_simota_ws_bytes.argtypes = [_i, _i, _i]
     lib.rvt_yolox_postprocess_ws_bytes.restype = ctypes.c_size_t
     lib.rvt_yolox_postprocess_ws_bytes.argtypes = [_i, _i, _i]
+    lib.rvt_yolox_detect_ws_bytes.restype = ctypes.c_size_t
+    lib.rvt_yolox_detect_ws_bytes.argtypes = [_i, _i, _i]
     lib.rvt_coco_accumulate_ws_bytes.restype = ctypes.c_size_t
     lib.rvt_coco_accumulate_ws_bytes.argtypes = [ctypes.c_longlong, _i]
     lib.rvt_event_sequence_ws_bytes.restype = ctypes.c_size_t

@@ -1,6 +1,8 @@
 // extern "C" entry points, part 10: the YOLOX head's tail — box decode, batched on-device SimOTA
 // assignment and the detection losses with their gradient (simota.hpp; reference models/detection/yolox/models/yolo_head.py),
-// and the detection post-processing that follows the eval-mode decode (nms.hpp; reference models/detection/yolox/utils/boxes.py).
+// the detection post-processing that follows the eval-mode decode (nms.hpp; reference models/detection/yolox/utils/boxes.py), and the
+// two fused: head maps in, padded detections out (rvt_yolox_detect).  Decode and NMS share this translation unit and its flags, so
+// expf, the divide and the multiplies of the fused kernel are the instructions of the two kernels it replaces.
 #include "host.hpp"
 #include "simota.hpp"
 #include "nms.hpp"
@@ -138,6 +140,36 @@ int rvt_yolox_postprocess(const float* pred, int B, int A, int num_classes, floa
     hipLaunchKernelGGL(yolox_postprocess_kernel, dim3(B), dim3(NMS_THREADS), 0, (hipStream_t)stream, pred, A, num_classes, conf_thre,
                        nms_thre, class_agnostic != 0 ? 1 : 0, max_det, det, count, anchor_idx, w);
     return check_launch("yolox_postprocess");
+}
+
+size_t rvt_yolox_detect_ws_bytes(int B, int A, int num_classes) { return rvt_yolox_postprocess_ws_bytes(B, A, num_classes); }
+
+int rvt_yolox_detect(const void* const* reg_obj, const void* const* cls, int ld_ro, int ld_cls, int dtype, const int* level_hw,
+                     const int* level_stride, int L, int B, int A, int num_classes, float conf_thre, float nms_thre, int class_agnostic,
+                     int max_det, float* det, int* count, int* anchor_idx, void* ws, size_t ws_bytes, void* stream) {
+    RVT_CHECK(L >= 1 && L <= 8, "yolox_detect: %d levels outside the supported range 1..8", L);
+    RVT_CHECK(A >= 1 && A <= NMS_MAX_A, "yolox_detect: A=%d anchors outside the supported range 1..%d", A, NMS_MAX_A);
+    RVT_CHECK(num_classes >= 1 && num_classes <= NMS_MAX_NC, "yolox_detect: num_classes=%d outside the supported range 1..%d", num_classes,
+              NMS_MAX_NC);
+    RVT_CHECK(B >= 1 && B <= 65535 && max_det >= 1 && max_det <= (1 << 24), "yolox_detect: B=%d max_det=%d out of range", B, max_det);
+    RVT_CHECK(reg_obj && cls && level_hw && level_stride && det && count && ws, "yolox_detect: null argument");
+    RVT_CHECK(ld_ro >= 5 && ld_cls >= num_classes, "yolox_detect: reg_obj needs >= 5 columns, cls >= %d", num_classes);
+    YoloLevels lv;
+    RVT_CHECK(fill_levels(lv, level_hw, level_stride, L, A), "yolox_detect: the %d levels do not add up to A=%d anchors", L, A);
+    DetectMaps m;
+    for (int l = 0; l < 8; l++) {
+        m.ro[l] = l < L ? reg_obj[l] : nullptr;
+        m.cl[l] = l < L ? cls[l] : nullptr;
+        RVT_CHECK(l >= L || (m.ro[l] && m.cl[l]), "yolox_detect: level %d has a null map", l);
+    }
+    m.ld_ro = ld_ro;
+    m.ld_cls = ld_cls;
+    NmsWs w;
+    const size_t need = carve_nms((char*)ws, B, A, w);
+    RVT_CHECK(ws_bytes >= need, "yolox_detect: workspace %zu < %zu bytes", ws_bytes, need);
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((yolox_detect_kernel<T>), dim3(B), dim3(NMS_THREADS), 0, (hipStream_t)stream, m, lv, A, num_classes,
+                                             conf_thre, nms_thre, class_agnostic != 0 ? 1 : 0, max_det, det, count, anchor_idx, w));
+    return check_launch("yolox_detect");
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 // compiled with -ffp-contract=off, so every keep / kill decision is the one the same formula gives in torch, bit for bit.
 #pragma once
 #include "common.hpp"
+#include "simota.hpp"    // YoloLevels, sigmoid_exact: the decode kernel's own expressions
 
 namespace rvt {
 
@@ -62,12 +63,89 @@ __device__ __forceinline__ bool nms_suppresses(float ax1, float ay1, float ax2, 
     return uni > 0.f && inter / uni > thr;
 }
 
-// pred [B][A][5+nc] (cx cy w h obj cls...) -> det [B][max_det][7] (x1 y1 x2 y2 obj class_conf class_pred), count [B] (kept, before
+// Where one image's anchors come from.  A source gives, for anchor a in [0, A):
+//   score(a, bc):  obj * max class score (one fp32 multiply) and the class that holds the max (lowest index on an exact tie);
+//   fetch(a, c, ...): the decoded box cx cy w h, the objectness score and the score of class c.
+// NmsPredSrc: rows of the decoded fp32 tensor [A][5+nc] (rvt_yolox_decode's pred_infer): everything is a copy.
+struct NmsPredSrc {
+    const float* p;
+    int nc;
+    __device__ __forceinline__ float score(int a, int& bc) const {
+        const float* r = p + (size_t)a * (5 + nc);
+        float best = r[5];
+        bc = 0;
+        for (int c = 1; c < nc; c++) {
+            const float v = r[5 + c];
+            if (v > best) { best = v; bc = c; }                       // the lowest class index wins an exact tie
+        }
+        return r[4] * best;
+    }
+    __device__ __forceinline__ void fetch(int a, int c, float& cx, float& cy, float& bw, float& bh, float& obj, float& conf) const {
+        const float* r = p + (size_t)a * (5 + nc);
+        cx = r[0]; cy = r[1]; bw = r[2]; bh = r[3];
+        obj = r[4];
+        conf = r[5 + c];
+    }
+};
+
+// NmsMapSrc: the head's per-level prediction maps themselves (reg_obj [B*H*W][ld_ro], cls [B*H*W][ld_cls], as yolox_decode_kernel
+// reads them), decoded on the fly with that kernel's expressions in its operation order: the scores for every anchor, the box only
+// for the anchors that became candidates.  The class max runs over the SIGMOID values (two logits may round to one sigmoid; the lower
+// class must still win), so score / class / box are the bits the decoded tensor would hold.
+struct DetectMaps {
+    const void *ro[8], *cl[8];
+    int ld_ro, ld_cls;
+};
+template <class T>
+struct NmsMapSrc {
+    const DetectMaps& m;
+    const YoloLevels& lv;
+    int b, nc;
+    // level of anchor a by a chain of selects over the (uniform) level table: no dynamically indexed kernel argument
+    __device__ __forceinline__ void locate(int a, const T*& rr, const T*& cc, float& gx, float& gy, float& st) const {
+        int a0 = 0, W = lv.w[0], hw = lv.h[0] * lv.w[0], s = lv.stride[0];
+        const T *ro = (const T*)m.ro[0], *cl = (const T*)m.cl[0];
+#pragma unroll
+        for (int i = 1; i < 8; i++)
+            if (i < lv.n && a >= lv.a0[i]) {
+                a0 = lv.a0[i]; W = lv.w[i]; hw = lv.h[i] * lv.w[i]; s = lv.stride[i];
+                ro = (const T*)m.ro[i]; cl = (const T*)m.cl[i];
+            }
+        const int q = a - a0;                                          // in [0, hw): the levels add up to A (checked by the host)
+        const size_t row = (size_t)b * hw + q;
+        rr = ro + row * m.ld_ro;
+        cc = cl + row * m.ld_cls;
+        gx = (float)(q % W); gy = (float)(q / W); st = (float)s;
+    }
+    __device__ __forceinline__ float score(int a, int& bc) const {
+        const T *rr, *cc;
+        float gx, gy, st;
+        locate(a, rr, cc, gx, gy, st);
+        float best = sigmoid_exact((float)cc[0]);
+        bc = 0;
+        for (int c = 1; c < nc; c++) {
+            const float v = sigmoid_exact((float)cc[c]);
+            if (v > best) { best = v; bc = c; }
+        }
+        return sigmoid_exact((float)rr[4]) * best;
+    }
+    __device__ __forceinline__ void fetch(int a, int c, float& cx, float& cy, float& bw, float& bh, float& obj, float& conf) const {
+        const T *rr, *cc;
+        float gx, gy, st;
+        locate(a, rr, cc, gx, gy, st);
+        cx = ((float)rr[0] + gx) * st; cy = ((float)rr[1] + gy) * st;
+        bw = expf((float)rr[2]) * st; bh = expf((float)rr[3]) * st;
+        obj = sigmoid_exact((float)rr[4]);
+        conf = sigmoid_exact((float)cc[c]);
+    }
+};
+
+// One image (blockIdx.x) of `src` -> det [B][max_det][7] (x1 y1 x2 y2 obj class_conf class_pred), count [B] (kept, before
 // the max_det cap), anchor_idx [B][max_det] (nullptr = skip).  Rows past min(count, max_det) are zero / -1.
 // Every index is an integer derived from A and the compaction counter, never from a float: any input bits terminate in bounds.
-__global__ void __launch_bounds__(NMS_THREADS)
-yolox_postprocess_kernel(const float* __restrict__ pred, int A, int nc, float conf_thre, float nms_thre, int agnostic, int max_det,
-                         float* __restrict__ det, int* __restrict__ count, int* __restrict__ anchor_idx, NmsWs w) {
+template <class Src>
+__device__ __forceinline__ void nms_image(const Src& src, int A, float conf_thre, float nms_thre, int agnostic, int max_det,
+                                          float* __restrict__ det, int* __restrict__ count, int* __restrict__ anchor_idx, const NmsWs& w) {
     __shared__ unsigned long long skey[NMS_CHUNK];
     __shared__ float kx1[64], ky1[64], kx2[64], ky2[64], karea[64];
     __shared__ int kcls[64];
@@ -75,9 +153,8 @@ yolox_postprocess_kernel(const float* __restrict__ pred, int A, int nc, float co
     __shared__ unsigned long long s_mask;
     __shared__ int s_n, s_total;
     constexpr int T = NMS_THREADS;
-    const int b = blockIdx.x, tid = threadIdx.x, NO = 5 + nc;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const size_t img = (size_t)b * A;
-    const float* p = pred + img * NO;
     unsigned long long* keys = w.keys + img;
     unsigned long long* sorted = w.sorted + img;
     float *bx1 = w.x1 + img, *by1 = w.y1 + img, *bx2 = w.x2 + img, *by2 = w.y2 + img, *barea = w.area + img;
@@ -88,15 +165,9 @@ yolox_postprocess_kernel(const float* __restrict__ pred, int A, int nc, float co
     if (tid == 0) s_n = 0;
     __syncthreads();
     for (int a = tid; a < A; a += T) {
-        const float* r = p + (size_t)a * NO;
-        float best = r[5];
-        int bc = 0;
-        for (int c = 1; c < nc; c++) {
-            const float v = r[5 + c];
-            if (v > best) { best = v; bc = c; }                       // the lowest class index wins an exact tie
-        }
+        int bc;
+        const float score = src.score(a, bc);
         acls[a] = bc;
-        const float score = r[4] * best;
         if (score >= conf_thre) {
             const int slot = atomicAdd(&s_n, 1);                      // < A: one increment per anchor at most
             keys[slot] = ((unsigned long long)nms_score_key(score) << 32) | (unsigned)~a;
@@ -153,15 +224,16 @@ yolox_postprocess_kernel(const float* __restrict__ pred, int A, int nc, float co
     for (int j = tid; j < n; j += T) {
         int a = (int)~(unsigned)order[j];
         a = a < 0 ? 0 : (a < A ? a : A - 1);
-        const float* r = p + (size_t)a * NO;
-        const float cx = r[0], cy = r[1], hw = r[2] / 2, hh = r[3] / 2;
-        const float x1 = cx - hw, y1 = cy - hh, x2 = cx + hw, y2 = cy + hh;
         const int c = acls[a];
+        float cx, cy, bw, bh, obj, conf;
+        src.fetch(a, c, cx, cy, bw, bh, obj, conf);
+        const float hw = bw / 2, hh = bh / 2;
+        const float x1 = cx - hw, y1 = cy - hh, x2 = cx + hw, y2 = cy + hh;
         bx1[j] = x1; by1[j] = y1; bx2[j] = x2; by2[j] = y2;
         barea[j] = (x2 - x1) * (y2 - y1);
         bcls[j] = c;
-        bobj[j] = r[4];
-        bconf[j] = r[5 + c];
+        bobj[j] = obj;
+        bconf[j] = conf;
         dead[j] = 0;
     }
     __syncthreads();
@@ -262,6 +334,23 @@ yolox_postprocess_kernel(const float* __restrict__ pred, int A, int nc, float co
     for (int i = tid; i < (max_det - first) * 7; i += T) dz[i] = 0.f;
     if (anchor_idx != nullptr)
         for (int i = first + tid; i < max_det; i += T) anchor_idx[(size_t)b * max_det + i] = -1;
+}
+
+// pred [B][A][5+nc] (cx cy w h obj cls...), the decoded tensor
+__global__ void __launch_bounds__(NMS_THREADS)
+yolox_postprocess_kernel(const float* __restrict__ pred, int A, int nc, float conf_thre, float nms_thre, int agnostic, int max_det,
+                         float* __restrict__ det, int* __restrict__ count, int* __restrict__ anchor_idx, NmsWs w) {
+    const NmsPredSrc src{pred + (size_t)blockIdx.x * A * (5 + nc), nc};
+    nms_image(src, A, conf_thre, nms_thre, agnostic, max_det, det, count, anchor_idx, w);
+}
+
+// the head's prediction maps: decode + score filter + NMS in one launch (rvt_yolox_detect)
+template <class T>
+__global__ void __launch_bounds__(NMS_THREADS)
+yolox_detect_kernel(DetectMaps m, YoloLevels lv, int A, int nc, float conf_thre, float nms_thre, int agnostic, int max_det,
+                    float* __restrict__ det, int* __restrict__ count, int* __restrict__ anchor_idx, NmsWs w) {
+    const NmsMapSrc<T> src{m, lv, (int)blockIdx.x, nc};
+    nms_image(src, A, conf_thre, nms_thre, agnostic, max_det, det, count, anchor_idx, w);
 }
 
 }  // namespace rvt

@@ -11,6 +11,9 @@ is how the reference trains (fixed sequence length and batch size, config/experi
 
     step = GraphedStep(lambda: train_step(static_batch))     # warm-up runs + capture
     static_batch.copy_(next_batch); step()                   # replay
+
+Inference has two captured forms of the streaming step (T = 1, recurrent state carried on the device): GraphedStreamStep replays the
+backbone, GraphedDetectorStream the whole detector - frame in, kept boxes out.
 """
 from __future__ import annotations
 
@@ -112,3 +115,76 @@ class GraphedStreamStep:
     def close(self) -> None:
         self.graph = None
         self.feats = None
+
+
+class GraphedDetectorStream:
+    """One streaming DETECTION step of an eval-mode rvt_amd.YoloXDetector - masked state reset, backbone (T = 1), PAFPN, the head's
+    prediction maps, decode + score filter + NMS (rvt_yolox_detect), state carry - as ONE hipGraph launch with no host
+    synchronisation: frame in, the kept boxes out.
+
+        stream = GraphedDetectorStream(detector, example_frame, conf_thre=0.1, nms_thre=0.45)    # eager warm-up + capture
+        det, count, anchor_idx = stream(frame)            # copies `frame` into stream.frame_buffer, replays
+        builder.build_from_table(table, out=...)          # or: a producer writes stream.frame_buffer in place ...
+        det, count, anchor_idx = stream()                 # ... and the step replays on it: no frame copy at all
+        stream.reset_mask.copy_(is_first)                 # new sequences: uint8 (B,), applied by the NEXT step on the device
+        stream.reset()                                    # every state back to zeros
+
+    `frame_buffer` is the graph's static input, `reset_mask` a static uint8 (B,) device tensor: the captured step zeroes the state rows of
+    the samples whose byte is set (rvt_state_reset_masked on every state tensor) before the backbone reads them and clears the mask at
+    its end, so marking a sequence boundary is a device-side copy - no boolean index_put, no host synchronisation.  The three tensors
+    returned are the graph's own buffers: valid until the next call (clone what has to outlive it).  The parameters must not change
+    while the graph lives (inference); call close() before training the detector again."""
+
+    def __init__(self, detector, example_frame: torch.Tensor, conf_thre: float, nms_thre: float, class_agnostic: bool = False,
+                 max_det: Optional[int] = None, warmup: int = 3):
+        from . import ops
+        assert example_frame.is_cuda and not detector.training, 'GraphedDetectorStream: an eval-mode detector and a CUDA frame (B, C, h, w)'
+        self.detector = detector
+        self.frame_buffer = torch.empty_like(example_frame)
+        self.frame_buffer.copy_(example_frame)
+        dev = example_frame.device
+        self.reset_mask = torch.zeros(example_frame.shape[0], dtype=torch.uint8, device=dev)
+        args = (float(conf_thre), float(nms_thre), bool(class_agnostic), max_det)
+        with torch.no_grad():
+            st = None
+            for _ in range(max(2, warmup)):                     # eager warm-up: weight packs, workspaces, occupancy caches
+                dets, st = detector.detect(self.frame_buffer, st, *args)
+            self.out = tuple(torch.empty_like(t) for t in dets)  # the graph's own outputs, not the per-shape cache other callers share
+            # static state buffers (same shapes / strides as the states the detector hands back)
+            self.states = [tuple(t.clone(memory_format=torch.preserve_format) for t in pair) for pair in st]
+            self.reset()
+            torch.cuda.synchronize(dev)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                for pair in self.states:
+                    for t in pair:                              # (B, C, H, W)-shaped views of channels-last storage
+                        ops.state_reset_masked(t.permute(0, 2, 3, 1) if not t.is_contiguous() else t, self.reset_mask)
+                _, new = detector.detect(self.frame_buffer, self.states, *args, out=self.out)
+                for (h, c), (hn, cn) in zip(self.states, new):
+                    h.copy_(hn)
+                    c.copy_(cn)
+                self.reset_mask.zero_()
+        self.reset()
+
+    def reset(self) -> None:
+        """Zero the recurrent state of every sample (and forget pending reset marks)."""
+        for h, c in self.states:
+            h.zero_()
+            c.zero_()
+        self.reset_mask.zero_()
+
+    def __call__(self, frame: Optional[torch.Tensor] = None):
+        if self.graph is None:
+            raise RuntimeError('GraphedDetectorStream: the stream was closed (close() dropped its graph); build a new one')
+        if frame is not None:
+            fb = self.frame_buffer
+            if tuple(frame.shape) != tuple(fb.shape) or frame.dtype != fb.dtype:
+                raise ValueError(f'GraphedDetectorStream: frame must be {fb.dtype} {tuple(fb.shape)} like frame_buffer, '
+                                 f'got {frame.dtype} {tuple(frame.shape)}')
+            fb.copy_(frame)
+        self.graph.replay()
+        return self.out
+
+    def close(self) -> None:
+        self.graph = None
+        self.out = None

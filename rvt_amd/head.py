@@ -242,6 +242,19 @@ class YOLOXHead(nn.Module):
         losses = {'loss': ls[0], 'iou_loss': ls[1], 'conf_loss': ls[2], 'cls_loss': ls[3], 'l1_loss': 0.0, 'num_fg': ls[4].detach()}
         return outputs, losses
 
+    @torch.no_grad()
+    def detect_padded(self, xin: Sequence[Tensor], conf_thre: float, nms_thre: float, class_agnostic: bool = False,
+                      max_det: Optional[int] = None, out=None):
+        """Eval mode: the FPN maps -> (det [B][max_det][7], count [B], anchor_idx [B][max_det]) with no host synchronisation: the
+        prediction GEMMs, then decode + score filter + NMS as ONE launch (rvt_amd.postprocess.detect_padded).  Bit-identical to
+        postprocess_padded(self(xin)[0], ...) without the [B][A][5 + nc] tensor between them; outputs and workspace are cached per
+        shape, so from the second call on nothing is allocated by the tail."""
+        assert not self.training, 'detect_padded is the inference tail: call .eval() first'
+        from .postprocess import detect_padded
+        maps, hws = self._pred_maps(xin)
+        self.hw = hws
+        return detect_padded(maps, hws, self.strides, self.num_classes, conf_thre, nms_thre, class_agnostic, max_det, out)
+
 
 def build_yolox_head(head_cfg, in_channels: Tuple[int, ...], strides: Tuple[int, ...], compute_dtype: torch.dtype = torch.float32) -> YOLOXHead:
     """Registry entry point (reference yolox_extension/models/build.py:9-18)."""

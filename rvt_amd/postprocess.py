@@ -12,6 +12,10 @@ eval-mode output runs first (modules/detection.py:175-178, :261-264): rows with 
     and the call can be captured in a torch.cuda.graph.  Rows from min(count, max_det) on are zero, their anchor_idx -1;
     count is the number kept BEFORE the max_det cap.
 
+  * `detect_padded(maps, hws, strides, num_classes, ...)`: the same three tensors straight from the head's per-level prediction maps
+    (rvt_yolox_detect: decode + score filter + NMS in ONE launch, the [B][A][5 + nc] tensor never written), bit-identical to
+    `postprocess_padded(decode(maps, ...))`.  YOLOXHead.detect_padded and YoloXDetector.detect end in it.
+
 Differences to the reference a caller can see: the input is NOT overwritten with corner boxes (the reference mutates
 prediction[:, :, :4] in place); non-fp32 or non-contiguous input is converted first; exact score ties are ordered by anchor
 index and exact class ties go to the lower class (the reference leaves both to the sort / max implementation).  There is no
@@ -19,7 +23,8 @@ PyTorch fallback: a missing kernel or an unsupported shape raises with the libra
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+import ctypes
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -66,6 +71,61 @@ def postprocess_padded(prediction: Tensor, num_classes: int, conf_thre: float, n
                 raise ValueError(f'out tensor must be {dt} {shp} on {pred.device}, got {t.dtype} {tuple(t.shape)} on {t.device}')
     L.call('rvt_yolox_postprocess', L.ptr(pred), B, A, num_classes, float(conf_thre), float(nms_thre), int(bool(class_agnostic)),
            max_det, L.ptr(det), L.ptr(count), L.ptr(aidx), L.ptr(ws), ws.numel(), L.stream_of(pred))
+    return det, count, aidx
+
+
+_detect_cache: Dict[tuple, tuple] = {}
+
+
+def _check_out(out, B: int, max_det: int, dev: torch.device):
+    det, count, aidx = out
+    for t, shp, dt in ((det, (B, max_det, 7), torch.float32), (count, (B,), torch.int32), (aidx, (B, max_det), torch.int32)):
+        if tuple(t.shape) != shp or t.dtype != dt or t.device != dev:
+            raise ValueError(f'out tensor must be {dt} {shp} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    return det, count, aidx
+
+
+def detect_padded(maps: Sequence[Tensor], hws, strides, num_classes: int, conf_thre: float, nms_thre: float,
+                  class_agnostic: bool = False, max_det: Optional[int] = None, out: Optional[Tuple[Tensor, Tensor, Tensor]] = None):
+    """The head's prediction maps -> (det, count, anchor_idx) in ONE launch, no host synchronisation (rvt_yolox_detect).
+
+    maps: [reg_obj_0, cls_0, reg_obj_1, cls_1, ...] as YOLOXHead._pred_maps returns them, (B, H, W, ld) of one dtype (fp32 or bf16)
+    with one ld_ro >= 5 and one ld_cls >= num_classes for all levels; hws[l] = (H, W), strides[l] the level's stride.  Everything
+    else as postprocess_padded: max_det defaults to A, `out` or the tensors cached for this shape (overwritten by the next call of
+    the same shape), workspace cached per shape and device.  Equal to postprocess_padded(decode(maps, ...)) bit for bit."""
+    hws, strides = tuple((int(h), int(w)) for h, w in hws), tuple(int(s) for s in strides)
+    nl = len(hws)
+    if len(maps) != 2 * nl or len(strides) != nl or nl == 0:
+        raise ValueError(f'{len(maps)} maps, {nl} level shapes and {len(strides)} strides do not describe the same levels')
+    maps = [m.detach().contiguous() for m in maps]
+    ro0, cl0 = maps[0], maps[1]
+    B, dev = ro0.shape[0], ro0.device
+    if B == 0:
+        raise ValueError('the maps hold no image')
+    for l in range(nl):
+        ro, cl = maps[2 * l], maps[2 * l + 1]
+        if ro.dtype != ro0.dtype or cl.dtype != ro0.dtype or ro.shape[-1] != ro0.shape[-1] or cl.shape[-1] != cl0.shape[-1]:
+            raise ValueError('the maps of all levels must share one dtype and one row length each')
+        if ro.numel() != B * hws[l][0] * hws[l][1] * ro.shape[-1] or cl.numel() != B * hws[l][0] * hws[l][1] * cl.shape[-1]:
+            raise ValueError(f'level {l}: maps {tuple(ro.shape)} / {tuple(cl.shape)} are not B = {B} images of {hws[l]}')
+    A = sum(h * w for h, w in hws)
+    max_det = A if max_det is None else int(max_det)
+    key = (B, hws, strides, num_classes, max_det, dev.type, dev.index)
+    hit = _detect_cache.get(key)
+    if hit is None:
+        ws_bytes = int(L.get_lib().rvt_yolox_detect_ws_bytes(B, A, num_classes)) if nl <= 8 else 0
+        hit = (torch.empty(B, max_det, 7, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, max_det, dtype=torch.int32, device=dev), torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev),
+               (ctypes.c_int * (2 * nl))(*[v for hw in hws for v in hw]), (ctypes.c_int * nl)(*strides))
+        _detect_cache[key] = hit
+    det, count, aidx, ws, hw_arr, st_arr = hit
+    if out is not None:
+        det, count, aidx = _check_out(out, B, max_det, dev)
+    ro_arr = (ctypes.c_void_p * nl)(*[L.ptr(maps[2 * l]) for l in range(nl)])
+    cl_arr = (ctypes.c_void_p * nl)(*[L.ptr(maps[2 * l + 1]) for l in range(nl)])
+    L.call('rvt_yolox_detect', ro_arr, cl_arr, ro0.shape[-1], cl0.shape[-1], L.dtype_code(ro0.dtype), hw_arr, st_arr, nl, B, A, num_classes,
+           float(conf_thre), float(nms_thre), int(bool(class_agnostic)), max_det, L.ptr(det), L.ptr(count), L.ptr(aidx), L.ptr(ws),
+           ws.numel(), L.stream_of(ro0))
     return det, count, aidx
 
 
