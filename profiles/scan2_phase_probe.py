@@ -2,7 +2,7 @@
 wave 0 of workgroup 0 spends in each phase of a step, averaged over its steps."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from rvt_amd import ops
+from rvt_amd import _lib, ops
 dev, dt = torch.device('cuda', 0), torch.bfloat16
 T_, Mp, Cc = 21, 368640, 64
 rnd = lambda *s: torch.randn(*s, device=dev).to(dt)
@@ -18,7 +18,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-ws = ops._WS[('scanbwd', 'cuda', 0, int(torch.cuda.current_stream().cuda_stream))]
+ws = _lib._WS[('scanbwd', 'cuda', 0, int(torch.cuda.current_stream().cuda_stream))]
 grid = 256
 rec = 4 * Cc * 2 * Cc + 4 * Cc
 t = ws[grid * rec: grid * rec + 8].cpu().tolist()

@@ -1,4 +1,5 @@
-"""ctypes binding of librvt_hip.so (include/rvt_hip.h) — the only compute path of this package.
+"""ctypes binding of librvt_hip.so — the only compute path of this package.  Every type in it is derived from
+include/rvt_hip.h (rvt_amd/_header.py); nothing here restates a prototype or a struct.
 
 There is no PyTorch / CPU fallback: if the gfx950 library or a GPU is missing, every op raises.
 The unit tests may install the CPU SIMT-emulator build of the same kernel sources through
@@ -12,6 +13,8 @@ from typing import Optional
 
 import torch
 
+from ._header import SIGS as _SIGS, bind as _bind        # name -> argument types; types onto a loaded library
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RVT_HIP_LIB') or os.path.join(_HERE, 'librvt_hip.so')   # env: another BUILD of the same library
 
@@ -21,156 +24,7 @@ _DT = {torch.float32: RVT_F32, torch.bfloat16: RVT_BF16}
 _lib: Optional[ctypes.CDLL] = None
 _is_emu = False
 
-_vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-_SIGS = {
-    'rvt_stacked_histogram': [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    'rvt_prepack_input': [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_conv_fwd': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_conv_dgrad4': [_vp] * 4 + [_i] * 6 + [_vp],
-    'rvt_conv_dgrad': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_conv_wgrad': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_stem_fwd': [_vp] * 6 + [_i] * 8 + [_f, _vp],
-    'rvt_stem_wgrad': [_vp] * 4 + [_i] * 8 + [_vp],
-    'rvt_layernorm_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    'rvt_layernorm_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    'rvt_linear_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    'rvt_linear_scale_res_fwd': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    'rvt_linear_dgrad': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    'rvt_linear_dgrad_ln': [_vp] * 8 + [_i, _i, _i, _i, _f, _vp],
-    'rvt_linear_dgrad_preln': [_vp] * 8 + [_i, _i, _i, _i, _f, _vp],
-    'rvt_ln_linear_fwd': [_vp] * 7 + [_i, _i, _i, _i, _f, _vp],
-    'rvt_linear_gelu_fwd': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    'rvt_linear_wgrad': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    'rvt_mlp_fwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    'rvt_mlp_bwd_dgrad': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    'rvt_attn_fwd': [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_attn_bwd': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_attn_block_fwd': [_vp] * 10 + [_i] * 9 + [_f, _vp],
-    'rvt_attn_block_bwd': [_vp] * 12 + [_i] * 9 + [_f, _vp],
-    'rvt_attn_block_bwd_preln': [_vp] * 11 + [_i] * 9 + [_f, _vp],
-    'rvt_lstm_fwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    'rvt_lstm_gates_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    'rvt_lstm_dgrad': [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    'rvt_lstm_wgrad': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    'rvt_dwconv_fwd': [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_dwconv_wgrad': [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    'rvt_token_mask_fwd': [_vp, _vp, _vp, _i, _i, _i, _vp],
-    'rvt_token_mask_bwd': [_vp, _vp, _vp, _i, _i, _i, _vp],
-    'rvt_state_reset_masked': [_vp, _vp, _i, _i, _sz, _vp],
-    'rvt_gather_frames': [_vp, _vp, _vp, _i, _sz, _i, _vp],
-    'rvt_pack_table': [_vp, _i, _i, _i, _vp],
-    'rvt_mlp_bwd_recompute_dgrad': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    'rvt_mlp_bwd_recompute_wgrad': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    'rvt_mlp_bwd_recompute_both': [_vp] * 16 + [_i, _i, _i, _f, _vp],
-    'rvt_lstm_scan_fwd': [_vp] * 8 + [_i, _i, _i, _i, _vp],
-    'rvt_lstm_scan_bwd': [_vp] * 17 + [_i, _i, _i, _i, _vp],
-    'rvt_lstm_scan3_pack': [_vp, _vp, _vp, _i, _vp],
-    'rvt_lstm_scan3_fwd': [_vp] * 8 + [_i, _i, _i, _i, _i, _vp],
-    'rvt_lstm_scan3_bwd': [_vp] * 10 + [_i, _i, _i, _i, _i, _vp],
-    'rvt_stage_routes': [_vp, _i, _i, _i, _i, _i, _vp],
-    'rvt_stage_seq_fwd': [_vp] * 7 + [_sz, _i, _i, _vp],
-    'rvt_stage_seq_train_fwd': [_vp, _vp, _vp, _vp, _i, _i, _vp],
-    'rvt_stage_seq_bwd': [_vp] * 10 + [_sz, _i, _i, _vp],
-    'rvt_layerscale_grad_table': [_vp, _i, _i, _vp],
-    'rvt_bn_stats': [_vp, _vp, _i, _i, _i, _vp],
-    'rvt_bn_finalize': [_vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    'rvt_bn_act_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    'rvt_bn_train_act_fwd': [_vp, _vp, _i, _vp, _vp, _f, _f] + [_vp] * 7 + [_i, _i, _i, _i, _vp],
-    'rvt_bn_act_bwd_stats': [_vp] * 8 + [_i, _i, _i, _i, _vp],
-    'rvt_bn_act_bwd_apply': [_vp] * 9 + [_i, _i, _i, _i, _vp],
-    'rvt_conv_bn_act_fwd': [_vp] * 5 + [_i] * 10 + [_vp],
-    'rvt_yolox_decode': [_vp, _vp] + [_i] * 10 + [_vp, _vp, _vp],
-    'rvt_yolox_decode_bwd': [_vp] * 5 + [_i] * 10 + [_vp],
-    'rvt_simota_loss': [_vp] * 4 + [_i] * 5 + [_vp] * 5 + [ctypes.c_size_t, _vp],
-    'rvt_yolox_postprocess': [_vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
-    'rvt_yolox_detect': [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
-    'rvt_augment_planes': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    'rvt_augment_labels': [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    'rvt_coco_match': [_vp] * 5 + [_i] * 5 + [_f, _f] + [_vp] * 4 + [_i, _vp, _vp],
-    'rvt_coco_accumulate': [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _sz, _vp],
-    'rvt_optim_step': [_vp, _i, _vp, _i, _vp, _i, _vp],
-    'rvt_event_sequence': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong] + [_i] * 6 + [_vp, _vp, _i, _i, _vp, _vp],
-    'rvt_mixed_density_stack': [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp],
-    'rvt_event_sequence_mixed': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp],
-}
-EXPORTS = sorted(list(_SIGS) + ['rvt_last_error', 'rvt_is_emulator', 'rvt_wgrad_workspace_floats',
-                               'rvt_mlp_fused_supported', 'rvt_lstm_scan_supported', 'rvt_mlp_bwd_fused_supported',
-                               'rvt_mlp_bwd_fused_ws_floats', 'rvt_attn_block_supported', 'rvt_lstm_scan_bwd_ws_floats',
-                               'rvt_lstm_scan_saves_gates', 'rvt_stem_supported', 'rvt_stem_wgrad_ws_floats', 'rvt_conv_dgrad4_supported',
-                               'rvt_linear_dgrad_ln_supported', 'rvt_ln_linear_supported', 'rvt_tuning_defaults', 'rvt_get_tuning', 'rvt_set_tuning', 'rvt_probe_mfma',
-                               'rvt_stage_seq_fwd_ws_bytes', 'rvt_lstm_scan3_supported', 'rvt_lstm_scan3_rows', 'rvt_lstm_scan3_rb', 'rvt_stage_seq_bwd_ws_bytes', 'rvt_simota_ws_bytes', 'rvt_mlp_bwd_both_supported',
-                               'rvt_yolox_postprocess_ws_bytes', 'rvt_coco_accumulate_ws_bytes', 'rvt_event_sequence_ws_bytes',
-                               'rvt_event_sequence_mixed_ws_bytes', 'rvt_yolox_detect_ws_bytes'])
-
-
-def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
-    for name, argtypes in _SIGS.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is missing -> loud
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
-    lib.rvt_last_error.restype = ctypes.c_char_p
-    lib.rvt_last_error.argtypes = []
-    lib.rvt_is_emulator.restype = ctypes.c_int
-    lib.rvt_is_emulator.argtypes = []
-    lib.rvt_mlp_fused_supported.restype = ctypes.c_int
-    lib.rvt_mlp_fused_supported.argtypes = [_i, _i]
-    lib.rvt_mlp_bwd_fused_supported.restype = ctypes.c_int
-    lib.rvt_mlp_bwd_fused_supported.argtypes = [_i, _i]
-    lib.rvt_mlp_bwd_both_supported.restype = ctypes.c_int
-    lib.rvt_mlp_bwd_both_supported.argtypes = [_i, _i]
-    lib.rvt_mlp_bwd_fused_ws_floats.restype = ctypes.c_size_t
-    lib.rvt_mlp_bwd_fused_ws_floats.argtypes = [_i, _i, _i]
-    lib.rvt_lstm_scan_bwd_ws_floats.restype = ctypes.c_size_t
-    lib.rvt_lstm_scan_bwd_ws_floats.argtypes = [_i, _i, _i]
-    lib.rvt_lstm_scan_saves_gates.restype = ctypes.c_int
-    lib.rvt_lstm_scan_saves_gates.argtypes = [_i, _i]
-    lib.rvt_attn_block_supported.restype = ctypes.c_int
-    lib.rvt_attn_block_supported.argtypes = [_i, _i, _i, _i]
-    lib.rvt_lstm_scan_supported.restype = ctypes.c_int
-    lib.rvt_lstm_scan_supported.argtypes = [_i, _i]
-    lib.rvt_lstm_scan3_supported.restype = ctypes.c_int
-    lib.rvt_lstm_scan3_supported.argtypes = [_i, _i]
-    lib.rvt_lstm_scan3_rows.restype = ctypes.c_int
-    lib.rvt_lstm_scan3_rows.argtypes = [_i, _i, _i]
-    lib.rvt_lstm_scan3_rb.restype = ctypes.c_int
-    lib.rvt_lstm_scan3_rb.argtypes = [_i]
-    lib.rvt_stage_seq_fwd_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_stage_seq_fwd_ws_bytes.argtypes = [_vp, _i, _i]
-    lib.rvt_stage_seq_bwd_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_stage_seq_bwd_ws_bytes.argtypes = [_vp, _vp, _i, _i]
-    lib.rvt_linear_dgrad_ln_supported.restype = ctypes.c_int
-    lib.rvt_linear_dgrad_ln_supported.argtypes = [_i, _i, _i]
-    lib.rvt_ln_linear_supported.restype = ctypes.c_int
-    lib.rvt_ln_linear_supported.argtypes = [_i, _i, _i]
-    lib.rvt_conv_dgrad4_supported.restype = ctypes.c_int
-    lib.rvt_conv_dgrad4_supported.argtypes = [_i] * 9
-    lib.rvt_stem_supported.restype = ctypes.c_int
-    lib.rvt_stem_supported.argtypes = [_i] * 8
-    lib.rvt_stem_wgrad_ws_floats.restype = ctypes.c_size_t
-    lib.rvt_stem_wgrad_ws_floats.argtypes = [_i] * 4
-    lib.rvt_wgrad_workspace_floats.restype = ctypes.c_size_t
-    lib.rvt_wgrad_workspace_floats.argtypes = [_i, _i, _i, _i, _i]
-    lib.rvt_simota_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_simota_ws_bytes.argtypes = [_i, _i, _i]
-    lib.rvt_yolox_postprocess_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_yolox_postprocess_ws_bytes.argtypes = [_i, _i, _i]
-    lib.rvt_yolox_detect_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_yolox_detect_ws_bytes.argtypes = [_i, _i, _i]
-    lib.rvt_coco_accumulate_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_coco_accumulate_ws_bytes.argtypes = [ctypes.c_longlong, _i]
-    lib.rvt_event_sequence_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_event_sequence_ws_bytes.argtypes = [_i] * 5
-    lib.rvt_event_sequence_mixed_ws_bytes.restype = ctypes.c_size_t
-    lib.rvt_event_sequence_mixed_ws_bytes.argtypes = [_i] * 5
-    lib.rvt_probe_mfma.restype = ctypes.c_double
-    lib.rvt_probe_mfma.argtypes = [_vp, _i, _i, _vp]
-    lib.rvt_tuning_defaults.restype = None
-    lib.rvt_tuning_defaults.argtypes = [_vp]
-    lib.rvt_get_tuning.restype = ctypes.c_int
-    lib.rvt_get_tuning.argtypes = [_vp]
-    lib.rvt_set_tuning.restype = ctypes.c_int
-    lib.rvt_set_tuning.argtypes = [_vp]
-    return lib
+EXPORTS = sorted(_SIGS)
 
 
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
@@ -254,4 +108,26 @@ def call(name: str, *args) -> None:
     else:
         rc = getattr(lib, name)(*args)
     if rc != 0:
-        raise RuntimeError(f'{name} failed: {lib.rvt_last_error().decode()}')
+        check(name, rc, lib)
+
+
+def check(name: str, rc: int, lib: Optional[ctypes.CDLL] = None) -> None:
+    """The one status check: a non-zero return of entry point `name` raises with the library's message.  For the calls that do not
+    go through call() (stage drivers, route planner, tuning record: bench.py and the launch-trace recorder price / record what call() sees)."""
+    if rc != 0:
+        raise RuntimeError(f'{name} failed: {(lib or get_lib()).rvt_last_error().decode()}')
+
+
+_WS = {}
+
+
+def workspace(kind: str, like: torch.Tensor, n: int, dtype: torch.dtype, floor: int = 0):
+    """(stream handle of `like`, the workspace of `kind` on that stream with at least n elements of `dtype`).  One buffer per
+    (kind, device, stream): kernels on one stream serialise, so consecutive launches of a kind share it, launches on different
+    streams never do.  Grow-only: a buffer that fits is never shrunk, dropped or replaced - captured graphs hold these addresses."""
+    st, dev = stream_of(like), like.device
+    key = (kind, dev.type, dev.index, 0 if st is None else int(st))
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _WS[key] = torch.empty(max(n, floor), dtype=dtype, device=dev)
+    return st, ws

@@ -1,4 +1,4 @@
-// extern "C" entry points, part 6 of 8: partition attention (attn.hpp, attn_core2.hpp) and the fused attention half (attn_block.hpp).
+// extern "C" entry points, part 6: partition attention (attn.hpp, attn_core2.hpp) and the fused attention half (attn_block.hpp).
 #include "host.hpp"
 #include "attn.hpp"
 #include "attn_block.hpp"

@@ -1,4 +1,4 @@
-// extern "C" entry points, part 2 of 8: down-sampling convolutions on the GEMM engines.
+// extern "C" entry points, part 2: down-sampling convolutions on the GEMM engines.
 #include "gemm_host.hpp"
 
 extern "C" {

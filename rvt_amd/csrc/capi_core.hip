@@ -1,4 +1,4 @@
-// extern "C" entry points of librvt_hip.so (declared in include/rvt_hip.h), part 1 of 8: error / tuning plumbing and the
+// extern "C" entry points of librvt_hip.so (declared in include/rvt_hip.h), part 1: error / tuning plumbing and the
 // row-wise operators.  Host-side only: argument checks, launch geometry.
 #include "host.hpp"
 #include "rowops.hpp"

@@ -1,4 +1,4 @@
-// extern "C" entry points, part 3 of 8: linear layers (forward / input gradient / weight gradient) on the GEMM engines.
+// extern "C" entry points, part 3: linear layers (forward / input gradient / weight gradient) on the GEMM engines.
 #include "gemm_host.hpp"
 #include "ln_linear.hpp"
 

@@ -1,4 +1,4 @@
-// extern "C" entry points, part 7 of 8: ConvLSTM cell, one launch per time step (GEMM engines).
+// extern "C" entry points, part 7: ConvLSTM cell, one launch per time step (GEMM engines).
 #include "gemm_host.hpp"
 #include "rowops.hpp"
 

@@ -1,4 +1,4 @@
-// extern "C" entry points, part 5 of 8: fused MLP halves (mlp.hpp, mlp_chain.hpp) and the LayerNorm-backward GEMM (dgrad_ln.hpp).
+// extern "C" entry points, part 5: fused MLP halves (mlp.hpp, mlp_chain.hpp) and the LayerNorm-backward GEMM (dgrad_ln.hpp).
 #include "host.hpp"
 #include "gemm.hpp"
 #include "dgrad_ln.hpp"

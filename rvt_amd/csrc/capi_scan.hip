@@ -1,4 +1,4 @@
-// extern "C" entry points, part 8 of 8: ConvLSTM with the time loop inside the kernel (lstm_scan.hpp).
+// extern "C" entry points, part 8: ConvLSTM with the time loop inside the kernel (lstm_scan.hpp).
 #include "host.hpp"
 #include "gemm.hpp"
 #include "lstm_scan.hpp"

@@ -1,4 +1,4 @@
-// extern "C" entry points, part 4 of 8: the stem on the loader's uint8 planes (stem.hpp).
+// extern "C" entry points, part 4: the stem on the loader's uint8 planes (stem.hpp).
 #include "host.hpp"
 #include "stem.hpp"
 

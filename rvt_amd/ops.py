@@ -18,20 +18,11 @@ def _out(like: Tensor, shape, dtype=None, out: Optional[Tensor] = None) -> Tenso
     return torch.empty(shape, dtype=dtype or like.dtype, device=like.device)
 
 
-_WS = {}
-
-
 def _wgrad_ws(like: Tensor, out_rows: int, out_cols: int, tokens: int, want_colsum: bool) -> Tensor:
     """Grow-only scratch for the two-stage split-K reduction, one per (device, stream): kernels on one stream serialise,
     so consecutive weight-gradient launches of that stream can share it; launches on different streams never do."""
     n = L.get_lib().rvt_wgrad_workspace_floats(L.dtype_code(like.dtype), out_rows, out_cols, tokens, int(want_colsum))
-    st = L.stream_of(like)
-    key = (like.device.type, like.device.index, 0 if st is None else int(st))
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(max(n, 1 << 20), dtype=torch.float32, device=like.device)
-        _WS[key] = ws
-    return ws
+    return L.workspace('wgrad', like, n, torch.float32, floor=1 << 20)[1]
 
 
 _PREPACK_KIND = {torch.float32: 0, torch.uint8: 1, torch.int8: 2}      # include/rvt_hip.h: src_kind
@@ -102,12 +93,7 @@ def stem_wgrad(src: Tensor, dy: Tensor, dw: Tensor, H: int, W: int) -> None:
     cp = dw.shape[1] // 49
     assert tuple(dw.shape) == (64, 49 * cp) and tuple(dy.shape[:1]) == (F_,) and dy.shape[-1] == 64
     n = L.get_lib().rvt_stem_wgrad_ws_floats(Cin, F_, H, W)
-    st = L.stream_of(dy)
-    key = ('stem', dy.device.type, dy.device.index, 0 if st is None else int(st))
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(n, dtype=torch.float32, device=dy.device)
-        _WS[key] = ws
+    st, ws = L.workspace('stem', dy, n, torch.float32)
     L.call('rvt_stem_wgrad', L.ptr(src), L.ptr(dy), L.ptr(dw), L.ptr(ws), L.dtype_code(dy.dtype), F_, Cin, cp, h, wd, H, W, st)
 
 
@@ -287,13 +273,7 @@ def _mlp_ws(xmid: Tensor) -> Tensor:
     C = xmid.shape[-1]
     M = xmid.numel() // C
     n = L.get_lib().rvt_mlp_bwd_fused_ws_floats(L.dtype_code(xmid.dtype), C, M)
-    st = L.stream_of(xmid)
-    key = ('mlpbwd', xmid.device.type, xmid.device.index, 0 if st is None else int(st))
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(n, dtype=torch.float32, device=xmid.device)
-        _WS[key] = ws
-    return ws
+    return L.workspace('mlpbwd', xmid, n, torch.float32)[1]
 
 
 def mlp_bwd_recompute_dgrad(dxout: Tensor, xmid: Tensor, ln_w: Tensor, ln_b: Tensor, w1: Tensor, b1: Tensor, w2g_t: Tensor,
@@ -490,16 +470,12 @@ def lstm_scan_bwd(x_all: Tensor, Hall: Tensor, Csave: Tensor, c0: Optional[Tenso
     T_, C = x_all.shape[0], x_all.shape[-1]
     M = x_all[0].numel() // C
     assert dc0.dtype == torch.float32 and (dc_last is None or dc_last.dtype == torch.float32)
-    ws = None
-    st = L.stream_of(x_all)
-    if dw is not None:
+    if dw is None:
+        st, ws = L.stream_of(x_all), None
+    else:
         assert dw.dtype == torch.float32 and db is not None and db.dtype == torch.float32 and tuple(dw.shape) == (4 * C, 2 * C)
         n = L.get_lib().rvt_lstm_scan_bwd_ws_floats(L.dtype_code(x_all.dtype), C, M)
-        key = ('scanbwd', x_all.device.type, x_all.device.index, 0 if st is None else int(st))
-        ws = _WS.get(key)
-        if ws is None or ws.numel() < n:
-            ws = torch.empty(n, dtype=torch.float32, device=x_all.device)
-            _WS[key] = ws
+        st, ws = L.workspace('scanbwd', x_all, n, torch.float32)
     L.call('rvt_lstm_scan_bwd', L.ptr(x_all), L.ptr(Hall), L.ptr(Csave), L.ptr(c0), L.ptr(dH), L.ptr(dc_last), L.ptr(w),
            L.ptr(wt), L.ptr(bias), L.ptr(dx_all), L.ptr(dz_all), L.ptr(dh0), L.ptr(dc0), L.ptr(dw), L.ptr(db), L.ptr(ws),
            L.ptr(gates), L.dtype_code(x_all.dtype), M, C, T_, st)

@@ -16,20 +16,10 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from ._header import STRUCTS, fields
 
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-
-
-class RvtBlockWeights(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ('n1_w', 'n1_b', 'qkv_w', 'qkv_b', 'proj_w', 'proj_b', 'g1', 'n2_w', 'n2_b', 'fc1_w', 'fc1_b',
-                                   'fc2_w', 'fc2_b', 'g2')]
-
-
-class RvtStageDesc(ctypes.Structure):
-    _fields_ = [('struct_bytes', _i), ('dtype', _i), ('C', _i), ('Cin', _i), ('cin_pad', _i), ('H_in', _i), ('W_in', _i), ('k', _i),
-                ('stride', _i), ('pad', _i), ('ph', _i), ('pw', _i), ('dim_head', _i), ('num_blocks', _i), ('eps', _f),
-                ('inp_u8', _i), ('h_raw', _i), ('w_raw', _i), ('conv_w', _vp), ('ln_w', _vp), ('ln_b', _vp),
-                ('blocks', ctypes.POINTER(RvtBlockWeights)), ('lstm_w', _vp), ('lstm_b', _vp), ('lstm_wn', _vp), ('lstm_bn', _vp)]
+RvtBlockWeights, RvtStageDesc, RvtStageRoutes, RvtBlockSaved, RvtBlockTrain, RvtStageTrain = (
+    STRUCTS[n] for n in ('RvtBlockWeights', 'RvtStageDesc', 'RvtStageRoutes', 'RvtBlockSaved', 'RvtBlockTrain', 'RvtStageTrain'))
 
 
 class StageCall:
@@ -43,7 +33,7 @@ class StageCall:
         for pair in sw.blocks:
             for bw in pair:
                 b = self.blocks[i]
-                for k in ('n1_w', 'n1_b', 'qkv_w', 'qkv_b', 'proj_w', 'proj_b', 'g1', 'n2_w', 'n2_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'g2'):
+                for k in fields(RvtBlockWeights):
                     setattr(b, k, p(bw[k]))
                 i += 1
         d = RvtStageDesc()
@@ -66,33 +56,13 @@ class StageCall:
         return n
 
 
-_WS = {}
-
-
-def _workspace(kind: str, like: torch.Tensor, n: int):
-    """(stream handle, grow-only byte workspace of at least n bytes for `kind` on that stream)."""
-    st, dev = L.stream_of(like), like.device
-    key = (kind, dev.type, dev.index, 0 if st is None else int(st))
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _WS[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-    return st, ws
-
-
-class RvtStageRoutes(ctypes.Structure):
-    """Mirror of `struct RvtStageRoutes` (include/rvt_hip.h): which kernels a stage runs."""
-    _fields_ = [(n, _i) for n in ('attn_block', 'ln_linear', 'mlp_route', 'mlp_bwd_both', 'dgrad_ln_qkv', 'dgrad_ln_fc1', 'lstm_route',
-                                  'lstm_scan_wgrad', 'conv_dgrad4', 'attn_preln', 'mlp_store_pre', 'mlp_bwd_dgrad', 'lstm_scan3_rb',
-                                  'driver_covers')]
-
-
 def plan(sw, g, dt, T: int, B: int, save: bool, token_mask, call: Optional[StageCall] = None) -> RvtStageRoutes:
     """The routes of one stage forward (and of its backward when save).  `call`: the stage's descriptor where the caller has one."""
     call = call or StageCall(sw, g, dt, False, 0, 0)
     r = RvtStageRoutes()
     lib = L.get_lib()
-    if lib.rvt_stage_routes(ctypes.byref(call.desc), T, B, int(save), int(sw.dws is not None), int(token_mask is not None), ctypes.byref(r)) != 0:
-        raise RuntimeError(f'rvt_stage_routes failed: {lib.rvt_last_error().decode()}')
+    L.check('rvt_stage_routes', lib.rvt_stage_routes(ctypes.byref(call.desc), T, B, int(save), int(sw.dws is not None), int(token_mask is not None),
+                                                     ctypes.byref(r)), lib)
     r.conv_dgrad4 = int(r.conv_dgrad4 and sw.conv_wd4 is not None)      # (the packed weight copy exists only for stages with an input gradient)
     return r
 
@@ -102,37 +72,20 @@ def stage_seq_fwd(call: StageCall, inp: torch.Tensor, h0: Optional[torch.Tensor]
     """Returns (Hall (T+1,B,H,W,C) in the compute dtype — slot 0 scratch, slots 1..T = h_t —, c_last (B,H,W,C) fp32)."""
     g, dt, dev = call.g, call.dtype, inp.device
     lib = L.get_lib()
-    st, ws = _workspace('fwd', inp, call.ws_bytes(T, B))
+    st, ws = L.workspace('fwd', inp, call.ws_bytes(T, B), torch.uint8)
     Hall = torch.empty((T + 1, B, g.H, g.W, g.C), dtype=dt, device=dev)
     c_last = torch.empty((B, g.H, g.W, g.C), dtype=torch.float32, device=dev)
     if h0 is not None:
         assert h0.dtype == dt and h0.is_contiguous() and c0 is not None and c0.dtype == torch.float32 and c0.is_contiguous()
     rc = lib.rvt_stage_seq_fwd(ctypes.byref(call.desc), L.ptr(inp), L.ptr(h0), L.ptr(c0), L.ptr(Hall), L.ptr(c_last), L.ptr(ws),
                                ws.numel(), T, B, st)
-    if rc != 0:
-        raise RuntimeError(f'rvt_stage_seq_fwd failed: {lib.rvt_last_error().decode()}')
+    L.check('rvt_stage_seq_fwd', rc, lib)
     return Hall, c_last
 
 
 # ---- training-side driver (round 6; include/rvt_hip.h: rvt_stage_seq_train_fwd / rvt_stage_seq_bwd, csrc/capi_train.hip) ----------------
 # plan() decides the routes; the host owns every tensor that outlives a call; the library sequences the launches.  `StageSaved` is filled
 # exactly as the Python host loop fills it, so either backward can consume it.
-class RvtBlockSaved(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ('xin', 'u', 'qkv', 'a', 'xmid', 'v2', 'hg', 'hgp', 'xout')]
-
-
-class RvtBlockTrain(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ('qkv_wt', 'proj_wt', 'fc1_wt', 'fc2_wt', 'd_n1_w', 'd_n1_b', 'd_qkv_w', 'd_qkv_b', 'd_S1', 'd_cs1',
-                                   'd_n2_w', 'd_n2_b', 'd_fc1_w', 'd_fc1_b', 'd_S2', 'd_cs2')]
-
-
-class RvtStageTrain(ctypes.Structure):
-    _fields_ = [('struct_bytes', _i), ('routes', RvtStageRoutes)] + \
-               [('saved', ctypes.POINTER(RvtBlockSaved)), ('tb', ctypes.POINTER(RvtBlockTrain))] + \
-               [(n, _vp) for n in ('y0', 'x0', 'Hall', 'c_last', 'Csave', 'gates', 'Call', 'c0_saved', 'lstm_wp3', 'lstm_wtp3', 'lstm_wt',
-                                   'conv_wd4', 'conv_wd', 'd_lstm_w', 'd_lstm_b', 'd_ln_w', 'd_ln_b', 'd_raw_conv')]
-
-
 class TrainCall:
     """Everything one stage's training forward built for its backward: descriptors, host-side block arrays, the routes taken."""
     __slots__ = ('call', 'tr', 'saved_arr', 'tb_arr', 'inp', 'keep')
@@ -201,8 +154,7 @@ def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0
     tr.Csave, tr.gates, tr.Call = L.ptr(Csave), L.ptr(gates), L.ptr(Call)
     lib = L.get_lib()
     rc = lib.rvt_stage_seq_train_fwd(ctypes.byref(call.desc), ctypes.byref(tr), L.ptr(inp), L.ptr(c0) if lr != 0 else None, T, B, L.stream_of(inp))
-    if rc != 0:
-        raise RuntimeError(f'rvt_stage_seq_train_fwd failed: {lib.rvt_last_error().decode()}')
+    L.check('rvt_stage_seq_train_fwd', rc, lib)
     sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, Call, gates
     sv.xin_lstm, sv.hconv, sv.Csave = x, None, Csave
     sv.c0 = None if (c0 is None or lr == 0) else c0.clone()      # (scan routes: the state the forward saw; RNNStates resets states in place)
@@ -251,9 +203,8 @@ def train_backward(sw, g, sv, dH, dc_last, T: int, B: int, need_input_grad: bool
     dc0 = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
     d_in = torch.empty((T * B, g.H_in, g.W_in, g.Cin), dtype=dt, device=dev) if need_input_grad else None
     lib = L.get_lib()
-    st, ws = _workspace('train', sv.y0, int(lib.rvt_stage_seq_bwd_ws_bytes(ctypes.byref(call.desc), ctypes.byref(tr), T, B)))
+    st, ws = L.workspace('train', sv.y0, int(lib.rvt_stage_seq_bwd_ws_bytes(ctypes.byref(call.desc), ctypes.byref(tr), T, B)), torch.uint8)
     rc = lib.rvt_stage_seq_bwd(ctypes.byref(call.desc), ctypes.byref(tr), L.ptr(tc.inp), L.ptr(dH), L.ptr(dcl), L.ptr(prev_cot), L.ptr(d_in),
                                L.ptr(dh0), L.ptr(dc0), L.ptr(ws), ws.numel(), T, B, st)
-    if rc != 0:
-        raise RuntimeError(f'rvt_stage_seq_bwd failed: {lib.rvt_last_error().decode()}')
+    L.check('rvt_stage_seq_bwd', rc, lib)
     return d_in, dh0, dc0

@@ -18,18 +18,10 @@ import contextlib
 import ctypes
 from typing import Dict, Iterator
 
-_GEOMETRY = ('gemm_resident', 'gemm_xcd_panels', 'wgrad_bn', 'wgrad_blocks', 'wgrad_slice_tokens', 'ppgemm', 'ppgemm_min_m',
-             'ppgemm_all', 'ppgemm_grid', 'ppgemm_tn_items', 'one_per_cu_grid', 'stem', 'stem_depth', 'mlp_tm', 'mlp_chain',
-             'mlp_chain_wgrad', 'chain_resident', 'attn_block_resident', 'dgrad_ln')
-_LATE = ('lstm_scan_v2', 'route_stage_driver', 'route_mlp_store_pre', 'route_mlp_bwd_both', 'mlp_stream', 'ln_linear', 'conv_wgrad_tn', 'attn_staged', 'lstm_scan3', 'lstm_scan3_rb256', 'lstm_scan3_rb128', 'route_stage_driver_train', 'route_attn_preln', 'conv_fwd_pp')          # fields appended after the routes (struct order = _GEOMETRY + _ROUTES + _LATE)
-_ROUTES = ('route_fused_mlp', 'route_mlp_bwd_fused', 'route_attn_block', 'route_lstm_scan', 'route_lstm_scan_wgrad',
-           'route_conv_dgrad4', 'route_wgrad_stream')
-FIELDS = _GEOMETRY + _ROUTES + _LATE
+from ._header import STRUCTS, fields
 
-
-class RvtTuning(ctypes.Structure):
-    """Mirror of `struct RvtTuning` (include/rvt_hip.h) — field order is part of the C ABI."""
-    _fields_ = [('struct_bytes', ctypes.c_int)] + [(f, ctypes.c_int) for f in FIELDS]
+RvtTuning = STRUCTS['RvtTuning']                                        # field order is part of the C ABI: the header's
+FIELDS = tuple(f for f in fields(RvtTuning) if f != 'struct_bytes')
 
 
 # what the tests install: small grids so that test-size problems walk several tiles / K slices per workgroup, and every
@@ -55,8 +47,8 @@ def push(lib) -> None:
     t = _defaults(lib)
     for k, v in _overrides.items():
         setattr(t, k, int(v))
-    if lib.rvt_set_tuning(ctypes.byref(t)) != 0:
-        raise RuntimeError(f'rvt_set_tuning failed: {lib.rvt_last_error().decode()}')
+    from . import _lib
+    _lib.check('rvt_set_tuning', lib.rvt_set_tuning(ctypes.byref(t)), lib)
     _pushed_to = lib
     _cache = {f: int(getattr(t, f)) for f in FIELDS}
 

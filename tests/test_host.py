@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import rvt_amd
-from rvt_amd import _lib, backbone_config
+from rvt_amd import _header, _lib, backbone_config
 from rvt_amd.states import RNNStates, merge_mixed_batches
 from rvt_amd.types import DataType, DatasetSamplingMode
 
@@ -23,7 +23,147 @@ def declared_symbols():
 
 
 def test_header_and_binding_agree():
-    assert declared_symbols() == _lib.EXPORTS
+    """An independent regex over the raw header against the names the binding derives from it."""
+    assert declared_symbols() == _lib.EXPORTS == sorted(_lib._SIGS)
+
+
+# ---- the header reader (rvt_amd/_header.py) on short synthetic headers: the exact ctypes types --------------------------------------
+_VP, _I, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
+
+
+def _same_types(got, want):
+    return len(got) == len(want) and all(a is b for a, b in zip(got, want))
+
+
+def test_header_reader_prototypes():
+    _, protos = _header.parse('''
+        /* a comment with ( and ; inside, int not_a_function(int x); and text right up to the end*/int rvt_a(const void* x,
+                  float* y, int n,
+                  float eps, void* stream);
+        // a line comment (with a parenthesis; and a semicolon)
+        #define RVT_SOMETHING {(int)sizeof(int), 0}
+        const char* rvt_msg(void);
+        double rvt_rate(float* scratch, int iters);
+        size_t rvt_bytes(size_t n, long long slots, const long long* perm, const void* const* maps, const unsigned char* mask);
+    ''')
+    assert list(protos) == ['rvt_a', 'rvt_msg', 'rvt_rate', 'rvt_bytes']
+    assert protos['rvt_a'].restype is _I and _same_types(protos['rvt_a'].argtypes, [_VP, _VP, _I, _F, _VP])
+    assert protos['rvt_a'].argnames == ('x', 'y', 'n', 'eps', 'stream')
+    assert protos['rvt_msg'].restype is ctypes.c_char_p and protos['rvt_msg'].argtypes == []
+    assert protos['rvt_rate'].restype is _D and _same_types(protos['rvt_rate'].argtypes, [_VP, _I])
+    assert protos['rvt_bytes'].restype is ctypes.c_size_t
+    assert _same_types(protos['rvt_bytes'].argtypes, [ctypes.c_size_t, ctypes.c_longlong, _VP, _VP, _VP])
+
+
+def test_header_reader_structs():
+    structs, protos = _header.parse('''
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        enum { RVT_X = 0, RVT_Y = 1 };
+        typedef struct Inner {
+            int a, b;                       /* two names, one declarator */
+            const float *w, *bias; const void* p; float eps;
+        } Inner;
+        typedef struct Outer {
+            int struct_bytes;
+            Inner by_value;
+            const Inner* arr;               /* HOST array */
+            void *y0, *x0;
+            double* sums;
+        } Outer;
+        void rvt_fill(Outer* t);
+        int rvt_use(const Outer* t, const Inner* i, int n);
+        #ifdef __cplusplus
+        }
+        #endif
+    ''')
+    Inner, Outer = structs['Inner'], structs['Outer']
+    assert list(structs) == ['Inner', 'Outer'] and issubclass(Inner, ctypes.Structure) and issubclass(Outer, ctypes.Structure)
+    assert [f for f, _ in Inner._fields_] == ['a', 'b', 'w', 'bias', 'p', 'eps'] == list(_header.fields(Inner))
+    assert _same_types([t for _, t in Inner._fields_], [_I, _I, _VP, _VP, _VP, _F])
+    assert [f for f, _ in Outer._fields_] == ['struct_bytes', 'by_value', 'arr', 'y0', 'x0', 'sums']
+    assert _same_types([t for _, t in Outer._fields_], [_I, Inner, ctypes.POINTER(Inner), _VP, _VP, _VP])
+    assert ctypes.sizeof(Outer) == 8 + ctypes.sizeof(Inner) + 4 * 8 and ctypes.sizeof(Inner) == 40
+    # in a prototype a struct pointer is the very object c_void_p (callers pass byref), a void return is None
+    assert protos['rvt_fill'].restype is None and _same_types(protos['rvt_fill'].argtypes, [_VP])
+    assert protos['rvt_use'].restype is _I and _same_types(protos['rvt_use'].argtypes, [_VP, _VP, _I])
+
+
+@pytest.mark.parametrize('text,says', [
+    ('int rvt_a(const void* x, uint64_t n);', 'uint64_t'),                          # unknown type of a parameter
+    ('typedef struct S { short a; } S;', 'short'),                                  # ... of a field
+    ('int rvt_a(int n);\nstatic int counter = 0;\nint rvt_b(int n);', 'counter'),    # a declaration the reader has no rule for
+    ('int rvt_a(int n);\nstruct Loose { int a; };', 'Loose'),                        # a struct outside the typedef form
+], ids=['unknown_param_type', 'unknown_field_type', 'leftover_declaration', 'leftover_struct'])
+def test_header_reader_refuses(text, says):
+    with pytest.raises(RuntimeError, match=says):
+        _header.parse(text)
+
+
+def test_header_reader_names_a_missing_header(monkeypatch):
+    monkeypatch.setattr(_header, 'HEADER_PATH', os.path.join(ROOT, 'include', 'no_such_header.h'))
+    with pytest.raises(RuntimeError, match='no_such_header.h'):
+        _header._read()
+
+
+def test_derived_binding_covers_the_real_header():
+    """Every prototype and all 7 structs of include/rvt_hip.h; tuning.FIELDS is the struct's own order."""
+    from rvt_amd import stage_driver, tuning
+    assert set(_header.STRUCTS) == {'RvtTuning', 'RvtBlockWeights', 'RvtStageDesc', 'RvtStageRoutes', 'RvtBlockSaved', 'RvtBlockTrain',
+                                    'RvtStageTrain'}
+    assert ('struct_bytes',) + tuning.FIELDS == _header.fields(tuning.RvtTuning) and tuning.RvtTuning is _header.STRUCTS['RvtTuning']
+    assert all(getattr(stage_driver, n) is c for n, c in _header.STRUCTS.items() if n != 'RvtTuning')
+    assert all(ty is ctypes.c_void_p or ty in (_I, _F, ctypes.c_size_t, ctypes.c_longlong) for sig in _lib._SIGS.values() for ty in sig)
+    assert _lib._SIGS['rvt_stage_routes'][0] is ctypes.c_void_p and _lib._SIGS['rvt_stage_routes'][-1] is ctypes.c_void_p
+
+
+def test_generated_structs_are_accepted_by_the_library():
+    """The C side compares struct_bytes with its own sizeof: the emulator build of the same header accepts the generated structs."""
+    from rvt_amd import stage_driver as SD, tuning
+    from tests.backends import emu_library
+    from tests.test_route_record import _desc
+    lib = emu_library()
+    t = tuning.RvtTuning()
+    t.struct_bytes = ctypes.sizeof(t)
+    assert lib.rvt_get_tuning(ctypes.byref(t)) == 0, lib.rvt_last_error()
+    t.struct_bytes -= 4
+    assert lib.rvt_get_tuning(ctypes.byref(t)) != 0                     # (the guard is live)
+    T = 1
+    d, keep, B = _desc(torch.bfloat16, 32, T, 2560)
+    assert d.struct_bytes == ctypes.sizeof(SD.RvtStageDesc)
+    tr = SD.RvtStageTrain()
+    assert lib.rvt_stage_routes(ctypes.byref(d), T, B, 1, 0, 0, ctypes.byref(tr.routes)) == 0, lib.rvt_last_error()
+    saved = (SD.RvtBlockSaved * 2)()
+    tr.saved = ctypes.cast(saved, ctypes.POINTER(SD.RvtBlockSaved))
+    tr.struct_bytes = ctypes.sizeof(SD.RvtStageTrain)
+    assert lib.rvt_stage_seq_bwd_ws_bytes(ctypes.byref(d), ctypes.byref(tr), T, B) > 0
+    tr.struct_bytes += 8
+    assert lib.rvt_stage_seq_bwd_ws_bytes(ctypes.byref(d), ctypes.byref(tr), T, B) == 0
+
+
+def test_one_workspace_cache(monkeypatch):
+    """One dict keyed (kind, device type, device index, stream): a buffer per kind, grow-only, the floor honoured, the dtype kept."""
+    monkeypatch.setattr(_lib, '_WS', {})
+    like = torch.zeros(1)
+    st, a = _lib.workspace('wgrad', like, 10, torch.float32, floor=64)
+    assert st is None and a.numel() == 64 and a.dtype == torch.float32
+    assert _lib.workspace('wgrad', like, 64, torch.float32, floor=64)[1] is a          # fits: the same buffer
+    b = _lib.workspace('wgrad', like, 65, torch.float32, floor=64)[1]
+    assert b is not a and b.numel() == 65
+    assert _lib.workspace('wgrad', like, 3, torch.float32, floor=64)[1] is b           # never shrunk
+    c = _lib.workspace('fwd', like, 7, torch.uint8)[1]
+    assert c.dtype == torch.uint8 and c.numel() == 7 and _lib.workspace('wgrad', like, 1, torch.float32)[1] is b      # kinds do not share
+    assert sorted(_lib._WS) == [('fwd', 'cpu', None, 0), ('wgrad', 'cpu', None, 0)]
+
+
+def test_one_status_check():
+    class Lib:
+        def rvt_last_error(self):
+            return b'why'
+    _lib.check('rvt_x', 0, Lib())
+    with pytest.raises(RuntimeError, match='rvt_x failed: why'):
+        _lib.check('rvt_x', 3, Lib())
 
 
 def test_hip_library_loads_and_exports_every_symbol():
