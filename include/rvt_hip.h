@@ -1,8 +1,11 @@
 /* C ABI of librvt_hip.so — the MI355X (gfx950) kernels behind the RVT recurrent backbone.
  *
  * The reference (uzh-rpg/RVT) is pure PyTorch and has no FFI of its own; these entry points are the
- * operator boundary a maintainer would bind (ctypes stub: rvt_amd/_lib.py).  Each
- * one replaces the ATen op sequence of the cited reference lines.  Plain pointers and sizes only:
+ * operator boundary a maintainer would bind.  Each one replaces the ATen op sequence of the
+ * cited reference lines.  This header is the ONLY statement of the boundary: the prototypes, the host-side records and
+ * the rows of every device table (RvtPackDesc, RvtLayerScaleDesc, RvtOptimChunk, RvtOptimGroup, RvtEventStream) with the
+ * enumerators a host needs to fill them are declared here; rvt_amd/_header.py derives the ctypes binding and the numpy
+ * row layouts from this text, and nothing restates a layout or an argument position elsewhere.  Plain pointers and sizes only:
  *   - every pointer is a DEVICE pointer unless stated otherwise;
  *   - `dtype` selects the storage / MFMA input type of activations and weights:
  *         RVT_F32  (0)  float   — parity mode, exact f32 MFMA
@@ -130,7 +133,7 @@ int rvt_conv_fwd(const void* in, const void* w, void* out, int dtype, int F, int
                  int k, int stride, int pad, void* stream);
 /* Input gradient of the 3x3 / stride-2 / pad-1 down-sampling conv of stages 2-4 (reference maxvit.py:160-168, autograd) as ONE
  * product over 2x2 blocks of input pixels (csrc/ppgemm.hpp, GATHER mode).  wd4: [4*Cin][4*Cout] weights in the block-sparse layout
- * of PACK_CONV_DGRAD4 (csrc/pack.hpp); add (nullable): cotangent already attached to the input, same shape as din.
+ * of RVT_PACK_CONV_DGRAD4 (below); add (nullable): cotangent already attached to the input, same shape as din.
  * rvt_conv_dgrad4_supported: bf16, k 3, stride 2, pad 1, even H and W, Cin and Cout multiples of 64, enough rows. */
 int rvt_conv_dgrad4_supported(int dtype, int H, int W, int Cin, int Cout, int k, int stride, int pad, int F);
 int rvt_conv_dgrad4(const void* dy, const void* wd4, const void* add, void* din, int dtype, int F, int H, int W, int Cin, int Cout,
@@ -581,16 +584,48 @@ int rvt_yolox_detect(const void* const* reg_obj, const void* const* cls, int ld_
  * st is [B][per_sample] of float32 (is_f32) or `dtype`. */
 int rvt_state_reset_masked(void* st, const unsigned char* mask, int dtype, int B, size_t per_sample, void* stream);
 
-/* Parameter-side tables (rvt_amd/csrc/pack.hpp; host mirror rvt_amd/weights.py).  One launch walks an array of
- * descriptors in DEVICE memory:
+/* Parameter-side tables (rvt_amd/csrc/pack.hpp; built by rvt_amd/weights.py).  One launch walks an array of descriptors in
+ * DEVICE memory, 8-byte aligned; the pointers in a row are device pointers that outlive the launches (parameter storage,
+ * packed-weight buffers, gradient buckets).  block0 of a row = the blocks of all rows before it (ascending, row 0 has 0).
  *   rvt_pack_table: element-wise gathers fp32 parameter -> kernel-side layout (cast, transpose with LayerScale folded in,
  *     tap-major conv weights, stride-parity conv-dgrad panels, gate-interleaved ConvLSTM rows) and the accumulating unpack
  *     of the raw conv weight gradient — what the reference leaves to autograd / .to() / permute (maxvit.py:51-53,160-168,
- *     rnn.py:52-61).  total_blocks = sum over descriptors of ceil(n / 1024).
- *   rvt_layerscale_grad_table: dW += gamma*S, db += gamma*cs, dgamma += rowsum(W*S) + b*cs for the proj / fc2 linears
- *     whose input-gradient weights carry LayerScale.  total_blocks = sum of C (one block per output channel). */
-int rvt_pack_table(const void* descs, int n_desc, int total_blocks, int dtype, void* stream);
-int rvt_layerscale_grad_table(const void* descs, int n_desc, int total_blocks, void* stream);
+ *     rnn.py:52-61).  A row owns ceil(n / RVT_PACK_BLOCK_ELEMS) blocks; total_blocks = their sum.
+ *   rvt_layerscale_grad_table: LayerScale (maxvit.py:51-53) folded out of the weight gradients of the proj / fc2 linears, whose
+ *     input-gradient weights carry gamma: dW += gamma*S, db += gamma*cs, dgamma += rowsum(W*S) + b*cs.  A row owns C blocks
+ *     (one per output channel); total_blocks = their sum. */
+enum {                               /* RvtPackDesc.kind: element-wise gather from one fp32 source into one destination */
+    RVT_PACK_COPY = 0,               /* dst[i] = src[i] */
+    RVT_PACK_TRANSPOSE = 1,          /* src [R][K] -> dst [K][R], optionally * scale[r]      (d0 = R, d1 = K) */
+    RVT_PACK_CONV_FWD = 2,           /* src [Cout][Cin][k][k] -> dst [Cout][k*k*cp] tap-major, cin fastest, zero padded (d0..d3 = Cout,Cin,k,cp) */
+    RVT_PACK_CONV_DGRAD = 3,         /* src [Cout][Cin][k][k] -> dst [Cin][nky*nkx*Cout] of one stride-parity class (d0..d4 = Cout,Cin,k,nky,nkx) */
+    RVT_PACK_LSTM_ROWS = 4,          /* src [4C][K] -> dst rows interleaved n' = (c/8)*32 + gate*8 + c%8            (d0 = C, d1 = K) */
+    RVT_PACK_CONV_WGRAD_ACC = 5,     /* src [Cout][k*k*cp] (raw fp32 product) -> dst [Cout][Cin][k][k] += ...      (d0..d3 = Cout,Cin,k,cp) */
+    RVT_PACK_CONV_DGRAD4 = 6         /* src [Cout][Cin][3][3] -> dst [(py,px,ci)][(da,db,co)] of the 2 x 2-block input gradient (ppgemm.hpp
+                                        GATHER; d0, d1 = Cout, Cin): w[co][ci][ky][kx], ky = 1 | 2, 0 for py = 0 | 1 and da = 0, 1; else 0 */
+};
+enum { RVT_PACK_BLOCK_ELEMS = 1024 };    /* consecutive destination elements of one descriptor per logical block (what block0 counts) */
+typedef struct RvtPackDesc {
+    const float* src;
+    void* dst;
+    const float* scale;
+    long long n;              /* destination elements */
+    int kind;                 /* RVT_PACK_* */
+    int out_f32;              /* destination is fp32 whatever the launch dtype */
+    int d[5];
+    int ky[4], kx[4];         /* RVT_PACK_CONV_DGRAD: the taps of the parity class */
+    unsigned block0;          /* first block of this descriptor within the launch */
+} RvtPackDesc;
+typedef struct RvtLayerScaleDesc {
+    const float* S; const float* cs;      /* raw products of the OUTER cotangent dy: S[c][k] = sum_tok dy[tok][c] a[tok][k],
+                                             cs[c] = sum_tok dy[tok][c] */
+    const float* W; const float* b; const float* gamma;
+    float* dW; float* db; float* dgamma;  /* accumulated (+=) */
+    int C, K;
+    unsigned block0; int pad;
+} RvtLayerScaleDesc;
+int rvt_pack_table(const RvtPackDesc* descs, int n_desc, int total_blocks, int dtype, void* stream);
+int rvt_layerscale_grad_table(const RvtLayerScaleDesc* descs, int n_desc, int total_blocks, void* stream);
 
 /* Event stream -> stacked histogram, the uint8 event tensor the backbone consumes (data/utils/representations.py:76-117,
  * StackedHistogram.construct): x, y, pol (0/1), time are int64 [n_events], time sorted ascending.
@@ -605,12 +640,9 @@ int rvt_stacked_histogram(const long long* x, const long long* y, const long lon
  * searchsorted over the timestamps, one StackedHistogram.construct per window and, for the 1 Mpx sensor, the half-scale
  * nearest-exact interpolate of the full-size histogram.  Bit-exact with that composition for any event order.
  *
- * streams: table of B rows of 48 bytes in DEVICE memory, 8-byte aligned:
- *     const void* x;  const void* y;  const void* p;  const int64* t;  int64 n;  const int64* ts_end
- *   x, y, p: n coordinates / polarities each, all of coord_bytes = 2 (int16), 4 (int32) or 8 (int64) bytes, one width per call;
- *   t: n timestamps in microseconds, NON-DECREASING (the reference reader's timestamp repair is the caller's); n is read on the
- *   device, so a captured graph replays after the host rewrote events and n in place, up to the buffers' capacity;
- *   ts_end: the T window end timestamps of that sample (rows may share one array).
+ * streams: B rows of RvtEventStream (below) in DEVICE memory, 8-byte aligned.  x, y, p are all of coord_bytes = 2 (int16), 4 (int32)
+ *   or 8 (int64) bytes, one width per call; n is read on the device, so a captured graph replays after the host rewrote events
+ *   and n in place, up to the buffers' capacity.
  * Window w of sample b:  end = searchsorted(t, ts_end[w], side='right');  window_us > 0: start = searchsorted(t, ts_end[w] -
  *   window_us, side='left');  window_events > 0: start = max(end - window_events, 0).  Exactly one of the two is positive.
  *   bounds int64 [B][T][2] receives (start, end).  Windows may overlap and may be empty (an all-zero image).
@@ -627,8 +659,16 @@ int rvt_stacked_histogram(const long long* x, const long long* y, const long lon
  *   chunks of windows_in_flight: one count and one narrowing launch per chunk, after one launch for all bounds.
  * count_blocks: workgroups per window of the count launch (they stride over the window; the grid cannot depend on bounds that
  *   live on the device); 0 = sized by the library (about 2048 over a chunk, 8..256 per window). */
+typedef struct RvtEventStream {
+    const void* x;            /* n coordinates / polarities each */
+    const void* y;
+    const void* p;
+    const long long* t;       /* n timestamps in microseconds, NON-DECREASING (the reference reader's timestamp repair is the caller's) */
+    long long n;
+    const long long* ts_end;  /* the T window end timestamps of that sample (rows may share one array) */
+} RvtEventStream;
 size_t rvt_event_sequence_ws_bytes(int bins, int H, int W, int downsample_by_2, int windows_in_flight);
-int rvt_event_sequence(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
+int rvt_event_sequence(const RvtEventStream* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
                        int H, int W, int downsample_by_2, int count_cutoff, int fastmode, long long* bounds, void* scratch,
                        int windows_in_flight, int count_blocks, unsigned char* out, void* stream);
 
@@ -657,7 +697,7 @@ int rvt_event_sequence(const void* streams, int B, int T, int coord_bytes, long 
 int rvt_mixed_density_stack(const long long* x, const long long* y, const long long* pol, const long long* time, size_t n_events,
                             int bins, int H, int W, int count_cutoff, int* scratch, signed char* out, void* stream);
 size_t rvt_event_sequence_mixed_ws_bytes(int bins, int H, int W, int downsample_by_2, int windows_in_flight);
-int rvt_event_sequence_mixed(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
+int rvt_event_sequence_mixed(const RvtEventStream* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
                              int H, int W, int downsample_by_2, int count_cutoff, long long* bounds, void* scratch,
                              int windows_in_flight, int count_blocks, signed char* out, void* stream);
 
@@ -697,14 +737,10 @@ int rvt_augment_labels(const float* rows, const int* count, const float* table, 
  * (decoupled weight decay, no amsgrad) and the OneCycle learning-rate schedule of every parameter of every parameter group in one
  * call (reference modules/detection.py:360-392 and the trainer's gradient_clip_val by value).  Two tables in DEVICE memory, built
  * once by the host, 8-byte aligned:
- *   chunks [n_chunks] of 40 bytes, one per piece of at most 4096 consecutive elements of one parameter (fp32, contiguous):
- *     float* p;  const float* g;  float* exp_avg;  float* exp_avg_sq;  int32 n (1..4096);  int32 group (0..n_groups-1)
- *     pieces of one tensor start 4096 elements apart; a tensor of at most 4096 elements is one entry.  A chunk whose four
- *     pointers are 16-byte aligned moves in 16-byte accesses, any other element by element.
- *   groups [n_groups] of 80 bytes, ten doubles:
- *     beta1, beta2, eps, weight_decay, clip (< 0 = no clipping), lr_init, lr_max, lr_final, warm_end, last
- *     warm_end = float(pct_start * total_steps) - 1 and last = total_steps - 1 are schedule POSITIONS (warm_end may be fractional);
- *     a constant learning rate is lr_init = lr_max = lr_final = lr, warm_end = last = 0.
+ *   chunks [n_chunks] of RvtOptimChunk, one per piece of at most RVT_OPTIM_CHUNK_ELEMS consecutive elements of one parameter
+ *     (fp32, contiguous): pieces of one tensor start that many elements apart; a shorter tensor is one entry.  A chunk whose
+ *     four pointers are 16-byte aligned moves in 16-byte accesses, any other element by element.
+ *   groups [n_groups] of RvtOptimGroup, all double like the Python floats torch keeps them in.
  *   step: int64 on the device, the optimizer steps done so far.  The call uses k = *step + 1 in every workgroup and leaves
  *     *step = k behind (a trailing one-thread launch of the same call), so a captured graph replays with nothing written by the host.
  * In double, per workgroup:  pos = k - 1;  lr = (lr_max - lr_init) * (pos / warm_end) + lr_init for pos <= warm_end,
@@ -715,7 +751,24 @@ int rvt_augment_labels(const float* rows, const int* count, const float* table, 
  *     p = p * (1 - lr * weight_decay);  m = m + (1 - beta1) * (g - m);  v = beta2 * v + ((1 - beta2) * g) * g
  *     p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))
  * max_blocks: grid cap, 0 = the default (2048 workgroups; chunks beyond are walked grid-stride). */
-int rvt_optim_step(const void* chunks, int n_chunks, const void* groups, int n_groups, long long* step, int max_blocks, void* stream);
+enum { RVT_OPTIM_CHUNK_ELEMS = 4096 };
+typedef struct RvtOptimChunk {
+    float* p;
+    const float* g;
+    float* m;                 /* exp_avg */
+    float* v;                 /* exp_avg_sq */
+    int n;                    /* 1 .. RVT_OPTIM_CHUNK_ELEMS elements */
+    int group;                /* 0 .. n_groups - 1 */
+} RvtOptimChunk;
+typedef struct RvtOptimGroup {
+    double beta1, beta2, eps, weight_decay;
+    double clip;              /* < 0: no clipping */
+    double lr_init, lr_max, lr_final;
+    double warm_end;          /* end of the first phase as a schedule position: float(pct_start * total_steps) - 1, may be fractional */
+    double last;              /* last position of the schedule: total_steps - 1.  No schedule: lr_init = lr_max = lr_final, 0, 0 */
+} RvtOptimGroup;
+int rvt_optim_step(const RvtOptimChunk* chunks, int n_chunks, const RvtOptimGroup* groups, int n_groups, long long* step, int max_blocks,
+                   void* stream);
 
 /* Prophesee / COCO mAP evaluation of detections on the device (rvt_amd/csrc/cocoeval.hpp; host mirror rvt_amd/evaluation.py).
  * Replaces utils/evaluation/prophesee/ (filter_boxes, evaluate_list, coco_eval.py) and the COCOeval core it calls (evaluateImg,

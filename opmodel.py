@@ -2,7 +2,7 @@
 
 MEASUREMENT INFRASTRUCTURE (not part of the product path).  Round 3's bench could only price GEMM-family launches, so its
 `roofline` could never name the worst kernels.  `model(name, args)` returns, from the launch's own
-arguments (positions per include/rvt_hip.h):
+arguments (read by the parameter names of include/rvt_hip.h, never by position):
 
   flops  ALGORITHMIC MFMA-side work of the operator, 2*MAC: the products the reference's forward / autograd
          performs for the same result - e.g. 16 M C^2 for each of {MLP forward, its input gradients, its weight gradients}.
@@ -20,6 +20,8 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+from rvt_amd._header import LaunchArgs
+
 HBM_PEAK_GBS = 8000.0                             # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6.3 TB/s achievable
 PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3}      # dense MFMA peaks at 2.4 GHz
 
@@ -32,184 +34,173 @@ def _conv_out(H, W, k, s, p):
     return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
 
 
-def model(name: str, a) -> Optional[Tuple[float, float]]:
-    """(flops, bytes) of one launch, or None for an entry point with no model (host-side tables, size queries)."""
-    P = lambda i: a[i] is not None              # pointer argument present?
+def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
+    """(algorithmic flops, bytes, flops a recompute adds on top) of one launch; `a` = the launch's arguments by the header's
+    parameter names (rvt_amd/_header.py: LaunchArgs).  None for an entry point with no model."""
     if name == 'rvt_stem_fwd':
-        e, F, Cin, h, w, H, W = _elt(a[6]), a[7], a[8], a[10], a[11], a[12], a[13]
-        Ho, Wo = _conv_out(H, W, 7, 4, 3)
-        return 2.0 * F * Ho * Wo * 64 * Cin * 49, F * Cin * h * w + 2.0 * F * Ho * Wo * 64 * e + 64 * 49 * Cin * e
+        e, F, Cin = _elt(a.dtype), a.F, a.Cin
+        Ho, Wo = _conv_out(a.H, a.W, 7, 4, 3)
+        return 2.0 * F * Ho * Wo * 64 * Cin * 49, F * Cin * a.h * a.wd + 2.0 * F * Ho * Wo * 64 * e + 64 * 49 * Cin * e, 0.0
     if name == 'rvt_stem_wgrad':
-        e, F, Cin, h, w, H, W = _elt(a[4]), a[5], a[6], a[8], a[9], a[10], a[11]
-        Ho, Wo = _conv_out(H, W, 7, 4, 3)
-        return 2.0 * F * Ho * Wo * 64 * Cin * 49, F * Cin * h * w + 1.0 * F * Ho * Wo * 64 * e + 64 * 49 * Cin * 4
-    if name == 'rvt_prepack_input':
-        src_u8, e, F, Cin, h, w, H, W, Cp = a[1], _elt(a[3]), a[4], a[5], a[6], a[7], a[8], a[9], a[10]
-        return 0.0, F * Cin * h * w * (1 if src_u8 else 4) + 1.0 * F * H * W * Cp * e
+        e, F, Cin = _elt(a.dtype), a.F, a.Cin
+        Ho, Wo = _conv_out(a.H, a.W, 7, 4, 3)
+        return 2.0 * F * Ho * Wo * 64 * Cin * 49, F * Cin * a.h * a.wd + 1.0 * F * Ho * Wo * 64 * e + 64 * 49 * Cin * 4, 0.0
+    if name == 'rvt_prepack_input':                      # src_kind 0 = float32 planes, else one byte per element
+        return 0.0, a.F * a.Cin * a.h * a.w * (1 if a.src_kind else 4) + 1.0 * a.F * a.H * a.W * a.Cp * _elt(a.dtype), 0.0
     if name in ('rvt_conv_fwd', 'rvt_conv_wgrad', 'rvt_conv_dgrad'):
-        o = {'rvt_conv_fwd': 3, 'rvt_conv_wgrad': 4, 'rvt_conv_dgrad': 4}[name]
-        e, F, H, W, Cin, Cout, k, s, p = _elt(a[o]), *a[o + 1:o + 9]
-        Ho, Wo = _conv_out(H, W, k, s, p)
+        e, F, H, W, Cin, Cout, k = _elt(a.dtype), a.F, a.H, a.W, a.Cin, a.Cout, a.k
+        Ho, Wo = _conv_out(H, W, k, a.stride, a.pad)
         fl = 2.0 * F * Ho * Wo * Cout * Cin * k * k
         by = 1.0 * F * H * W * Cin * e + 1.0 * F * Ho * Wo * Cout * e + Cout * Cin * k * k * (4 if name.endswith('wgrad') else e)
-        if name == 'rvt_conv_dgrad' and P(2):
+        if name == 'rvt_conv_dgrad' and a.has('add'):
             by += 1.0 * F * H * W * Cin * e
-        return fl, by
+        return fl, by, 0.0
     if name == 'rvt_conv_dgrad4':
-        e, F, H, W, Cin, Cout = _elt(a[4]), *a[5:10]
-        by = 1.0 * F * H * W * Cin * e * (2 if P(2) else 1) + 1.0 * F * (H // 2) * (W // 2) * Cout * e + 9 * Cout * Cin * e
-        return 2.0 * F * (H // 2) * (W // 2) * Cout * Cin * 9, by
+        e, F, H, W, Cin, Cout = _elt(a.dtype), a.F, a.H, a.W, a.Cin, a.Cout
+        by = 1.0 * F * H * W * Cin * e * (2 if a.has('add') else 1) + 1.0 * F * (H // 2) * (W // 2) * Cout * e + 9 * Cout * Cin * e
+        return 2.0 * F * (H // 2) * (W // 2) * Cout * Cin * 9, by, 0.0
     if name == 'rvt_layernorm_fwd':
-        e, rows, C = _elt(a[4]), a[5], a[6]
-        return 0.0, 2.0 * rows * C * e
+        return 0.0, 2.0 * a.rows * a.C * _elt(a.dtype), 0.0
     if name == 'rvt_layernorm_bwd':
-        e, rows, C = _elt(a[7]), a[8], a[9]
-        return 0.0, (3.0 + (1 if P(3) else 0)) * rows * C * e
+        return 0.0, (3.0 + (1 if a.has('dres') else 0)) * a.rows * a.C * _elt(a.dtype), 0.0
     if name == 'rvt_linear_fwd':
-        e, M, N, K = _elt(a[4]), a[5], a[6], a[7]
-        return 2.0 * M * N * K, (1.0 * M * (N + K) + N * K) * e
+        e, M, N, K = _elt(a.dtype), a.M, a.N, a.K
+        return 2.0 * M * N * K, (1.0 * M * (N + K) + N * K) * e, 0.0
     if name == 'rvt_ln_linear_fwd':                      # u = LN(x), y = u w^T + bias
-        e, M, C, N = _elt(a[7]), a[8], a[9], a[10]
-        return 2.0 * M * N * C, (1.0 * M * (C * (2 if P(5) and P(1) else 1) + N) + N * C) * e
+        e, M, C, N = _elt(a.dtype), a.M, a.C, a.N
+        return 2.0 * M * N * C, (1.0 * M * (C * (2 if a.has('u') and a.has('ln_w') else 1) + N) + N * C) * e, 0.0
     if name == 'rvt_linear_gelu_fwd':
-        e, M, N, K = _elt(a[5]), a[6], a[7], a[8]
-        return 2.0 * M * N * K, (1.0 * M * (N * (2 if P(4) else 1) + K) + N * K) * e
+        e, M, N, K = _elt(a.dtype), a.M, a.N, a.K
+        return 2.0 * M * N * K, (1.0 * M * (N * (2 if a.has('gp') else 1) + K) + N * K) * e, 0.0
     if name == 'rvt_linear_scale_res_fwd':
-        e, M, N, K = _elt(a[6]), a[7], a[8], a[9]
-        return 2.0 * M * N * K, (1.0 * M * (2 * N + K) + N * K) * e
+        e, M, N, K = _elt(a.dtype), a.M, a.N, a.K
+        return 2.0 * M * N * K, (1.0 * M * (2 * N + K) + N * K) * e, 0.0
     if name == 'rvt_linear_dgrad':                       # dx[M][K] = dy[M][N] wt[K][N]^T (* gelu' | + add | * mul)
-        e, M, N, K = _elt(a[6]), a[7], a[8], a[9]
-        side = 1 if (P(2) or P(3) or P(4)) else 0
-        return 2.0 * M * N * K, (1.0 * M * (N + K * (1 + side)) + N * K) * e
+        e, M, N, K = _elt(a.dtype), a.M, a.N, a.K
+        side = 1 if (a.has('gelu_pre') or a.has('add') or a.has('mul')) else 0
+        return 2.0 * M * N * K, (1.0 * M * (N + K * (1 + side)) + N * K) * e, 0.0
     if name == 'rvt_linear_dgrad_preln':                 # dy0 = LN'(dy w + add; y0): same rows as the form below with add
-        e, M, C, K = _elt(a[8]), a[9], a[10], a[11]
-        return 2.0 * M * C * K, (1.0 * M * (K + 3 * C) + K * C) * e
+        e, M, C, K = _elt(a.dtype), a.M, a.C, a.K
+        return 2.0 * M * C * K, (1.0 * M * (K + 3 * C) + K * C) * e, 0.0
     if name == 'rvt_linear_dgrad_ln':                    # dx = add + LN'(dy w; x)
-        e, M, C, K = _elt(a[8]), a[9], a[10], a[11]
-        return 2.0 * M * C * K, (1.0 * M * (K + C * (2 + (1 if P(3) else 0))) + K * C) * e
+        e, M, C, K = _elt(a.dtype), a.M, a.C, a.K
+        return 2.0 * M * C * K, (1.0 * M * (K + C * (2 + (1 if a.has('add') else 0))) + K * C) * e, 0.0
     if name == 'rvt_linear_wgrad':
-        e, M, N, K = _elt(a[5]), a[6], a[7], a[8]
-        return 2.0 * M * N * K, 1.0 * M * (N + K) * e + 4.0 * N * K
+        e, M, N, K = _elt(a.dtype), a.M, a.N, a.K
+        return 2.0 * M * N * K, 1.0 * M * (N + K) * e + 4.0 * N * K, 0.0
     if name == 'rvt_mlp_fwd':                            # LN2 -> fc1 -> GELU -> fc2 -> gamma, + residual
-        e, M, C = _elt(a[12]), a[13], a[14]
-        rows = 2 + ((8 if P(3) else 4) if P(2) else 0) + (1 if P(4) else 0)        # (g_out alone = the pre-activation only)
-        return 16.0 * M * C * C, (1.0 * rows * M * C + 8 * C * C) * e
+        e, M, C = _elt(a.dtype), a.M, a.C
+        rows = 2 + ((8 if a.has('gp_out') else 4) if a.has('g_out') else 0) + (1 if a.has('v2_out') else 0)        # (g_out alone = the pre-activation only)
+        return 16.0 * M * C * C, (1.0 * rows * M * C + 8 * C * C) * e, 0.0
     if name == 'rvt_mlp_bwd_dgrad':                      # fc2 dgrad * gp -> dh (stored) -> fc1 dgrad -> LN2' + residual
-        e, M, C = _elt(a[10]), a[11], a[12]
-        return 16.0 * M * C * C, (11.0 * M * C + 8 * C * C) * e
-    if name == 'rvt_mlp_bwd_recompute_dgrad':            # both input gradients (16); executed: + recompute of fc1 (8)
-        e, M, C = _elt(a[11]), a[12], a[13]
-        return 16.0 * M * C * C, (3.0 * M * C + 12 * C * C) * e
-    if name == 'rvt_mlp_bwd_recompute_wgrad':            # both weight gradients (16); executed: + recompute of fc1 (8) + fc2 dgrad for dh (8)
-        e, M, C = _elt(a[12]), a[13], a[14]
-        return 16.0 * M * C * C, 2.0 * M * C * e + 8.0 * C * C * (e + 4)
-    if name == 'rvt_mlp_bwd_recompute_both':             # input + weight gradients (32); executed: + recompute of fc1 (8)
-        e, M, C = _elt(a[16]), a[17], a[18]
-        return 32.0 * M * C * C, 3.0 * M * C * e + 8.0 * C * C * (e + 4)
-    if name == 'rvt_attn_fwd':
-        e, F, H, W, C, dh, ph, pw = _elt(a[2]), *a[3:10]
-        M, L = F * H * W, ph * pw
-        return 4.0 * M * L * C, 4.0 * M * C * e
-    if name == 'rvt_attn_bwd':                           # dV, dP, dQ, dK (8 L C); executed: + recompute of S (2)
-        e, F, H, W, C, dh, ph, pw = _elt(a[3]), *a[4:11]
-        M, L = F * H * W, ph * pw
-        return 8.0 * M * L * C, 7.0 * M * C * e
-    if name == 'rvt_attn_block_fwd':                     # LN1 -> qkv (6C^2) -> attention (4LC) -> proj (2C^2) -> gamma + residual
-        e, F, H, W, C, dh, ph, pw = _elt(a[10]), *a[11:18]
-        M, L = F * H * W, ph * pw
-        return M * (8.0 * C * C + 4.0 * L * C), ((2.0 + (1 if P(2) else 0)) * M * C + 4 * C * C) * e
-    if name == 'rvt_attn_block_bwd':                     # dproj (2C^2), core (8LC), du (6C^2); executed: + recompute of qkv (6C^2) + S (2LC)
-        e, F, H, W, C, dh, ph, pw = _elt(a[12]), *a[13:20]
-        M, L = F * H * W, ph * pw
-        return M * (8.0 * C * C + 8.0 * L * C), ((6.0 + (1 if P(4) else 0)) * M * C + 7 * C * C) * e
-    if name == 'rvt_attn_block_bwd_preln':               # the same products; rows: x, y0, dxmid in, dy0 + dqkv (3) out
-        e, F, H, W, C, dh, ph, pw = _elt(a[11]), *a[12:19]
-        M, L = F * H * W, ph * pw
-        return M * (8.0 * C * C + 8.0 * L * C), (7.0 * M * C + 7 * C * C) * e
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 16.0 * M * C * C, (11.0 * M * C + 8 * C * C) * e, 0.0
+    if name == 'rvt_mlp_bwd_recompute_dgrad':            # both input gradients (16); recompute of fc1 (8)
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 16.0 * M * C * C, (3.0 * M * C + 12 * C * C) * e, 8.0 * M * C * C
+    if name == 'rvt_mlp_bwd_recompute_wgrad':            # both weight gradients (16); recompute of fc1 (8) + fc2 dgrad for dh (8)
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 16.0 * M * C * C, 2.0 * M * C * e + 8.0 * C * C * (e + 4), 16.0 * M * C * C
+    if name == 'rvt_mlp_bwd_recompute_both':             # input + weight gradients (32); recompute of fc1 (8)
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 32.0 * M * C * C, 3.0 * M * C * e + 8.0 * C * C * (e + 4), 8.0 * M * C * C
+    if name in ('rvt_attn_fwd', 'rvt_attn_bwd', 'rvt_attn_block_fwd', 'rvt_attn_block_bwd', 'rvt_attn_block_bwd_preln'):
+        e, F, H, W, C, L = _elt(a.dtype), a.F, a.H, a.W, a.C, a.ph * a.pw
+        M = F * H * W                                    # (the recompute terms below keep the parent formulas' own spelling, F * H * W * ph * pw:
+                                                         #  the same product in another order can differ in the last bit)
+        if name == 'rvt_attn_fwd':
+            return 4.0 * M * L * C, 4.0 * M * C * e, 0.0
+        if name == 'rvt_attn_bwd':                       # dV, dP, dQ, dK (8 L C); recompute of S (2)
+            return 8.0 * M * L * C, 7.0 * M * C * e, 2.0 * F * H * W * a.ph * a.pw * C
+        if name == 'rvt_attn_block_fwd':                 # LN1 -> qkv (6C^2) -> attention (4LC) -> proj (2C^2) -> gamma + residual
+            return M * (8.0 * C * C + 4.0 * L * C), ((2.0 + (1 if a.has('a_out') else 0)) * M * C + 4 * C * C) * e, 0.0
+        recompute = F * H * W * (6.0 * C * C + 2.0 * a.ph * a.pw * C)             # of qkv (6C^2) + S (2LC)
+        if name == 'rvt_attn_block_bwd':                 # dproj (2C^2), core (8LC), du (6C^2)
+            return M * (8.0 * C * C + 8.0 * L * C), ((6.0 + (1 if a.has('u_out') else 0)) * M * C + 7 * C * C) * e, recompute
+        return M * (8.0 * C * C + 8.0 * L * C), (7.0 * M * C + 7 * C * C) * e, recompute      # _preln: the same products; rows: x, y0, dxmid in, dy0 + dqkv (3) out
     if name == 'rvt_lstm_fwd':
-        e, M, C = _elt(a[8]), a[9], a[10]
-        return 16.0 * M * C * C, 1.0 * M * C * (3 * e + 8 + (4 * e if P(7) else 0)) + 8.0 * C * C * e
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 16.0 * M * C * C, 1.0 * M * C * (3 * e + 8 + (4 * e if a.has('gates') else 0)) + 8.0 * C * C * e, 0.0
     if name == 'rvt_lstm_gates_bwd':
-        e, M, C = _elt(a[7]), a[8], a[9]
-        return 0.0, 1.0 * M * C * ((1 + (1 if P(1) else 0) + 8) * e + 16)
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 0.0, 1.0 * M * C * ((1 + (1 if a.has('dh_rec') else 0) + 8) * e + 16), 0.0
     if name == 'rvt_lstm_dgrad':
-        e, M, C = _elt(a[4]), a[5], a[6]
-        return 16.0 * M * C * C, (6.0 * M * C + 8 * C * C) * e
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 16.0 * M * C * C, (6.0 * M * C + 8 * C * C) * e, 0.0
     if name == 'rvt_lstm_wgrad':
-        e, M, C = _elt(a[6]), a[7], a[8]
-        return 16.0 * M * C * C, 6.0 * M * C * e + 32.0 * C * C
+        e, M, C = _elt(a.dtype), a.M, a.C
+        return 16.0 * M * C * C, 6.0 * M * C * e + 32.0 * C * C, 0.0
     if name == 'rvt_lstm_scan_fwd':                      # per token-step: x in, h out (+ c copy, + gates) — h / c stay on chip
-        e, M, C, T = _elt(a[8]), a[9], a[10], a[11]
-        rows = 2 + (1 if P(4) else 0) + (4 if P(7) else 0)
-        return 16.0 * M * C * C * T, 1.0 * rows * M * C * T * e + 8.0 * M * C + 8 * C * C * e
+        e, M, C, T = _elt(a.dtype), a.M, a.C, a.T_steps
+        rows = 2 + (1 if a.has('Csave') else 0) + (4 if a.has('gates_out') else 0)
+        return 16.0 * M * C * C * T, 1.0 * rows * M * C * T * e + 8.0 * M * C + 8 * C * C * e, 0.0
     if name == 'rvt_lstm_scan_bwd':
-        e, M, C, T = _elt(a[17]), a[18], a[19], a[20]
-        saved_gates, wgrad, dz = P(16), P(13), P(10)
-        fl = 16.0 + (16.0 if wgrad else 0.0)                                 # dgrad (+ in-kernel weight gradient); executed: + gate recompute (16) unless the gates were saved
-        rows = (2 + 4 if saved_gates else 4) + 1 + (4 if dz else 0)          # (c, dH, gates | x, h, c, dH) in, dx out (+ dz out)
-        return fl * M * C * C * T, 1.0 * rows * M * C * T * e + 16.0 * M * C + 16 * C * C * e
+        e, M, C, T = _elt(a.dtype), a.M, a.C, a.T_steps
+        saved_gates = a.has('gates')
+        fl = 16.0 + (16.0 if a.has('dw') else 0.0)                           # dgrad (+ in-kernel weight gradient)
+        rows = (2 + 4 if saved_gates else 4) + 1 + (4 if a.has('dz_all') else 0)        # (c, dH, gates | x, h, c, dH) in, dx out (+ dz out)
+        return (fl * M * C * C * T, 1.0 * rows * M * C * T * e + 16.0 * M * C + 16 * C * C * e,
+                0.0 if saved_gates else 16.0 * M * C * C * T)                           # gate recompute (16) unless the gates were saved
     if name == 'rvt_lstm_scan3_fwd':                     # wide stages: x in, h out (+ bf16 c copy + 4 activated gates when saving); weights once
-        e, M, C, T = _elt(a[8]), a[9], a[10], a[11]
-        rows = 2 + (5 if P(7) else 0)
-        return 16.0 * M * C * C * T, 1.0 * rows * M * C * T * e + 8.0 * M * C + 8 * C * C * e
+        e, M, C, T = _elt(a.dtype), a.M, a.C, a.T_steps
+        rows = 2 + (5 if a.has('gsave') else 0)
+        return 16.0 * M * C * C * T, 1.0 * rows * M * C * T * e + 8.0 * M * C + 8 * C * C * e, 0.0
     if name == 'rvt_lstm_scan3_bwd':                     # gates (4) + c + dH in, dz (4) + dx out; W^T once
-        e, M, C, T = _elt(a[10]), a[11], a[12], a[13]
-        rows = 4 + 1 + (1 if P(3) else 0) + 4 + 1
-        return 16.0 * M * C * C * T, 1.0 * rows * M * C * T * e + 16.0 * M * C + 8 * C * C * e
+        e, M, C, T = _elt(a.dtype), a.M, a.C, a.T_steps
+        rows = 4 + 1 + (1 if a.has('dH') else 0) + 4 + 1
+        return 16.0 * M * C * C * T, 1.0 * rows * M * C * T * e + 16.0 * M * C + 8 * C * C * e, 0.0
     if name == 'rvt_lstm_scan3_pack':
-        C = a[3]
-        return 0.0, 8.0 * C * C * 2 * (1 + (1 if P(1) else 0) + (1 if P(2) else 0))
-    if name == 'rvt_dwconv_fwd':
-        e, N, H, W, C, k = _elt(a[6]), *a[7:12]
-        return 0.0, 2.0 * N * H * W * C * e
-    if name == 'rvt_dwconv_wgrad':
-        e, N, H, W, C, k = _elt(a[6]), *a[7:12]
-        return 0.0, 2.0 * N * H * W * C * e
+        return 0.0, 8.0 * a.C * a.C * 2 * (1 + (1 if a.has('wp_fwd') else 0) + (1 if a.has('wtp_bwd') else 0)), 0.0
+    if name in ('rvt_dwconv_fwd', 'rvt_dwconv_wgrad'):
+        return 0.0, 2.0 * a.N * a.H * a.W * a.C * _elt(a.dtype), 0.0
     if name in ('rvt_token_mask_fwd', 'rvt_token_mask_bwd'):
-        e, M, C = _elt(a[3]), a[4], a[5]
-        return 0.0, 1.0 * M * C * e
+        return 0.0, 1.0 * a.M * a.C * _elt(a.dtype), 0.0
     # ---- detection tail (rows f2 / f3): BatchNorm + SiLU row kernels around the PAFPN / head convolutions, decode, SimOTA + losses
     if name == 'rvt_bn_stats':                                   # one read of the conv output
-        e, rows, C = _elt(a[2]), a[3], a[4]
-        return 0.0, 1.0 * rows * C * e
+        return 0.0, 1.0 * a.rows * a.C * _elt(a.dtype), 0.0
     if name == 'rvt_bn_act_fwd':                                 # read + write
-        e, rows, C = _elt(a[4]), a[5], a[6]
-        return 0.0, 2.0 * rows * C * e
+        return 0.0, 2.0 * a.rows * a.C * _elt(a.dtype), 0.0
     if name == 'rvt_bn_act_bwd_stats':                           # dy and x in
-        e, rows, C = _elt(a[8]), a[9], a[10]
-        return 0.0, 2.0 * rows * C * e
+        return 0.0, 2.0 * a.rows * a.C * _elt(a.dtype), 0.0
     if name == 'rvt_bn_act_bwd_apply':                           # dy and x in, dx out
-        e, rows, C = _elt(a[9]), a[10], a[11]
-        return 0.0, 3.0 * rows * C * e
+        return 0.0, 3.0 * a.rows * a.C * _elt(a.dtype), 0.0
     if name == 'rvt_bn_finalize':
-        return 0.0, 48.0 * a[12]                                 # two fp64 sums in; running statistics, four fp32 vectors out
+        return 0.0, 48.0 * a.C, 0.0                              # two fp64 sums in; running statistics, four fp32 vectors out
     if name in ('rvt_yolox_decode', 'rvt_yolox_decode_bwd'):     # the level's two prediction maps <-> [B][A][5+nc] fp32 rows
-        o = 2 if name == 'rvt_yolox_decode' else 5
-        ld_ro, ld_cls, e, B, H, W, _st, nc = a[o], a[o + 1], _elt(a[o + 2]), *a[o + 3:o + 8]
-        outs = (1 if P(12) else 0) + (1 if P(13) else 0) if name == 'rvt_yolox_decode' else 2
-        return 0.0, 1.0 * B * H * W * ((ld_ro + ld_cls) * e + outs * (5 + nc) * 4)
+        outs = (1 if a.has('pred_train') else 0) + (1 if a.has('pred_infer') else 0) if name == 'rvt_yolox_decode' else 2
+        return 0.0, 1.0 * a.B * a.H * a.W * ((a.ld_ro + a.ld_cls) * _elt(a.dtype) + outs * (5 + a.num_classes) * 4), 0.0
     if name == 'rvt_simota_loss':                                # pred in (cost, select/resolve, loss passes), cost + IoU matrices out and back
-        L_, B, G, A, nc = a[4:9]
-        return 0.0, 3.0 * B * A * (5 + nc) * 4 + (B * A * (5 + nc) * 4 if P(10) else 0) + 4.0 * B * G * A * 4 + 6.0 * B * A * 4
+        B, G, A, nc = a.B, a.G, a.A, a.num_classes
+        return 0.0, 3.0 * B * A * (5 + nc) * 4 + (B * A * (5 + nc) * 4 if a.has('g_pred') else 0) + 4.0 * B * G * A * 4 + 6.0 * B * A * 4, 0.0
+    # post-processing: the executed figure is vector (not MFMA) work, data dependent: the all-pairs bound of the greedy NMS, 12 flops
+    # per IoU test (4 min/max, 3 sub, 2 max, mul, add, div)
     if name == 'rvt_yolox_postprocess':                          # pred in, det / count / anchor_idx out, the workspace written and read back
-        B, A, nc, max_det = a[1], a[2], a[3], a[7]
-        return 0.0, 1.0 * B * A * (5 + nc) * 4 + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if P(10) else 0) + 2.0 * 52 * B * A
+        B, A, nc, max_det = a.B, a.A, a.num_classes, a.max_det
+        by = 1.0 * B * A * (5 + nc) * 4 + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if a.has('anchor_idx') else 0) + 2.0 * 52 * B * A
+        return 0.0, by, 12.0 * B * A * (A - 1) / 2
     if name == 'rvt_yolox_detect':                               # the levels' maps read once (A rows per image over all levels), det / count /
-        ld_ro, ld_cls, e, B, A, max_det = a[2], a[3], _elt(a[4]), a[8], a[9], a[14]          # anchor_idx out, the workspace written and read back
-        return 0.0, 1.0 * B * A * (ld_ro + ld_cls) * e + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if P(17) else 0) + 2.0 * 52 * B * A
+        B, A, nc, max_det = a.B, a.A, a.num_classes, a.max_det   # anchor_idx out, the workspace written and read back
+        by = (1.0 * B * A * (a.ld_ro + a.ld_cls) * _elt(a.dtype) + B * max_det * 7 * 4 + B * 4 + (B * max_det * 4 if a.has('anchor_idx') else 0)
+              + 2.0 * 52 * B * A)
+        return 0.0, by, 12.0 * B * A * (A - 1) / 2 + 3.0 * B * A * (1 + nc)      # + one sigmoid (exp, add, divide: 3) per class and objectness logit
     if name == 'rvt_augment_planes':                             # uint8 planes in and out; the per-sample windows live in the device table,
-        F, B, C, H, W = a[3:8]                                   # so this is the bound of a flip: every byte read once, written once
-        return 0.0, 2.0 * F * C * H * W + 32.0 * B
+        return 0.0, 2.0 * a.F * a.C * a.H * a.W + 32.0 * a.B, 0.0          # so this is the bound of a flip: every byte read once, written once
     if name == 'rvt_augment_labels':                             # rows + count in, rows + count (+ yolox) out
-        F, B, G = a[3:6]
-        return 0.0, 2.0 * F * (G * 7 * 4 + 4) + (F * G * 5 * 4 if P(8) else 0) + 48.0 * B
+        F, B, G = a.F, a.B, a.G
+        return 0.0, 2.0 * F * (G * 7 * 4 + 4) + (F * G * 5 * 4 if a.has('yolox_out') else 0) + 48.0 * B, 0.0
     if name == 'rvt_coco_match':                                 # det + count, label rows + count, timestamps in; the frame's record slots out
-        F, max_det, G, nc, stride = a[5], a[6], a[7], a[8], a[16]
-        return 0.0, 1.0 * F * (max_det * 7 * 4 + 4 + G * 7 * 4 + 4 + 8) + 24.0 * F * stride + 80.0
+        F, max_det, G = a.F, a.max_det, a.G
+        return 0.0, 1.0 * F * (max_det * 7 * 4 + 4 + G * 7 * 4 + 4 + 8) + 24.0 * F * a.rec_stride + 80.0, 0.0
     if name == 'rvt_coco_accumulate':                            # permutation + the two mask planes read twice (count, emit); table out
-        n, nc = a[3], a[4]
-        return 0.0, 2.0 * 24 * n + 10 * 101 * nc * 4 * 8.0
+        return 0.0, 2.0 * 24 * a.n_slots + 10 * 101 * a.num_classes * 4 * 8.0, 0.0
     return None
+
+
+def model(name: str, args) -> Optional[Tuple[float, float]]:
+    """(flops, bytes) of one launch from its positional arguments as `_lib.call` sees them, or None for an entry point with no model
+    (host-side tables, size queries)."""
+    m = _price(name, LaunchArgs(name, args))
+    return None if m is None else m[:2]
 
 
 def augment_planes_bytes(F: int, C: int, H: int, W: int, windows) -> float:
@@ -223,39 +214,11 @@ def augment_planes_bytes(F: int, C: int, H: int, W: int, windows) -> float:
     return total
 
 
-def executed(name: str, a) -> Optional[float]:
+def executed(name: str, args) -> Optional[float]:
     """MFMA-side FLOPs the launch actually EXECUTES: model()'s algorithmic figure plus the products a recompute-style backward
     re-does by design.  Equal to the algorithmic figure for every other entry point."""
-    m = model(name, a)
-    if m is None:
-        return None
-    fl = m[0]
-    P = lambda i: a[i] is not None
-    if name == 'rvt_mlp_bwd_recompute_dgrad':
-        return fl + 8.0 * a[12] * a[13] * a[13]
-    if name == 'rvt_mlp_bwd_recompute_wgrad':
-        return fl + 16.0 * a[13] * a[14] * a[14]
-    if name == 'rvt_mlp_bwd_recompute_both':
-        return fl + 8.0 * a[17] * a[18] * a[18]
-    if name == 'rvt_attn_bwd':
-        F, H, W, C, dh, ph, pw = a[4:11]
-        return fl + 2.0 * F * H * W * ph * pw * C
-    if name == 'rvt_attn_block_bwd':
-        F, H, W, C, dh, ph, pw = a[13:20]
-        return fl + F * H * W * (6.0 * C * C + 2.0 * ph * pw * C)
-    if name == 'rvt_attn_block_bwd_preln':
-        F, H, W, C, dh, ph, pw = a[12:19]
-        return fl + F * H * W * (6.0 * C * C + 2.0 * ph * pw * C)
-    if name == 'rvt_yolox_postprocess':                          # vector (not MFMA) work, data dependent: the all-pairs bound of the greedy
-        B, A = a[1], a[2]                                        # NMS, 12 flops per IoU test (4 min/max, 3 sub, 2 max, mul, add, div)
-        return 12.0 * B * A * (A - 1) / 2
-    if name == 'rvt_yolox_detect':                               # the same NMS bound, plus one sigmoid (exp, add, divide: 3) per class and
-        B, A, nc = a[8], a[9], a[10]                             # objectness logit of every anchor
-        return 12.0 * B * A * (A - 1) / 2 + 3.0 * B * A * (1 + nc)
-    if name == 'rvt_lstm_scan_bwd' and not P(16):
-        M, C, T = a[18], a[19], a[20]
-        return fl + 16.0 * M * C * C * T
-    return fl
+    m = _price(name, LaunchArgs(name, args))
+    return None if m is None else m[0] + m[2]
 
 
 def roofline_entry(name: str, flops: float, bytes_: float, ms: float, launches: int, dtype: str, mfma_peak_tflops: float = None,

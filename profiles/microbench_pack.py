@@ -30,10 +30,9 @@ for kind in range(7):
     rows = [r for r in tab.rows if r['kind'] == kind]
     if not rows:
         continue
-    sub = Wt._Table(Wt.PACK_DT, 1024)
+    sub = Wt.pack_table()
     for r in rows:
-        f = {k: v for k, v in r.items() if k != 'block0'}
-        sub.add((int(f['n']) + 1023) // 1024, **f)
+        sub.add((int(r['n']) + Wt.PACK_BLOCK - 1) // Wt.PACK_BLOCK, **r)          # (add renumbers block0)
     sub.upload(dev)
     t = timeit(lambda: L.call('rvt_pack_table', L.ptr(sub.dev), len(sub), sub.blocks, L.dtype_code(torch.bfloat16), L.stream_of(mw.bufT)))
     print(f'  {names[kind]:<15} {len(rows):4d} descriptors {sum(int(r["n"]) for r in rows) / 1e6:8.2f} M elements {t:8.1f} us')

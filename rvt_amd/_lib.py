@@ -1,5 +1,5 @@
 """ctypes binding of librvt_hip.so — the only compute path of this package.  Every type in it is derived from
-include/rvt_hip.h (rvt_amd/_header.py); nothing here restates a prototype or a struct.
+include/rvt_hip.h (rvt_amd/_header.py); nothing here restates a prototype, a struct, a table row or an enumerator.
 
 There is no PyTorch / CPU fallback: if the gfx950 library or a GPU is missing, every op raises.
 The unit tests may install the CPU SIMT-emulator build of the same kernel sources through
@@ -11,14 +11,15 @@ import ctypes
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 
-from ._header import SIGS as _SIGS, bind as _bind        # name -> argument types; types onto a loaded library
+from ._header import ENUMS, SIGS as _SIGS, STRUCTS as _STRUCTS, bind as _bind     # enumerators; name -> argument types; structs; types onto a loaded library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RVT_HIP_LIB') or os.path.join(_HERE, 'librvt_hip.so')   # env: another BUILD of the same library
 
-RVT_F32, RVT_BF16 = 0, 1
+RVT_F32, RVT_BF16 = ENUMS['RVT_F32'], ENUMS['RVT_BF16']
 _DT = {torch.float32: RVT_F32, torch.bfloat16: RVT_BF16}
 
 _lib: Optional[ctypes.CDLL] = None
@@ -131,3 +132,42 @@ def workspace(kind: str, like: torch.Tensor, n: int, dtype: torch.dtype, floor: 
     if ws is None or ws.numel() < n:
         ws = _WS[key] = torch.empty(max(n, floor), dtype=dtype, device=dev)
     return st, ws
+
+
+def row_dtype(struct: str) -> np.dtype:
+    """numpy dtype of one of the header's table rows: the C struct's field names, offsets and size."""
+    return np.dtype(_STRUCTS[struct])
+
+
+class DeviceTable:
+    """Host-built array of one of the header's row structs -> device bytes (one launch walks it).  Filled row by row (`add`) or
+    from a whole array of the struct's dtype (`upload(device, arr)`)."""
+
+    def __init__(self, struct: str):
+        self.dtype = row_dtype(struct)
+        self.rows = []                              # {field: value} per row; the array itself after upload(device, arr)
+        self.blocks = 0                             # blocks owned by the rows so far = block0 of the next one
+        self.dev: Optional[torch.Tensor] = None
+
+    def add(self, nblocks: int = 0, **fields) -> None:
+        """One row by field name.  A struct with a block0 field: the row owns nblocks blocks of the launch behind those before it."""
+        if 'block0' in self.dtype.names:
+            fields['block0'] = self.blocks
+        self.rows.append(fields)
+        self.blocks += nblocks
+
+    def upload(self, device, arr: Optional[np.ndarray] = None) -> 'DeviceTable':
+        if arr is None:
+            arr = np.zeros(len(self.rows), dtype=self.dtype)
+            for i, r in enumerate(self.rows):
+                for k, v in r.items():
+                    arr[i][k] = v                   # (a field the struct does not have raises)
+        elif arr.dtype != self.dtype:
+            raise TypeError(f'table rows of dtype {arr.dtype}, the header says {self.dtype}')
+        else:
+            self.rows = arr
+        self.dev = torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(device)
+        return self
+
+    def __len__(self):
+        return len(self.rows)

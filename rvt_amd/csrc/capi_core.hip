@@ -208,18 +208,20 @@ int rvt_stacked_histogram(const long long* x, const long long* y, const long lon
 }
 
 // ------------------------------------------------------------------------------ parameter-side tables
-int rvt_pack_table(const void* descs, int n_desc, int total_blocks, int dtype, void* stream) {
+int rvt_pack_table(const RvtPackDesc* descs, int n_desc, int total_blocks, int dtype, void* stream) {
     RVT_CHECK(n_desc >= 1 && total_blocks >= 1 && descs != nullptr, "pack_table: empty table");
     hipStream_t st = (hipStream_t)stream;
+    // (PackDesc / LayerScaleDesc add nothing to the header's rows - same size, asserted in pack.hpp - and exist only for the kernels'
+    //  symbol names: the downcast re-labels device memory that the host never dereferences)
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((pack_table_kernel<T>), dim3((total_blocks + PACK_LBPW - 1) / PACK_LBPW), dim3(256), 0, st,
-                                             (const PackDesc*)descs, n_desc, (unsigned)total_blocks));
+                                             static_cast<const PackDesc*>(descs), n_desc, (unsigned)total_blocks));
     return check_launch("pack_table");
 }
 
-int rvt_layerscale_grad_table(const void* descs, int n_desc, int total_blocks, void* stream) {
+int rvt_layerscale_grad_table(const RvtLayerScaleDesc* descs, int n_desc, int total_blocks, void* stream) {
     RVT_CHECK(n_desc >= 1 && total_blocks >= 1 && descs != nullptr, "layerscale_grad_table: empty table");
     hipLaunchKernelGGL(layerscale_grad_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const LayerScaleDesc*)descs, n_desc);
+                       static_cast<const LayerScaleDesc*>(descs), n_desc);
     return check_launch("layerscale_grad_table");
 }
 

@@ -9,7 +9,7 @@
 
 using namespace rvt;
 
-static_assert(sizeof(EvStream) == 48, "stream table row is 48 bytes (include/rvt_hip.h)");
+static_assert(sizeof(EvStream) == 48 && sizeof(EvStream) == sizeof(RvtEventStream), "stream table row is 48 bytes (include/rvt_hip.h)");
 
 // planes of one window: polarity x bins for the stacked histogram, bins for the mixed-density stack
 static size_t evseq_planes(int bins, int rep) { return (size_t)(rep == EVSEQ_MIXED ? 1 : 2) * bins; }
@@ -34,7 +34,7 @@ static void evseq_launch_count(dim3 grid, hipStream_t st, int coord_bytes, const
 
 // what the two sequence entries share: the argument checks (the cutoff is the entry's own), one bounds launch, then the windows in
 // chunks of windows_in_flight with one count and one narrowing launch each
-static int evseq_run(const char* what, int rep, const void* streams, int B, int T, int coord_bytes, long long window_us,
+static int evseq_run(const char* what, int rep, const RvtEventStream* streams, int B, int T, int coord_bytes, long long window_us,
                      long long window_events, int bins, int H, int W, int downsample_by_2, int count_cutoff, int fastmode, long long* bounds,
                      void* scratch, int windows_in_flight, int count_blocks, void* out, void* stream) {
     RVT_CHECK(streams && bounds && scratch && out, "%s: null argument", what);
@@ -53,7 +53,9 @@ static int evseq_run(const char* what, int rep, const void* streams, int B, int 
     const size_t cells = evseq_planes(bins, rep) * plane;
     const size_t slot = evseq_slot_cells(bins, H, W, ds, rep);
     hipStream_t st = (hipStream_t)stream;
-    const EvStream* table = (const EvStream*)streams;
+    // (EvStream adds nothing to RvtEventStream - same size, asserted above - and exists only for the kernels' symbol names: the downcast
+    //  re-labels device memory that the host never dereferences)
+    const EvStream* table = static_cast<const EvStream*>(streams);
     const int windows = B * T;
 
     hipLaunchKernelGGL(evseq_bounds_kernel, dim3((windows + EVSEQ_THREADS - 1) / EVSEQ_THREADS), dim3(EVSEQ_THREADS), 0, st, table, B, T,
@@ -86,7 +88,7 @@ size_t rvt_event_sequence_ws_bytes(int bins, int H, int W, int downsample_by_2, 
     return evseq_slot_cells(bins, H, W, downsample_by_2, EVSEQ_HIST) * sizeof(unsigned) * (size_t)windows_in_flight;
 }
 
-int rvt_event_sequence(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
+int rvt_event_sequence(const RvtEventStream* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
                        int H, int W, int downsample_by_2, int count_cutoff, int fastmode, long long* bounds, void* scratch,
                        int windows_in_flight, int count_blocks, unsigned char* out, void* stream) {
     RVT_CHECK(count_cutoff >= 1 && count_cutoff <= 255, "event_sequence: count_cutoff=%d outside 1..255", count_cutoff);
@@ -99,7 +101,7 @@ size_t rvt_event_sequence_mixed_ws_bytes(int bins, int H, int W, int downsample_
     return evseq_slot_cells(bins, H, W, downsample_by_2, EVSEQ_MIXED) * sizeof(int) * (size_t)windows_in_flight;
 }
 
-int rvt_event_sequence_mixed(const void* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
+int rvt_event_sequence_mixed(const RvtEventStream* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
                              int H, int W, int downsample_by_2, int count_cutoff, long long* bounds, void* scratch,
                              int windows_in_flight, int count_blocks, signed char* out, void* stream) {
     RVT_CHECK(count_cutoff <= 127, "event_sequence_mixed: count_cutoff=%d above 127 (negative = none)", count_cutoff);

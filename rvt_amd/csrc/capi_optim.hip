@@ -10,7 +10,7 @@ using namespace rvt;
 
 extern "C" {
 
-int rvt_optim_step(const void* chunks, int n_chunks, const void* groups, int n_groups, long long* step, int max_blocks, void* stream) {
+int rvt_optim_step(const RvtOptimChunk* chunks, int n_chunks, const RvtOptimGroup* groups, int n_groups, long long* step, int max_blocks, void* stream) {
     RVT_CHECK(chunks && groups && step, "optim_step: null argument");
     RVT_CHECK(n_chunks >= 1 && n_groups >= 1, "optim_step: n_chunks=%d n_groups=%d must be positive", n_chunks, n_groups);
     RVT_CHECK(max_blocks >= 0, "optim_step: max_blocks=%d is negative", max_blocks);
@@ -18,8 +18,10 @@ int rvt_optim_step(const void* chunks, int n_chunks, const void* groups, int n_g
               "optim_step: tables and step count must be 8-byte aligned");
     const int cap = max_blocks > 0 ? imin(max_blocks, OPTIM_MAX_GRID) : OPTIM_MAX_GRID;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(optim_step_kernel, dim3((unsigned)imin(n_chunks, cap)), dim3(OPTIM_THREADS), 0, st, (const OptimChunk*)chunks,
-                       n_chunks, (const OptimGroup*)groups, n_groups, (const long long*)step);
+    // (OptimChunk / OptimGroup add nothing to the header's rows - same size, asserted in optim.hpp - and exist only for the kernel's
+    //  symbol name: the downcast re-labels device memory that the host never dereferences)
+    hipLaunchKernelGGL(optim_step_kernel, dim3((unsigned)imin(n_chunks, cap)), dim3(OPTIM_THREADS), 0, st, static_cast<const OptimChunk*>(chunks),
+                       n_chunks, static_cast<const OptimGroup*>(groups), n_groups, (const long long*)step);
     RVT_TRY(check_launch("optim_step"));
     hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, st, step);
     return check_launch("optim_step (advance)");

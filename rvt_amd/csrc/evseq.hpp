@@ -33,15 +33,8 @@
 
 namespace rvt {
 
-// One row of the stream table (include/rvt_hip.h: 48 bytes, 8-byte aligned, in DEVICE memory).
-struct EvStream {
-    const void* x;
-    const void* y;
-    const void* p;
-    const long long* t;
-    long long n;
-    const long long* ts_end;
-};
+// One row of the stream table, declared in include/rvt_hip.h; the empty derived struct keeps the kernels' symbol names.
+struct EvStream : RvtEventStream {};
 
 typedef __attribute__((ext_vector_type(2))) long long i64x2;
 typedef __attribute__((ext_vector_type(4))) int i32x4;

@@ -3,7 +3,7 @@
 // OneCycleLR, linear, cycle_momentum=False), train.py (gradient_clip_val by VALUE), i.e. per step and parameter
 //     clip_grad_value_(g, clip);  AdamW without amsgrad (decoupled weight decay);  scheduler.step()
 //
-// Two device tables the host builds once (host mirror rvt_amd/optim.py):
+// Two device tables the host builds once (rows declared in include/rvt_hip.h; built by rvt_amd/optim.py):
 //   chunks: one OptimChunk per piece of at most OPTIM_CHUNK consecutive elements of one parameter (a tensor shorter than that is one
 //           entry), naming the piece of the parameter, its gradient and its two moments, and the parameter group it belongs to;
 //   groups: one OptimGroup per parameter group, all double like the Python floats torch keeps them in.
@@ -30,27 +30,14 @@
 namespace rvt {
 
 constexpr int OPTIM_THREADS = 256;
-constexpr int OPTIM_CHUNK = 4096;                     // elements per table entry: 4 float4 per lane
+constexpr int OPTIM_CHUNK = RVT_OPTIM_CHUNK_ELEMS;    // elements per table entry: 4 float4 per lane
 constexpr int OPTIM_MAX_GRID = 2048;                  // 256 CUs x 8 workgroups; the chunks beyond are walked grid-stride
 
-struct OptimChunk {           // 40 bytes; mirrored by rvt_amd/optim.py (numpy structured dtype)
-    float* p;
-    const float* g;
-    float* m;                 // exp_avg
-    float* v;                 // exp_avg_sq
-    int n;                    // 1 .. OPTIM_CHUNK elements
-    int group;
-};
-static_assert(sizeof(OptimChunk) == 40, "OptimChunk layout is part of the C ABI");
-
-struct OptimGroup {           // 80 bytes
-    double beta1, beta2, eps, weight_decay;
-    double clip;              // < 0: no clipping
-    double lr_init, lr_max, lr_final;
-    double warm_end;          // end of the first phase as a schedule position: float(pct_start * total_steps) - 1, may be fractional
-    double last;              // last position of the schedule: total_steps - 1.  No schedule: lr_init = lr_max = lr_final, 0, 0
-};
-static_assert(sizeof(OptimGroup) == 80, "OptimGroup layout is part of the C ABI");
+// the rows are declared in include/rvt_hip.h; the empty derived structs keep the kernel's symbol name
+struct OptimChunk : RvtOptimChunk {};
+static_assert(sizeof(OptimChunk) == 40 && sizeof(OptimChunk) == sizeof(RvtOptimChunk), "OptimChunk layout is part of the C ABI");
+struct OptimGroup : RvtOptimGroup {};
+static_assert(sizeof(OptimGroup) == 80 && sizeof(OptimGroup) == sizeof(RvtOptimGroup), "OptimGroup layout is part of the C ABI");
 
 struct OptimScalars { float clip, decay, w1, beta2, w2, step, bc2s, eps; };
 

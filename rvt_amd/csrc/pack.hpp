@@ -9,43 +9,24 @@
 
 namespace rvt {
 
-// element-wise gather from one fp32 source into one destination
-enum PackKind {
-    PACK_COPY = 0,           // dst[i] = src[i]
-    PACK_TRANSPOSE = 1,      // src [R][K] -> dst [K][R], optionally * scale[r]      (d0 = R, d1 = K)
-    PACK_CONV_FWD = 2,       // src [Cout][Cin][k][k] -> dst [Cout][k*k*cp] tap-major, cin fastest, zero padded (d0..d3 = Cout,Cin,k,cp)
-    PACK_CONV_DGRAD = 3,     // src [Cout][Cin][k][k] -> dst [Cin][nky*nkx*Cout] of one stride-parity class (d0..d4 = Cout,Cin,k,nky,nkx)
-    PACK_LSTM_ROWS = 4,      // src [4C][K] -> dst rows interleaved n' = (c/8)*32 + gate*8 + c%8            (d0 = C, d1 = K)
-    PACK_CONV_WGRAD_ACC = 5, // src [Cout][k*k*cp] (raw fp32 product) -> dst [Cout][Cin][k][k] += ...      (d0..d3 = Cout,Cin,k,cp)
-    PACK_CONV_DGRAD4 = 6     // src [Cout][Cin][3][3] -> dst [(py,px,ci)][(da,db,co)] of the 2 x 2-block input gradient (ppgemm.hpp
-                             // GATHER; d0, d1 = Cout, Cin): w[co][ci][ky][kx], ky = 1 | 2, 0 for py = 0 | 1 and da = 0, 1; else 0
-};
+// The rows and the descriptor kinds are declared in include/rvt_hip.h (RvtPackDesc, RVT_PACK_*); the empty derived structs keep the
+// kernels' symbol names (rvt::PackDesc const*), which the committed profiles are keyed by.
+struct PackDesc : RvtPackDesc {};
+static_assert(sizeof(PackDesc) == 96 && sizeof(PackDesc) == sizeof(RvtPackDesc), "PackDesc layout is part of the C ABI");
 
-struct PackDesc {             // 96 bytes; mirrored by rvt_amd/weights.py (numpy structured dtype)
-    const float* src;
-    void* dst;
-    const float* scale;
-    long long n;              // destination elements
-    int kind;
-    int out_f32;              // destination is fp32 whatever the launch dtype
-    int d[5];
-    int ky[4], kx[4];
-    unsigned block0;          // first block of this descriptor within the launch
-};
-static_assert(sizeof(PackDesc) == 96, "PackDesc layout is part of the C ABI");
-
-// one "logical block" = 1024 consecutive destination elements of one descriptor (block0 counts them): the unit the host tables are
-// built in.  A workgroup serves PACK_LBPW consecutive logical blocks: it finds the descriptor of its first one by COUNTING the
+// one "logical block" = RVT_PACK_BLOCK_ELEMS (1024) consecutive destination elements of one descriptor (block0 counts them): the unit
+// the host tables are built in.  A workgroup serves PACK_LBPW consecutive logical blocks: it finds the descriptor of its first one by COUNTING the
 // descriptors that start at or before it (every thread looks at its share: one round of loads) and walks on from there - a
 // launch over the 18.5 M parameters of RVT-Base is 30 k logical blocks, and one workgroup per logical block spent its time
 // on the descriptor look-up and the launch of the workgroup itself (0.21 ms per step; 0.07 ms for the plain copies alone).
 constexpr int PACK_LBPW = 8;
+static_assert(RVT_PACK_BLOCK_ELEMS == 256 * 4, "a logical block is four elements per thread of a 256-thread workgroup");
 
 template <class T>
 __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned lbi, float (*tile)[33]) {
     // (32-bit element indices: a packed weight has far fewer than 2^32 elements, and the index arithmetic below is all divisions)
     const unsigned i0 = (lbi * 256u + threadIdx.x) * 4u, n32 = (unsigned)d.n;
-    if (d.kind == PACK_TRANSPOSE && ((d.d[0] | d.d[1]) & 31) == 0) {
+    if (d.kind == RVT_PACK_TRANSPOSE && ((d.d[0] | d.d[1]) & 31) == 0) {
         // logical block = one 32 x 32 tile (r fastest), through LDS: 128-byte runs on the source side AND on the destination side
         // (every weight of the backbone takes this path; the two forms below serve odd shapes).  d is uniform: every thread is here.
         const unsigned R = (unsigned)d.d[0], K = (unsigned)d.d[1], ntr = R >> 5;
@@ -69,7 +50,7 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
         }
         return;
     }
-    if (d.kind == PACK_TRANSPOSE && (d.d[1] & 3) == 0 && ((size_t)d.src & 15) == 0) {
+    if (d.kind == RVT_PACK_TRANSPOSE && (d.d[1] & 3) == 0 && ((size_t)d.src & 15) == 0) {
         // a thread takes FOUR CONSECUTIVE k of one source row r (one 16-byte read) and writes them to four destination rows; the
         // threads of a wave walk r, so every one of the four stores is a contiguous run (the element-order form reads the source
         // with stride K: one 4-byte word per fetched line)
@@ -86,7 +67,7 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
         }
         return;
     }
-    if (d.kind == PACK_COPY && ((size_t)d.src & 15) == 0 && ((size_t)d.dst & 15) == 0 && i0 + 4 <= n32) {
+    if (d.kind == RVT_PACK_COPY && ((size_t)d.src & 15) == 0 && ((size_t)d.dst & 15) == 0 && i0 + 4 <= n32) {
         const f32x4 v4 = *reinterpret_cast<const f32x4*>(d.src + i0);
         if (d.out_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(d.dst) + i0) = v4;
         else {
@@ -98,7 +79,7 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
         }
         return;
     }
-    if (d.kind == PACK_LSTM_ROWS && (d.d[1] & 3) == 0 && ((size_t)d.src & 15) == 0 && ((size_t)d.dst & 15) == 0 && i0 < n32) {
+    if (d.kind == RVT_PACK_LSTM_ROWS && (d.d[1] & 3) == 0 && ((size_t)d.src & 15) == 0 && ((size_t)d.dst & 15) == 0 && i0 < n32) {
         // four consecutive k of one (interleaved) row: one 16-byte read, one store
         const unsigned C = (unsigned)d.d[0], K = (unsigned)d.d[1];
         const unsigned np = i0 / K, kc = i0 - np * K;
@@ -121,15 +102,15 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
         float v = 0.f;
         const unsigned o = i;
         switch (d.kind) {
-        case PACK_COPY: v = d.src[i]; break;
-        case PACK_TRANSPOSE: {
+        case RVT_PACK_COPY: v = d.src[i]; break;
+        case RVT_PACK_TRANSPOSE: {
             const int R = d.d[0], K = d.d[1];
             const int k = (int)(i / R), r = (int)(i % R);
             v = d.src[(size_t)r * K + k];
             if (d.scale) v *= d.scale[r];
             break;
         }
-        case PACK_CONV_FWD: {
+        case RVT_PACK_CONV_FWD: {
             const int Cin = d.d[1], k = d.d[2], cp = d.d[3];
             const int kk = k * k * cp;
             const int co = (int)(i / kk), rem = (int)(i % kk);
@@ -138,7 +119,7 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
             v = ci < Cin ? d.src[(((size_t)co * Cin + ci) * k + ky) * k + kx] : 0.f;
             break;
         }
-        case PACK_CONV_DGRAD: {
+        case RVT_PACK_CONV_DGRAD: {
             const int Cout = d.d[0], Cin = d.d[1], k = d.d[2], nkx = d.d[4];
             const int per = d.d[3] * nkx * Cout;
             const int ci = (int)(i / per), rem = (int)(i % per);
@@ -147,14 +128,14 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
             v = d.src[(((size_t)co * Cin + ci) * k + d.ky[a & 3]) * k + d.kx[b & 3]];
             break;
         }
-        case PACK_LSTM_ROWS: {
+        case RVT_PACK_LSTM_ROWS: {
             const int C = d.d[0], K = d.d[1];
             const int np = (int)(i / K), kc = (int)(i % K);
             const int c = (np / 32) * 8 + np % 8, gate = (np % 32) / 8;
             v = d.src[(size_t)(gate * C + c) * K + kc];
             break;
         }
-        case PACK_CONV_DGRAD4: {
+        case RVT_PACK_CONV_DGRAD4: {
             const int Cout = d.d[0], Cin = d.d[1];
             const int n = (int)(i / (4 * Cout)), kc = (int)(i % (4 * Cout));
             const int cls = n / Cin, ci = n % Cin, tap = kc / Cout, co = kc % Cout;
@@ -164,7 +145,7 @@ __device__ __forceinline__ void pack_logical_block(const PackDesc& d, unsigned l
             v = on ? d.src[(((size_t)co * Cin + ci) * 3 + ky) * 3 + kx] : 0.f;
             break;
         }
-        case PACK_CONV_WGRAD_ACC: {
+        case RVT_PACK_CONV_WGRAD_ACC: {
             const int Cin = d.d[1], k = d.d[2], cp = d.d[3];
             const int per = Cin * k * k;
             const int co = (int)(i / per), rem = (int)(i % per);
@@ -211,13 +192,8 @@ pack_table_kernel(const PackDesc* __restrict__ descs, int nd, unsigned total_blo
 // weight-gradient GEMMs deliver the raw products S[c][k] = sum_tok dy[tok][c] a[tok][k] and cs[c] = sum_tok dy[tok][c] of
 // the *outer* cotangent dy (the dgrad weights carry gamma instead).  Then
 //   dW[c][k] += gamma[c] S[c][k],   db[c] += gamma[c] cs[c],   dgamma[c] += sum_k W[c][k] S[c][k] + b[c] cs[c].
-struct LayerScaleDesc {       // 80 bytes
-    const float* S; const float* cs; const float* W; const float* b; const float* gamma;
-    float* dW; float* db; float* dgamma;
-    int C, K;
-    unsigned block0; int pad;
-};
-static_assert(sizeof(LayerScaleDesc) == 80, "LayerScaleDesc layout is part of the C ABI");
+struct LayerScaleDesc : RvtLayerScaleDesc {};
+static_assert(sizeof(LayerScaleDesc) == 80 && sizeof(LayerScaleDesc) == sizeof(RvtLayerScaleDesc), "LayerScaleDesc layout is part of the C ABI");
 
 __global__ void __launch_bounds__(256)
 layerscale_grad_kernel(const LayerScaleDesc* __restrict__ descs, int nd) {

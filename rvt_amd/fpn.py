@@ -215,7 +215,7 @@ class ConvPack:
                 ar32.buf = torch.zeros(max(ar32.n, 64), dtype=torch.float32, device=dev)
                 n_stats = ar32_stats
                 arT.n = ar32.n = 0
-            tab = weights._Table(weights.PACK_DT, 1024)
+            tab = weights.pack_table()
             for c in self.convs:                         # statistics first: one contiguous region to zero per forward
                 st = ar32.take(2, 2 * c.out_channels)         # two fp64 vectors
                 if second:

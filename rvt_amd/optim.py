@@ -33,11 +33,8 @@ from . import _lib as L
 
 Tensor = torch.Tensor
 
-CHUNK = 4096                                          # csrc/optim.hpp: OPTIM_CHUNK
-CHUNK_DT = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('n', '<i4'), ('group', '<i4')])
-GROUP_FIELDS = ('beta1', 'beta2', 'eps', 'weight_decay', 'clip', 'lr_init', 'lr_max', 'lr_final', 'warm_end', 'last')
-GROUP_DT = np.dtype([(k, '<f8') for k in GROUP_FIELDS])
-assert CHUNK_DT.itemsize == 40 and GROUP_DT.itemsize == 80
+CHUNK = L.ENUMS['RVT_OPTIM_CHUNK_ELEMS']              # elements per row of the chunk table (include/rvt_hip.h: RvtOptimChunk)
+SCHEDULE = ('lr_init', 'lr_max', 'lr_final', 'warm_end', 'last')      # the schedule fields of RvtOptimGroup = OneCycle.constants()
 
 
 class OneCycle:
@@ -73,17 +70,6 @@ def schedule_lr(lr_init: float, lr_max: float, lr_final: float, warm_end: float,
     if pos <= last:
         return (lr_final - lr_max) * ((pos - warm_end) / (last - warm_end)) + lr_max
     return lr_final
-
-
-class _DeviceTable:
-    """Host-built descriptor array -> device bytes (one launch walks it)."""
-
-    def __init__(self, arr: np.ndarray, device):
-        self.n = len(arr)
-        self.dev = torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(device)
-
-    def __len__(self):
-        return self.n
 
 
 def _check_grad(p: Tensor, g: Tensor) -> None:
@@ -131,8 +117,8 @@ class AdamW(torch.optim.Optimizer):
         self._views: Dict[Tensor, Tuple[Tensor, Tensor]] = {
             p: (self._exp_avg[o:o + n].view(p.shape), self._exp_avg_sq[o:o + n].view(p.shape)) for p, (o, n) in zip(ps, spans)}
         self._step = torch.zeros(1, dtype=torch.int64, device=dev)        # optimizer steps done so far; the kernel advances it
-        self._chunks: Optional[_DeviceTable] = None
-        self._groups: Optional[_DeviceTable] = None
+        self._chunks: Optional[L.DeviceTable] = None
+        self._groups: Optional[L.DeviceTable] = None
         self._sig = self._hyper = None
 
     # ---- construction-time checks ---------------------------------------------------------------------------
@@ -153,29 +139,31 @@ class AdamW(torch.optim.Optimizer):
                                  f'weight_decay={g["weight_decay"]}')
 
     # ---- tables -----------------------------------------------------------------------------------------------
-    def _group_rows(self) -> List[Tuple[float, ...]]:
+    def _group_rows(self) -> List[Dict[str, float]]:
+        """One RvtOptimGroup per parameter group, by field name."""
         clip = -1.0 if self.clip_value is None else float(self.clip_value)
         rows = []
         for g in self.param_groups:
             lr = float(g['lr'])
             sched = self.schedule.constants(lr) if self.schedule is not None else (lr, lr, lr, 0.0, 0.0)
-            rows.append((float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), clip) + sched)
+            rows.append(dict(zip(SCHEDULE, sched), beta1=float(g['betas'][0]), beta2=float(g['betas'][1]), eps=float(g['eps']),
+                             weight_decay=float(g['weight_decay']), clip=clip))
         return rows
 
-    def _build_chunks(self, entries) -> _DeviceTable:
+    def _build_chunks(self, entries) -> L.DeviceTable:
         parts = []
         for p, g, gi in entries:
             m, v = self._views[p]
             if p not in self.state or 'exp_avg' not in self.state[p]:
                 self.state[p]['exp_avg'], self.state[p]['exp_avg_sq'] = m, v
             n = p.numel()
-            arr = np.zeros((n + CHUNK - 1) // CHUNK, dtype=CHUNK_DT)
+            arr = np.zeros((n + CHUNK - 1) // CHUNK, dtype=L.row_dtype('RvtOptimChunk'))
             o = np.arange(len(arr), dtype=np.uint64) * np.uint64(4 * CHUNK)
             arr['p'], arr['g'], arr['m'], arr['v'] = p.data_ptr() + o, g.data_ptr() + o, m.data_ptr() + o, v.data_ptr() + o
             arr['n'] = np.minimum(n - np.arange(len(arr), dtype=np.int64) * CHUNK, CHUNK)
             arr['group'] = gi
             parts.append(arr)
-        return _DeviceTable(np.concatenate(parts), self._step.device)
+        return L.DeviceTable('RvtOptimChunk').upload(self._step.device, np.concatenate(parts))
 
     # ---- the step ---------------------------------------------------------------------------------------------
     def step(self, closure=None):
@@ -202,7 +190,10 @@ class AdamW(torch.optim.Optimizer):
         rows = self._group_rows()
         if rows != self._hyper:
             self._check_groups()
-            self._groups = _DeviceTable(np.array(rows, dtype=np.float64).view(GROUP_DT).reshape(-1), self._step.device)
+            self._groups = L.DeviceTable('RvtOptimGroup')
+            for row in rows:
+                self._groups.add(**row)
+            self._groups.upload(self._step.device)
             self._hyper = rows
         L.call('rvt_optim_step', L.ptr(self._chunks.dev), len(self._chunks), L.ptr(self._groups.dev), len(self._groups),
                L.ptr(self._step), int(self.max_blocks), L.stream_of(self._step))
@@ -218,7 +209,7 @@ class AdamW(torch.optim.Optimizer):
     def current_lr(self) -> List[float]:
         """Learning rate of every group at the NEXT step (the schedule at position = steps done).  Reads the step count back."""
         k = self.step_count()
-        return [schedule_lr(*row[5:], float(k)) for row in self._group_rows()]
+        return [schedule_lr(*(row[f] for f in SCHEDULE), float(k)) for row in self._group_rows()]
 
     def state_dict(self) -> Dict[str, Any]:
         k = self.step_count()
@@ -228,7 +219,8 @@ class AdamW(torch.optim.Optimizer):
         sd = super().state_dict()
         if self.schedule is not None:                     # the keys OneCycleLR keeps in the groups; lr = the current one, as there
             for g, row in zip(sd['param_groups'], self._group_rows()):
-                g.update(lr=schedule_lr(*row[5:], float(k)), initial_lr=row[5], max_lr=row[6], min_lr=row[7])
+                g.update(lr=schedule_lr(*(row[f] for f in SCHEDULE), float(k)), initial_lr=row['lr_init'], max_lr=row['lr_max'],
+                         min_lr=row['lr_final'])
         return sd
 
     def load_state_dict(self, state_dict: Dict[str, Any]) -> None:

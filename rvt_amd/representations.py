@@ -137,7 +137,6 @@ class MixedDensityEventStack:
 
 _COORD_BYTES = {torch.int16: 2, torch.int32: 4, torch.int64: 8}
 REPRESENTATIONS = ('stacked_histogram', 'mixed_density')
-TABLE_COLS = 6                       # include/rvt_hip.h: x, y, p, t, n, ts_end per stream, 8 bytes each
 DEFAULT_WINDOWS_IN_FLIGHT = 8        # scratch images per chunk (profiles/evseq_bench.txt)
 Stream = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
 
@@ -199,7 +198,7 @@ class EventSequenceBuilder:
         if B < 1:
             raise ValueError('streams is empty')
         dev, cdt = ts_end.device, None
-        rows = np.zeros((B, TABLE_COLS), dtype=np.int64)
+        rows = np.zeros(B, dtype=L.row_dtype('RvtEventStream'))
         capacity = 0
         for b, s in enumerate(streams):
             if len(s) != 4 or not all(torch.is_tensor(a) for a in s):
@@ -218,9 +217,10 @@ class EventSequenceBuilder:
             if not 0 <= n <= t.numel():
                 raise ValueError(f'counts[{b}]={n} outside the buffers\' capacity 0..{t.numel()}')
             te = ts_end if ts_end.dim() == 1 else ts_end[b]
-            rows[b] = (L.ptr(x), L.ptr(y), L.ptr(p), L.ptr(t), n, te.data_ptr())
+            row = rows[b]
+            row['x'], row['y'], row['p'], row['t'], row['n'], row['ts_end'] = L.ptr(x), L.ptr(y), L.ptr(p), L.ptr(t), n, te.data_ptr()
             capacity = max(capacity, t.numel())
-        return streams, rows, _COORD_BYTES[cdt], capacity
+        return streams, rows.view(np.int64).reshape(B, -1), _COORD_BYTES[cdt], capacity
 
     @staticmethod
     def _check_ts_end(ts_end_us: torch.Tensor, B: int) -> torch.Tensor:

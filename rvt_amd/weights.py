@@ -6,7 +6,7 @@ The nn.Module keeps the reference's parameter names and shapes 
   * the ConvLSTM 1x1-conv rows interleaved so one 32-column epilogue unit holds all four gates,
   * everything cast to the activation dtype.
 All of that is ONE launch per optimisation step: ``ModelWeights`` lays the packed tensors out in two flat buffers,
-builds a descriptor table (rvt_amd/csrc/pack.hpp) once, and ``pack()`` replays it through ``rvt_pack_table``.
+builds a descriptor table (include/rvt_hip.h: RvtPackDesc) once, and ``pack()`` replays it through ``rvt_pack_table``.
 
 Gradients go the other way through persistent per-stage fp32 buckets (``StageGrads``): the weight-gradient kernels
 accumulate straight into views of a bucket (param order = the module's), the LayerScale fold and the conv unpack are one
@@ -24,12 +24,9 @@ from . import _lib as L
 
 Tensor = torch.Tensor
 
-PACK_COPY, PACK_TRANSPOSE, PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_LSTM_ROWS, PACK_CONV_WGRAD_ACC, PACK_CONV_DGRAD4 = range(7)
-PACK_DT = np.dtype([('src', '<u8'), ('dst', '<u8'), ('scale', '<u8'), ('n', '<i8'), ('kind', '<i4'), ('out_f32', '<i4'),
-                    ('d', '<i4', (5,)), ('ky', '<i4', (4,)), ('kx', '<i4', (4,)), ('block0', '<u4')])
-LS_DT = np.dtype([('S', '<u8'), ('cs', '<u8'), ('W', '<u8'), ('b', '<u8'), ('gamma', '<u8'), ('dW', '<u8'), ('db', '<u8'),
-                  ('dgamma', '<u8'), ('C', '<i4'), ('K', '<i4'), ('block0', '<u4'), ('pad', '<i4')])
-assert PACK_DT.itemsize == 96 and LS_DT.itemsize == 80
+PACK_COPY, PACK_TRANSPOSE, PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_LSTM_ROWS, PACK_CONV_WGRAD_ACC, PACK_CONV_DGRAD4 = (
+    L.ENUMS['RVT_PACK_' + k] for k in ('COPY', 'TRANSPOSE', 'CONV_FWD', 'CONV_DGRAD', 'LSTM_ROWS', 'CONV_WGRAD_ACC', 'CONV_DGRAD4'))
+PACK_BLOCK = L.ENUMS['RVT_PACK_BLOCK_ELEMS']         # destination elements per block of a pack table
 
 
 def round8(c: int) -> int:
@@ -40,36 +37,15 @@ def conv_dgrad_taps(k: int, stride: int, pad: int, parity: int) -> List[int]:
     return [t for t in range(k) if t % stride == (parity + pad) % stride]
 
 
-class _Table:
-    """Host-built descriptor array -> device bytes (one launch walks it)."""
-
-    def __init__(self, dt: np.dtype, per_block: Optional[int]):
-        self.dt, self.per_block = dt, per_block
-        self.rows: List[dict] = []
-        self.blocks = 0
-        self.dev: Optional[Tensor] = None
-
-    def add(self, nblocks: int, **fields) -> None:
-        fields['block0'] = self.blocks
-        self.rows.append(fields)
-        self.blocks += nblocks
-
-    def upload(self, device) -> None:
-        arr = np.zeros(len(self.rows), dtype=self.dt)
-        for i, r in enumerate(self.rows):
-            for k, v in r.items():
-                arr[i][k] = v
-        self.dev = torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(device)
-
-    def __len__(self):
-        return len(self.rows)
+def pack_table() -> L.DeviceTable:
+    return L.DeviceTable('RvtPackDesc')
 
 
-def _pack_entry(tab: _Table, src: Tensor, dst: Tensor, kind: int, d=(), scale: Optional[Tensor] = None, ky=(), kx=(),
+def _pack_entry(tab: L.DeviceTable, src: Tensor, dst: Tensor, kind: int, d=(), scale: Optional[Tensor] = None, ky=(), kx=(),
                 n: Optional[int] = None) -> None:
     n = dst.numel() if n is None else n
     dd = list(d) + [0] * (5 - len(d))
-    tab.add((n + 1023) // 1024, src=src.data_ptr(), dst=dst.data_ptr(), scale=0 if scale is None else scale.data_ptr(), n=n,
+    tab.add((n + PACK_BLOCK - 1) // PACK_BLOCK, src=src.data_ptr(), dst=dst.data_ptr(), scale=0 if scale is None else scale.data_ptr(), n=n,
             kind=kind, out_f32=int(dst.dtype == torch.float32), d=dd, ky=list(ky) + [0] * (4 - len(ky)),
             kx=list(kx) + [0] * (4 - len(kx)))
 
@@ -131,8 +107,8 @@ class StageGrads:
         self.flat = torch.zeros(max(off, 4), dtype=torch.float32, device=device)
         self.view = {n: self.flat[o:o + c].view(*shp) for n, (o, c, shp) in spans.items()}
         self.param_region = self.flat[:self.n_param]
-        self.ls_table: Optional[_Table] = None
-        self.unpack_table: Optional[_Table] = None
+        self.ls_table: Optional[L.DeviceTable] = None
+        self.unpack_table: Optional[L.DeviceTable] = None
 
     def zero(self, keep_params: bool = False) -> None:
         """Start a backward: the raw products always restart from zero (their fold ADDS them into the parameter
@@ -170,7 +146,7 @@ class ModelWeights:
                 arT.buf = torch.empty(max(arT.n, 64), dtype=dtype, device=dev)
                 ar32.buf = torch.empty(max(ar32.n, 64), dtype=torch.float32, device=dev)
                 arT.n = ar32.n = 0
-            tab = _Table(PACK_DT, 1024)
+            tab = pack_table()
             stages = []
             for si, g in enumerate(geoms):
                 stages.append(self._build_stage(tab if second else None, arT, ar32, p, f'stages.{si}.', g, need_grad))
@@ -184,7 +160,7 @@ class ModelWeights:
                 self.grads.append(self._build_grads(mod, p, f'stages.{si}.', g, stages[si], dev))
 
     # ---- packed weights ---------------------------------------------------------------------------------
-    def _build_stage(self, tab: Optional[_Table], arT: _Arena, ar32: _Arena, p, pre: str, g, need_grad: bool) -> StageWeights:
+    def _build_stage(self, tab: Optional[L.DeviceTable], arT: _Arena, ar32: _Arena, p, pre: str, g, need_grad: bool) -> StageWeights:
         m = self.master
         dtype_is_bf16 = self.dtype == torch.bfloat16
         sw = StageWeights()
@@ -282,7 +258,7 @@ class ModelWeights:
                 bp = f'{pre}att_blocks.{bi}.{blk}.'
                 aux += [(bp + 'S1', (C, C)), (bp + 'cs1', (C,)), (bp + 'S2', (C, 4 * C)), (bp + 'cs2', (C,))]
         sg = StageGrads(names, shapes, aux, dev)
-        ls = _Table(LS_DT, None)
+        ls = L.DeviceTable('RvtLayerScaleDesc')
         for bi in range(g.num_blocks):
             for wi, blk in enumerate(('att_window', 'att_grid')):
                 bp = f'{pre}att_blocks.{bi}.{blk}.'
@@ -294,7 +270,7 @@ class ModelWeights:
                            dW=sg.g(bp + Wn).data_ptr(), db=sg.g(bp + bn).data_ptr(), dgamma=sg.g(bp + gn).data_ptr(), C=C, K=K, pad=0)
         ls.upload(dev)
         sg.ls_table = ls
-        up = _Table(PACK_DT, 1024)
+        up = pack_table()
         cw = sg.g(pre + 'downsample_cf2cl.conv.weight')
         _pack_entry(up, sg.g('raw/conv'), cw, PACK_CONV_WGRAD_ACC, (C, g.Cin, k, cp))
         up.upload(dev)
@@ -367,7 +343,7 @@ def lstm_gate_perm(C: int, device) -> Tensor:
 def pack_conv_dgrad4(w: Tensor, dtype: torch.dtype) -> Tensor:
     """[4*Cin][4*Cout] block-sparse weights of the one-launch input gradient (rvt_conv_dgrad4; 3x3 / stride 2 / pad 1):
     row (py, px, ci), column (da, db, co) = w[co][ci][ky][kx] with ky = 1 | 2, 0 for py = 0 | 1 and da = 0, 1 (kx likewise), else 0.
-    Host-side restatement of PACK_CONV_DGRAD4 (csrc/pack.hpp) for the kernel tests."""
+    Host-side restatement of RVT_PACK_CONV_DGRAD4 (include/rvt_hip.h) for the kernel tests."""
     Cout, Cin, k, _ = w.shape
     assert k == 3
     out = torch.zeros(4, Cin, 4, Cout, dtype=torch.float32, device=w.device)

@@ -5,13 +5,13 @@ with which integer / float arguments and which pointers NULL.  A refactor of the
     python -m tests.make_golden_launch_trace --backend hip        (MI355X, production route)
 
 rewrites the cases of that backend in tests/golden/launch_trace.json (per case: launch count, {name: count} histogram, SHA-256
-of the canonical sequence).  The recorder only wraps `rvt_amd._lib.call` and reads `_lib._SIGS`, so it runs unchanged on any
-revision; the golden is recorded on the revision BEFORE a change and tests/test_launch_trace.py replays it on the one after.
+of the canonical sequence).  The recorder only wraps `rvt_amd._lib.call` and reads the header's prototypes (`_header.PROTOS`), so it
+runs unchanged on any revision that derives its binding from the header; the golden is recorded on the revision BEFORE a change and tests/test_launch_trace.py replays it on the one after.
 The host loop is forced (route_stage_driver = route_stage_driver_train = 0): the C-side drivers issue their launches inside one
 library call, and tests/test_stage_driver.py ties them to the host loop bit for bit.
 
-One normalisation: `rb`, the tile factor rvt_lstm_scan3_fwd / _bwd take as their last argument before the stream (absent when
-the golden was recorded: the library read it from the tuning record), is taken out of the tuple and returned separately."""
+One normalisation: `rb`, the tile factor rvt_lstm_scan3_fwd / _bwd take (absent when the golden was recorded: the library read it
+from the tuning record), is found by its parameter name, taken out of the tuple and returned separately."""
 import argparse
 import ctypes
 import hashlib
@@ -20,13 +20,13 @@ import os
 
 import torch
 
-from rvt_amd import RNNDetector, _lib, backbone_config, tuning
+from rvt_amd import RNNDetector, _header, _lib, backbone_config, tuning
 from tests import casegen
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_trace.json')
 MODES = ('train', 'nograd', 'stream')
 HOST_LOOP = dict(route_stage_driver=0, route_stage_driver_train=0)
-_SCAN3_ARGS = {'rvt_lstm_scan3_fwd': 13, 'rvt_lstm_scan3_bwd': 15}      # argument counts without `rb`
+SCAN3 = ('rvt_lstm_scan3_fwd', 'rvt_lstm_scan3_bwd')
 
 # ---- emulator cases: (casegen name, dtype) x tuning on top of TEST_GEOMETRY x mode ----
 EMU_MODELS = [('micro', 'f32'), ('micro', 'bf16'), ('micro_mask', 'f32'), ('micro_dws_xh', 'f32'), ('micro_dws_hidden', 'f32'),
@@ -53,19 +53,18 @@ def hip_cases():
 
 def canonical(name, args):
     """(entry of the canonical sequence, rb or None)."""
-    sig = _lib._SIGS[name]
-    assert len(sig) == len(args), (name, len(sig), len(args))
-    out = [name]
-    for ty, a in zip(sig, args):
-        if ty is ctypes.c_void_p:
+    proto = _header.PROTOS[name]
+    assert len(proto.argtypes) == len(args), (name, len(proto.argtypes), len(args))
+    out, rb = [name], None
+    for ty, arg, a in zip(proto.argtypes, proto.argnames, args):
+        if name in SCAN3 and arg == 'rb':
+            rb = int(a)
+        elif ty is ctypes.c_void_p:
             out.append(int(a is not None and int(a) != 0))
         elif ty is ctypes.c_float:
             out.append(repr(float(a)))
         else:
             out.append(int(a))
-    rb = None
-    if name in _SCAN3_ARGS and len(args) == _SCAN3_ARGS[name] + 1:
-        rb = out.pop(-2)
     return out, rb
 
 
@@ -78,7 +77,7 @@ def record(fn):
         entry, rb = canonical(name, args)
         seq.append(entry)
         if rb is not None:
-            rbs.append((name, int(args[-4]), rb))        # (.., dtype, M, C, T_steps, rb, stream)
+            rbs.append((name, int(_header.LaunchArgs(name, args).C), rb))
         return orig(name, *args)
     _lib.call = rec
     try:

@@ -6,6 +6,7 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -36,7 +37,7 @@ def _same_types(got, want):
 
 
 def test_header_reader_prototypes():
-    _, protos = _header.parse('''
+    _, protos, _ = _header.parse('''
         /* a comment with ( and ; inside, int not_a_function(int x); and text right up to the end*/int rvt_a(const void* x,
                   float* y, int n,
                   float eps, void* stream);
@@ -56,7 +57,7 @@ def test_header_reader_prototypes():
 
 
 def test_header_reader_structs():
-    structs, protos = _header.parse('''
+    structs, protos, enums = _header.parse('''
         #ifdef __cplusplus
         extern "C" {
         #endif
@@ -79,6 +80,7 @@ def test_header_reader_structs():
         #endif
     ''')
     Inner, Outer = structs['Inner'], structs['Outer']
+    assert enums == dict(RVT_X=0, RVT_Y=1)
     assert list(structs) == ['Inner', 'Outer'] and issubclass(Inner, ctypes.Structure) and issubclass(Outer, ctypes.Structure)
     assert [f for f, _ in Inner._fields_] == ['a', 'b', 'w', 'bias', 'p', 'eps'] == list(_header.fields(Inner))
     assert _same_types([t for _, t in Inner._fields_], [_I, _I, _VP, _VP, _VP, _F])
@@ -90,12 +92,52 @@ def test_header_reader_structs():
     assert protos['rvt_use'].restype is _I and _same_types(protos['rvt_use'].argtypes, [_VP, _VP, _I])
 
 
+def test_header_reader_arrays_and_enums():
+    text = '''
+        enum { RVT_X = 0, RVT_Y = 1 };
+        enum {                    /* one enumerator per line, a comment with a , and a = behind each */
+            RVT_KIND_A = 3,       /* explicit */
+            RVT_KIND_B,           /* auto-increment: 4 */
+            RVT_KIND_C = -2,
+            RVT_KIND_D            /* -1; no trailing comma */
+        };
+        enum { RVT_ELEMS = 1024, };
+        typedef struct Row {
+            const float* src; long long n;
+            int d[5];
+            int ky[4], kx [ 2 ];            /* two arrays, one declarator */
+            unsigned block0;
+            double w[3];
+        } Row;
+        int rvt_walk(const Row* rows, unsigned n, void* stream);
+    '''
+    structs, protos, enums = _header.parse(text)
+    Row = structs['Row']
+    assert [f for f, _ in Row._fields_] == ['src', 'n', 'd', 'ky', 'kx', 'block0', 'w']
+    assert _same_types([t for _, t in Row._fields_], [_VP, ctypes.c_longlong, _I * 5, _I * 4, _I * 2, ctypes.c_uint, _D * 3])
+    assert [getattr(Row, f).offset for f in _header.fields(Row)] == [0, 8, 16, 36, 52, 60, 64] and ctypes.sizeof(Row) == 88
+    dt = np.dtype(Row)                       # what the device tables are built from
+    assert dt.names == _header.fields(Row) and dt.itemsize == 88 and dt['d'].shape == (5,) and dt['kx'].shape == (2,)
+    assert dt['src'] == np.dtype('<u8') and dt['block0'] == np.dtype('<u4') and dt['w'].base == np.dtype('<f8')
+    assert _same_types(protos['rvt_walk'].argtypes, [_VP, ctypes.c_uint, _VP])
+    assert enums == dict(RVT_X=0, RVT_Y=1, RVT_KIND_A=3, RVT_KIND_B=4, RVT_KIND_C=-2, RVT_KIND_D=-1, RVT_ELEMS=1024)
+
+
 @pytest.mark.parametrize('text,says', [
     ('int rvt_a(const void* x, uint64_t n);', 'uint64_t'),                          # unknown type of a parameter
     ('typedef struct S { short a; } S;', 'short'),                                  # ... of a field
     ('int rvt_a(int n);\nstatic int counter = 0;\nint rvt_b(int n);', 'counter'),    # a declaration the reader has no rule for
     ('int rvt_a(int n);\nstruct Loose { int a; };', 'Loose'),                        # a struct outside the typedef form
-], ids=['unknown_param_type', 'unknown_field_type', 'leftover_declaration', 'leftover_struct'])
+    ('typedef struct S { int d[N]; } S;', r'd\[N\]'),                                # an array whose length is not a literal
+    ('typedef struct S { int d[2][3]; } S;', r'd\[2\]\[3\]'),                        # more than one dimension
+    ('typedef struct S { int d[]; } S;', r'd\[\]'),                                  # a flexible array member
+    ('int rvt_a(int d[4], int n);', 'array in the prototype of rvt_a'),             # arrays are struct fields only
+    ('enum { RVT_A = 1 << 2 };', '1 << 2'),                                         # an enumerator that is an expression
+    ('enum { RVT_A = RVT_B };', 'RVT_B'),                                           # ... or another name
+    ('enum { RVT_A, RVT_A };', 'RVT_A'),                                            # a name twice
+    ('enum Kind { RVT_A = 0 };', 'Kind'),                                           # a named enum
+], ids=['unknown_param_type', 'unknown_field_type', 'leftover_declaration', 'leftover_struct', 'array_symbolic_length', 'array_2d',
+        'array_flexible', 'array_parameter', 'enum_expression', 'enum_alias', 'enum_duplicate', 'enum_named'])
 def test_header_reader_refuses(text, says):
     with pytest.raises(RuntimeError, match=says):
         _header.parse(text)
@@ -108,14 +150,70 @@ def test_header_reader_names_a_missing_header(monkeypatch):
 
 
 def test_derived_binding_covers_the_real_header():
-    """Every prototype and all 7 structs of include/rvt_hip.h; tuning.FIELDS is the struct's own order."""
+    """Every prototype, the 7 host-side structs and the 5 device-table rows of include/rvt_hip.h; tuning.FIELDS is the struct's own order."""
     from rvt_amd import stage_driver, tuning
     assert set(_header.STRUCTS) == {'RvtTuning', 'RvtBlockWeights', 'RvtStageDesc', 'RvtStageRoutes', 'RvtBlockSaved', 'RvtBlockTrain',
-                                    'RvtStageTrain'}
+                                    'RvtStageTrain'} | set(TABLE_ROWS)
     assert ('struct_bytes',) + tuning.FIELDS == _header.fields(tuning.RvtTuning) and tuning.RvtTuning is _header.STRUCTS['RvtTuning']
-    assert all(getattr(stage_driver, n) is c for n, c in _header.STRUCTS.items() if n != 'RvtTuning')
+    assert all(getattr(stage_driver, n) is c for n, c in _header.STRUCTS.items() if n != 'RvtTuning' and n not in TABLE_ROWS)
     assert all(ty is ctypes.c_void_p or ty in (_I, _F, ctypes.c_size_t, ctypes.c_longlong) for sig in _lib._SIGS.values() for ty in sig)
     assert _lib._SIGS['rvt_stage_routes'][0] is ctypes.c_void_p and _lib._SIGS['rvt_stage_routes'][-1] is ctypes.c_void_p
+
+
+# sizeof of the device-table rows and the descriptor kinds: the values the kernels' static_asserts and enum held before the header declared them
+TABLE_ROWS = {'RvtPackDesc': 96, 'RvtLayerScaleDesc': 80, 'RvtOptimChunk': 40, 'RvtOptimGroup': 80, 'RvtEventStream': 48}
+PACK_KINDS = {'RVT_PACK_COPY': 0, 'RVT_PACK_TRANSPOSE': 1, 'RVT_PACK_CONV_FWD': 2, 'RVT_PACK_CONV_DGRAD': 3, 'RVT_PACK_LSTM_ROWS': 4,
+              'RVT_PACK_CONV_WGRAD_ACC': 5, 'RVT_PACK_CONV_DGRAD4': 6}
+
+
+def test_table_rows_match_the_c_compiler(tmp_path):
+    """The layout is pinned against a C compiler, not against the reader: a C99 program that includes the header prints sizeof, every
+    offsetof and the enumerators; the ctypes structs, the numpy dtypes the tables are built from and ENUMS must say the same."""
+    rows = {n: _header.STRUCTS[n] for n in TABLE_ROWS}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rvt_hip.h"', 'int main(void) {']
+    for n, st in rows.items():
+        lines.append(f'    printf("{n} %zu\\n", sizeof({n}));')
+        lines += [f'    printf("{n}.{f} %zu\\n", offsetof({n}, {f}));' for f in _header.fields(st)]
+    lines += [f'    printf("{e} %d\\n", (int){e});' for e in _header.ENUMS]
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / 'layout.c', tmp_path / 'layout'
+    src.write_text('\n'.join(lines) + '\n')
+    subprocess.run(['cc', '-std=c99', '-pedantic', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)],
+                   check=True, capture_output=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    c = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    for n, st in rows.items():
+        dt = np.dtype(st)
+        assert c[n] == ctypes.sizeof(st) == dt.itemsize == TABLE_ROWS[n], n
+        assert dt.names == _header.fields(st)
+        for f in dt.names:
+            assert c[f'{n}.{f}'] == getattr(st, f).offset == dt.fields[f][1], (n, f)
+    assert {e: c[e] for e in _header.ENUMS} == _header.ENUMS
+    assert {e: c[e] for e in PACK_KINDS} == PACK_KINDS
+    assert c['RVT_PACK_BLOCK_ELEMS'] == 1024 and c['RVT_OPTIM_CHUNK_ELEMS'] == 4096 and (c['RVT_F32'], c['RVT_BF16']) == (0, 1)
+    # the offsets of the hand-written dtype this replaced (rvt_amd/weights.py: PACK_DT), and the formats numpy derives
+    pk = np.dtype(rows['RvtPackDesc'])
+    assert [pk.fields[f][1] for f in pk.names] == [0, 8, 16, 24, 32, 36, 40, 60, 76, 92]
+    assert [pk[f].base.str for f in pk.names] == ['<u8', '<u8', '<u8', '<i8', '<i4', '<i4', '<i4', '<i4', '<i4', '<u4']
+    assert (pk['d'].shape, pk['ky'].shape, pk['kx'].shape) == ((5,), (4,), (4,))
+
+
+def test_launch_args_by_name_and_arity_guard():
+    """A recorded launch is read by the header's parameter names; a record that does not fit the prototype raises and names the entry."""
+    import opmodel
+    args = (1, 2, None, 3, 0, 128, 64, 32, 0, None)          # rvt_linear_fwd(x, w, bias, y, dtype, M, N, K, gelu_in, stream)
+    a = _header.LaunchArgs('rvt_linear_fwd', args)
+    assert (a.M, a.N, a.K, a.dtype) == (128, 64, 32, 0) and a.has('x') and not a.has('bias') and not a.has('stream')
+    with pytest.raises(TypeError, match="'M' is not a pointer parameter of rvt_linear_fwd"):
+        a.has('M')
+    with pytest.raises(AttributeError, match="rvt_linear_fwd has no parameter 'T_steps'"):
+        a.T_steps
+    assert opmodel.model('rvt_linear_fwd', args) == (2.0 * 128 * 64 * 32, (128 * (64 + 32) + 64 * 32) * 4.0)
+    for fn in (_header.LaunchArgs, opmodel.model, opmodel.executed):
+        with pytest.raises(TypeError, match='rvt_linear_fwd takes 10 arguments .* the record has 9'):
+            fn('rvt_linear_fwd', args[:-1])
+    with pytest.raises(TypeError, match='rvt_pack_table takes 5 arguments'):          # also an entry point that has no model
+        opmodel.model('rvt_pack_table', (1, 2, 3, 0))
 
 
 def test_generated_structs_are_accepted_by_the_library():

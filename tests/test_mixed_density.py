@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from rvt_amd import RNNDetector, _lib
+from rvt_amd._header import LaunchArgs
 from rvt_amd.representations import EventSequenceBuilder, MixedDensityEventStack
 from tests import casegen
 from tests.backends import backend  # noqa: F401
@@ -289,7 +290,7 @@ def test_backbone_takes_int8_planes(backend, dtype):
                 got_f, got_s = m.forward_sequence(planes)
             finally:
                 _lib.call = orig
-        kinds = [a[1] for n, a in calls if n == 'rvt_prepack_input']
+        kinds = [LaunchArgs(n, a).src_kind for n, a in calls if n == 'rvt_prepack_input']
         assert kinds == [2], (grad, kinds)
         assert sorted(got_f) == sorted(want_f) == [1, 2, 3, 4]
         for k in want_f:

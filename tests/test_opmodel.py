@@ -4,6 +4,7 @@ import torch
 
 import opmodel
 from rvt_amd import _lib, tuning
+from rvt_amd._header import LaunchArgs
 from tests.backends import emu_library
 from tests.test_backbone import run_hip_case
 
@@ -42,7 +43,8 @@ def test_every_launch_of_a_training_step_is_priced():
             assert fl >= 0 and by > 0, (name, fl, by)
             seen.add(name)
             if name == 'rvt_linear_fwd':
-                M, N, K = args[5], args[6], args[7]
+                a = LaunchArgs(name, args)
+                M, N, K = a.M, a.N, a.K
                 assert fl == 2.0 * M * N * K
     assert {'rvt_linear_wgrad', 'rvt_lstm_scan_bwd', 'rvt_attn_bwd', 'rvt_conv_fwd', 'rvt_layernorm_bwd', 'rvt_lstm_fwd',
             'rvt_dwconv_fwd', 'rvt_token_mask_fwd'} <= seen, seen
