@@ -59,9 +59,6 @@ typedef struct RvtTuning {
     int struct_bytes;         /* sizeof(RvtTuning) of the caller; set / get reject a mismatch */
     /* ---- launch geometry ---- */
     int gemm_resident;        /* persistent workgroups of the 128-row GEMM engine, fused MLP (mlp.hpp) and ConvLSTM scan kernels */
-    int gemm_xcd_panels;      /* 1: panels of long NT tile walks are dealt per XCD (gemm.hpp tile_of mode 3) */
-    int wgrad_bn;             /* output-tile width of the split-K weight-gradient kernel: 0 = by shape, 64, 128 */
-    int wgrad_blocks;         /* target workgroups of a split-K weight-gradient launch (512 = two per CU) */
     int wgrad_slice_tokens;   /* minimum tokens per K slice (8192; >= 64) */
     int ppgemm;               /* 1: bf16 products whose shape fits take the 256x256 LDS-DMA kernels (ppgemm.hpp, ppgemm_tn.hpp) */
     int ppgemm_min_m;         /* ... from this many token rows (4096) */
@@ -70,12 +67,9 @@ typedef struct RvtTuning {
     int ppgemm_tn_items;      /* token slices per output tile of ppgemm_tn (0 = fill the chip) */
     int one_per_cu_grid;      /* grid cap of the one-workgroup-per-CU kernels: stem forward / weight gradient, chain-MLP weight gradient (0 = 256) */
     int stem;                 /* 1: uint8 planes take the stem kernels (stem.hpp) */
-    int stem_depth;           /* software-pipeline depth of the stem forward's plane loads: 4 or 5 */
-    int mlp_tm;               /* token-tile height of the LDS-staged fused MLP at bf16 C = 64: 0 / 64, or 128 */
     int mlp_chain;            /* 1: C = 64 MLP halves take the register-chained kernels (mlp_chain.hpp) */
     int mlp_chain_wgrad;      /* 1: ... including the weight-gradient half */
     int chain_resident;       /* persistent workgroups of the chain-MLP / dgrad_ln kernels */
-    int attn_block_resident;  /* persistent workgroups of the fused attention half (attn_block.hpp) */
     int dgrad_ln;             /* 1: rvt_linear_dgrad_ln_supported may say yes */
     /* ---- routes taken by the host-side stage driver (rvt_amd/stage.py reads them back through rvt_get_tuning) ---- */
     int route_fused_mlp;      /* -1: by measurement (C = 64 all halves, C = 128 forward); 0: op-by-op; 1: every supported half */
@@ -84,8 +78,6 @@ typedef struct RvtTuning {
     int route_lstm_scan;      /* -1: time loop in the kernel where the weights stay on chip; 0: one launch per step; 1: every built width */
     int route_lstm_scan_wgrad;/* 1: ConvLSTM weight gradients inside the reverse scan where built */
     int route_conv_dgrad4;    /* 1: 3x3 / stride-2 conv input gradient as one gather GEMM */
-    int route_wgrad_stream;   /* 1: weight-gradient launches on a second HIP stream */
-    int lstm_scan_v2;         /* 1: bf16 C = 64 ConvLSTM scans take the T-form kernels of lstm_scan2.hpp (0: lstm_scan.hpp, A/B) */
     int route_stage_driver;   /* 1: the no-grad forward of rvt_amd takes rvt_stage_seq_fwd (one call per stage); 0: the Python host loop */
     int route_mlp_store_pre;  /* 1: the LDS-staged fused MLP forward (C = 128) saves the pre-activation h only, not GELU(h) and GELU'(h); default 0: measured slower (GELU on load costs more than the bytes it saves, profiles/r4/microbench_mlp128.txt) */
     int route_mlp_bwd_both;   /* 1: stage-1 MLP backward = ONE launch (rvt_mlp_bwd_recompute_both) instead of dgrad + wgrad */
@@ -101,7 +93,7 @@ typedef struct RvtTuning {
     int route_attn_preln;     /* 1 (round 6): the backward of a stage's first block also carries the gradient through the down-sampling LayerNorm where no token mask sits between them: rvt_attn_block_bwd_preln on the fused attention half, rvt_linear_dgrad_preln on the op-by-op route (C <= 128); 0: separate rvt_layernorm_bwd */
     int conv_fwd_pp;          /* 1 (round 6): 3 x 3 / stride 2 / pad 1 convs with Cin % 64 == 0 and Cout % 256 == 0 take the 256-wide kernel with the im2col gather in its load stream (ppgemm.hpp GATHER = 2); 0: the 128-row engine */
 } RvtTuning;
-#define RVT_TUNING_DEFAULTS {(int)sizeof(RvtTuning), 0, 1, 0, 512, 8192, 1, 4096, 0, 0, 0, 0, 1, 4, 0, 1, 1, 0, 0, 1, -1, 1, 1, -1, 1, 1, 0, 1, 1, 0, 1, 1, 1, 1, 1, 3, 1, 1, 1, 1, 1}
+#define RVT_TUNING_DEFAULTS {(int)sizeof(RvtTuning), 0, 8192, 1, 4096, 0, 0, 0, 0, 1, 1, 1, 0, 1, -1, 1, 1, -1, 1, 1, 1, 0, 1, 1, 1, 1, 1, 3, 1, 1, 1, 1, 1}
 void rvt_tuning_defaults(RvtTuning* t);        /* fills *t with the production defaults */
 int rvt_get_tuning(RvtTuning* t);              /* t->struct_bytes must be set by the caller */
 int rvt_set_tuning(const RvtTuning* t);
@@ -411,7 +403,7 @@ typedef struct RvtStageRoutes {
     int mlp_bwd_dgrad;                    /* route 2: both MLP input gradients + the norm2 backward in one launch (rvt_mlp_bwd_dgrad) */
     int lstm_scan3_rb;                    /* route 3: the tile factor of forward, dump buffers and reverse scan (1 or 2); 0 otherwise */
     int driver_covers;                    /* 1: the C-side driver of this direction runs these routes (no token mask, no DWS-ConvLSTM; training:
-                                             also RvtTuning.route_wgrad_stream = 0 and mlp_route != 2); 0: the host loop does */
+                                             also mlp_route != 2); 0: the host loop does */
 } RvtStageRoutes;
 /* save: the forward keeps activations for a backward.  has_dws / has_token_mask: the stage has a DWS-ConvLSTM / a token mask is applied. */
 int rvt_stage_routes(const RvtStageDesc* desc, int T, int B, int save, int has_dws, int has_token_mask, RvtStageRoutes* out);

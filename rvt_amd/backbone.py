@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, tuning
-from .stage import SideStream, StageGeom, stage_seq_backward, stage_seq_forward
+from .stage import StageGeom, stage_seq_backward, stage_seq_forward
 from .weights import ModelWeights, param_signature, param_versions, round8
 
 Tensor = torch.Tensor
@@ -365,11 +365,6 @@ class _BackboneSeqFn(torch.autograd.Function):
                     if m_:
                         p[n].grad = p[n].grad.clone()
             sg.zero(keep_params=acc)
-        # weight-gradient GEMMs run on a side stream, joined at the end of every stage (measured: deferring the join to
-        # the end of backward is slower — 162 vs 145 ms/step — the caching allocator cannot recycle the operands the side
-        # stream still holds and the extra resident work competes with the next stage's critical path)
-        side = SideStream(ctx.svs[ns - 1].y0)
-        held_hooks: List[int] = []      # deferred mode: stages whose weight gradients are still queued / running on the side stream
 
         def call_hook(sj: int) -> None:
             if hook is None:
@@ -382,10 +377,6 @@ class _BackboneSeqFn(torch.autograd.Function):
                 hook(sj, mw.grads[sj].param_region)
         for si in range(ns - 1, -1, -1):
             g = geoms[si]
-            # deferred weight gradients (tuning.route_wgrad_stream = 2): those of the stage above start now, beside this stage's reverse
-            # scan; this stage queues its own iff the stage below scans per step (a chip-filling scan kernel leaves nothing to fill)
-            side.flush()
-            side.deferring = side.defer_mode and si > 0 and ctx.svs[si - 1].routes.lstm_route == 0
             dF, dC = gout[2 * si], gout[2 * si + 1]
             if si == ns - 1:
                 dH = None if dF is None else _to_cl(dF, dt)
@@ -398,24 +389,14 @@ class _BackboneSeqFn(torch.autograd.Function):
                 gp = geoms[si - 1]
                 prev_cot = _to_cl(gout[2 * (si - 1)], dt).view(T * B, gp.H, gp.W, gp.C)
             d_in, dh0, dc0 = stage_seq_backward(mw.stages[si], g, ctx.svs[si], dH, dc_last, T, B, si > 0, prev_cot,
-                                                mw.grads[si], f'stages.{si}.', side=side,
+                                                mw.grads[si], f'stages.{si}.',
                                                 finalize=lambda si=si: mw.finalize_stage_grads(si))
             d_from_above = d_in
-            for sj in held_hooks:         # (stage_seq_backward ended with side.join(): the stage above is complete now)
-                call_hook(sj)
-            held_hooks = []
-            if side.deferring:
-                held_hooks.append(si)
-            else:
-                call_hook(si)
+            call_hook(si)                 # every parameter gradient of the stage is final
             if ctx.needs_input_grad[4 + 2 * si]:
                 state_grads[2 * si] = dh0.permute(0, 3, 1, 2)
                 state_grads[2 * si + 1] = dc0.permute(0, 3, 1, 2)
             ctx.svs[si] = None
-        if side.flush():                  # (cannot happen with the rule above - stage 1 never defers - but a queue must never be dropped)
-            side.join()
-        for sj in held_hooks:
-            call_hook(sj)
         finish = getattr(mod, '_stage_grad_finish', None)
         if finish is not None:            # data parallel: order everything downstream after the per-stage all-reduces
             finish()

@@ -98,10 +98,9 @@ int rvt_attn_block_supported(int dtype, int C, int dim_head, int L) {
 // waves per workgroup: what the LDS holds (weights + per-wave backward scratch)
 template <class T, int NB> struct AbWaves { static constexpr int V = sizeof(T) == 2 ? (NB == 2 ? 4 : 3) : 2; };
 template <class K> static int ab_grid(K kernel, int threads, int n_part, int wpb) {
-    const int resident_override = tuning().attn_block_resident;
     const int per_cu = resident_per_cu(kernel, threads, 1);
     const int want = (n_part + wpb - 1) / wpb;
-    return imax(1, imin(want, resident_override > 0 ? resident_override : 256 * per_cu));
+    return imax(1, imin(want, 256 * per_cu));
 }
 template <class T, int NB, bool LN>
 static void launch_ab_fwd(const void* x, void* xmid, void* a_out, const float* ln_w, const float* ln_b, const void* wqkv,

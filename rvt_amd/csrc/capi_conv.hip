@@ -10,7 +10,7 @@ size_t rvt_wgrad_workspace_floats(int dtype, int out_rows, int out_cols, int tok
         const size_t pc = ppgemm_tn_conv_ws_floats(tokens, out_rows, out_cols);  // rvt_conv_wgrad on the same kernel (K a multiple of 64 only)
         if (pc > pp) pp = pc;
     }
-    int bn = wgrad_bn(out_cols);
+    int bn = out_cols <= 64 ? 64 : 128;      // DISPATCH_BN
     int bk = dtype == RVT_F32 ? TileGeom<float>::BK : TileGeom<bf16>::BK;
     size_t n = wgrad_ws_floats(out_rows, out_cols, tokens, bn, bk, want_colsum);
     if (out_rows <= 64) {                    // rvt_conv_wgrad may compute the transposed product (see there)
@@ -103,7 +103,7 @@ int rvt_conv_wgrad(const void* in, const void* dy, float* dw, float* ws, int dty
             constexpr int BN = 64;
             launch_wgrad<T, BN>(b, a, XfNone(), dw, nullptr, ws, b.cols, Cout, b.rows, st, true);
         } else {
-            DISPATCH_WGRAD_BN(b.cols, (launch_wgrad<T, BN>(a, b, XfNone(), dw, nullptr, ws, Cout, b.cols, b.rows, st)));
+            DISPATCH_BN(b.cols, (launch_wgrad<T, BN>(a, b, XfNone(), dw, nullptr, ws, Cout, b.cols, b.rows, st)));
         }
     });
     return check_launch("conv_wgrad");

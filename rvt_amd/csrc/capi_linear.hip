@@ -125,7 +125,7 @@ int rvt_linear_wgrad(const void* dy, const void* x, float* dw, float* dy_colsum,
     DISPATCH_DTYPE(dtype, {
         PlainSrc<T> a{(const T*)dy, N, M, N};
         PlainSrc<T> b{(const T*)x, K, M, K};
-        DISPATCH_WGRAD_BN(K, {
+        DISPATCH_BN(K, {
             if (gelu_in) launch_wgrad<T, BN>(a, b, XfGelu(), dw, dy_colsum, ws, N, K, M, st);
             else launch_wgrad<T, BN>(a, b, XfNone(), dw, dy_colsum, ws, N, K, M, st);
         });

@@ -50,7 +50,7 @@ int rvt_lstm_wgrad(const void* dz, const void* x, const void* h_prev, float* dw,
     DISPATCH_DTYPE(dtype, {
         PlainSrc<T> a{(const T*)dz, 4 * C, M, 4 * C};
         ConcatSrc<T> b{(const T*)x, (const T*)h_prev, C, M, 2 * C};
-        DISPATCH_WGRAD_BN(2 * C, (launch_wgrad<T, BN>(a, b, XfNone(), dw, dz_colsum, ws, 4 * C, 2 * C, M, st)));
+        DISPATCH_BN(2 * C, (launch_wgrad<T, BN>(a, b, XfNone(), dw, dz_colsum, ws, 4 * C, 2 * C, M, st)));
     });
     return check_launch("lstm_wgrad");
 }

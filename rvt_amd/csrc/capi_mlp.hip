@@ -18,11 +18,7 @@ int rvt_mlp_fused_supported(int dtype, int C) {
 }
 
 // tile height and resident workgroups per CU of the fused MLP kernels (LDS: ~41 KiB at bf16 C=64 TM=64, ~57 KiB at C=128)
-static int mlp_tm(int dtype, int C) {
-    const int tm_override = tuning().mlp_tm;     // tuning knob (bf16 C=64 only)
-    if (dtype == RVT_BF16 && C == 64 && tm_override == 128) return 128;
-    return 64;
-}
+static const int MLP_TM = 64;
 }  // extern "C"
 template <class K> static int mlp_grid(K kernel, int M, int tm) {
     const int resident_override = tuning().gemm_resident;
@@ -142,16 +138,14 @@ int rvt_mlp_fwd(const void* xmid, void* xout, void* g_out, void* gp_out, void* v
         });
         return check_launch("mlp_fwd(chain)");
     }
-    const int tm = mlp_tm(dtype, C);
-#define RVT_MLP_FWD(TT, CC, TMM)                                                                                           \
-    hipLaunchKernelGGL((mlp_fwd_kernel<TT, CC, TMM>), dim3(mlp_grid(mlp_fwd_kernel<TT, CC, TMM>, M, tm)), dim3(256), 0, st, \
+#define RVT_MLP_FWD(TT, CC)                                                                                                \
+    hipLaunchKernelGGL((mlp_fwd_kernel<TT, CC, MLP_TM>), dim3(mlp_grid(mlp_fwd_kernel<TT, CC, MLP_TM>, M, MLP_TM)), dim3(256), 0, st, \
                        (const TT*)xmid, (TT*)xout, (TT*)g_out, (TT*)gp_out, (TT*)v2_out, ln_w, ln_b, (const TT*)w1, b1,    \
                        (const TT*)w2,                                                                                       \
                        b2, gamma, M, eps)
-    if (dtype == RVT_BF16 && C == 64 && tm == 128) RVT_MLP_FWD(bf16, 64, 128);
-    else if (dtype == RVT_BF16 && C == 64) RVT_MLP_FWD(bf16, 64, 64);
-    else if (dtype == RVT_BF16 && C == 128) RVT_MLP_FWD(bf16, 128, 64);
-    else RVT_MLP_FWD(float, 64, 64);
+    if (dtype == RVT_BF16 && C == 64) RVT_MLP_FWD(bf16, 64);
+    else if (dtype == RVT_BF16 && C == 128) RVT_MLP_FWD(bf16, 128);
+    else RVT_MLP_FWD(float, 64);
 #undef RVT_MLP_FWD
     return check_launch("mlp_fwd");
 }
@@ -161,15 +155,13 @@ int rvt_mlp_bwd_dgrad(const void* dxout, const void* gp, const void* xmid, void*
                       void* stream) {
     RVT_CHECK(rvt_mlp_fused_supported(dtype, C), "mlp_bwd_dgrad: fused MLP not built for dtype=%d C=%d", dtype, C);
     hipStream_t st = (hipStream_t)stream;
-    const int tm = mlp_tm(dtype, C);
-#define RVT_MLP_BWD(TT, CC, TMM)                                                                                          \
-    hipLaunchKernelGGL((mlp_bwd_dgrad_kernel<TT, CC, TMM>), dim3(mlp_grid(mlp_bwd_dgrad_kernel<TT, CC, TMM>, M, tm)),       \
+#define RVT_MLP_BWD(TT, CC)                                                                                               \
+    hipLaunchKernelGGL((mlp_bwd_dgrad_kernel<TT, CC, MLP_TM>), dim3(mlp_grid(mlp_bwd_dgrad_kernel<TT, CC, MLP_TM>, M, MLP_TM)), \
                        dim3(256), 0, st, (const TT*)dxout, (const TT*)gp, (const TT*)xmid, (TT*)dh, (TT*)dxmid, ln_w,      \
                        (const TT*)w2g_t, (const TT*)w1_t, dln_w, dln_b, M, eps)
-    if (dtype == RVT_BF16 && C == 64 && tm == 128) RVT_MLP_BWD(bf16, 64, 128);
-    else if (dtype == RVT_BF16 && C == 64) RVT_MLP_BWD(bf16, 64, 64);
-    else if (dtype == RVT_BF16 && C == 128) RVT_MLP_BWD(bf16, 128, 64);
-    else RVT_MLP_BWD(float, 64, 64);
+    if (dtype == RVT_BF16 && C == 64) RVT_MLP_BWD(bf16, 64);
+    else if (dtype == RVT_BF16 && C == 128) RVT_MLP_BWD(bf16, 128);
+    else RVT_MLP_BWD(float, 64);
 #undef RVT_MLP_BWD
     return check_launch("mlp_bwd_dgrad");
 }

@@ -161,9 +161,8 @@ int rvt_stage_routes(const RvtStageDesc* dp, int T, int B, int save, int has_dws
     }
     r.lstm_scan_wgrad = r.lstm_route == 1 && tn.route_lstm_scan_wgrad != 0 && rvt_lstm_scan_bwd_ws_floats(dt, C, Ms) > 0;
     r.conv_dgrad4 = tn.route_conv_dgrad4 != 0 && rvt_conv_dgrad4_supported(dt, d.H_in, d.W_in, d.Cin, C, d.k, d.stride, d.pad, T * B);
-    // what the C-side drivers sequence; the training driver also leaves the second weight-gradient stream and the saving fused-MLP
-    // flavour to the host loop
-    r.driver_covers = !has_dws && !has_token_mask && (!save || (tn.route_wgrad_stream == 0 && r.mlp_route != 2));
+    // what the C-side drivers sequence; the training driver also leaves the saving fused-MLP flavour to the host loop
+    r.driver_covers = !has_dws && !has_token_mask && (!save || r.mlp_route != 2);
     *out = r;
     return 0;
 }

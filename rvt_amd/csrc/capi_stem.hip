@@ -7,10 +7,7 @@ using namespace rvt;
 extern "C" {
 // ---- the stem on the uint8 planes (stem.hpp) ----
 static const int STEM_FWD_PB = 4;
-static int stem_fwd_depth() {                          // software-pipeline depth of the forward's plane loads (k-steps in flight)
-    const int d = tuning().stem_depth;
-    return d == 5 ? 5 : 4;
-}
+static const int STEM_FWD_DEPTH = 4;                   // software-pipeline depth of the forward's plane loads (k-steps in flight)
 
 int rvt_stem_supported(int dtype, int src_u8, int Cin, int Cout, int k, int stride, int pad, int w) {
     const int on = tuning().stem;
@@ -25,7 +22,7 @@ int rvt_stem_fwd(const void* src, const void* w, const float* ln_w, const float*
     StemGeom g;
     g.F = F; g.Cin = Cin; g.cp = cp; g.h = h; g.w = wd;
     g.Ho = (H + 2 * STEM_PAD - STEM_K) / STEM_STRIDE + 1; g.Wo = (W + 2 * STEM_PAD - STEM_K) / STEM_STRIDE + 1;
-    const int D = stem_fwd_depth();
+    const int D = STEM_FWD_DEPTH;
     g.NR = Cin * STEM_K; g.KS = (g.NR + 1) / 2; g.KSP = (g.KS + D - 1) / D * D;
     RVT_CHECK(g.KSP <= STEM_KSP_MAX, "stem_fwd: %d k-steps do not fit the LDS", g.KSP);
     g.XS = (g.Wo + 31) / 32; g.OG = (g.Ho + STEM_FWD_PB - 1) / STEM_FWD_PB;
@@ -33,12 +30,8 @@ int rvt_stem_fwd(const void* src, const void* w, const float* ln_w, const float*
     g.n_items = F * og8;
     g.dOG = FastDiv(og8); g.d7 = FastDiv(STEM_K); g.dXS = FastDiv(g.XS);
     const int grid = one_per_cu_grid(g.n_items);
-    if (D == 5)
-        hipLaunchKernelGGL((stem_fwd_kernel<STEM_FWD_PB, 5>), dim3(grid), dim3(512), 0, (hipStream_t)stream, (const uint8_t*)src,
-                           (const bf16*)w, ln_w, ln_b, (bf16*)y0, (bf16*)x, g, eps);
-    else
-        hipLaunchKernelGGL((stem_fwd_kernel<STEM_FWD_PB, 4>), dim3(grid), dim3(512), 0, (hipStream_t)stream, (const uint8_t*)src,
-                           (const bf16*)w, ln_w, ln_b, (bf16*)y0, (bf16*)x, g, eps);
+    hipLaunchKernelGGL((stem_fwd_kernel<STEM_FWD_PB, STEM_FWD_DEPTH>), dim3(grid), dim3(512), 0, (hipStream_t)stream, (const uint8_t*)src,
+                       (const bf16*)w, ln_w, ln_b, (bf16*)y0, (bf16*)x, g, eps);
     return check_launch("stem_fwd");
 }
 

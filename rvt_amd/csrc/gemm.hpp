@@ -1059,8 +1059,7 @@ inline void launch_gemm(const ASrc& as, const AXf& axf, const BSrc& bs, const BX
         if (total > resident) gx = resident;
         panel_major = (n_tiles > 1 && m_tiles >= 4 * gx) ? 1 : 0;
         if (ASrc::SPATIAL_REUSE && total > gx && (gx & 7) == 0) panel_major = 2;
-        const int xcd_panels = g_tuning.gemm_xcd_panels;    // (A/B knob)
-        if (panel_major == 0 && n_tiles > 1 && xcd_panels && total >= 8 * gx) {
+        if (panel_major == 0 && n_tiles > 1 && total >= 8 * gx) {
             // XCD-grouped panels (tile_of, mode 3).  Only for long tile walks: the per-XCD lists differ by up to one panel, which
             // on a one- or two-round launch (the per-step ConvLSTM GEMMs: measured +16 % on rvt_lstm_dgrad) is a whole extra round.
             gx = (gx + 7) & ~7;

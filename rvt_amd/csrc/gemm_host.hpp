@@ -7,19 +7,12 @@
 
 namespace rvt {
 // split the token contraction of a weight gradient so that the launch fills the chip
-// output-tile width of the weight-gradient kernels
-static inline int wgrad_bn(int out_cols) {
-    const int forced = tuning().wgrad_bn;                   // tuning knob
-    if (forced == 64 || forced == 128) return forced;
-    return out_cols <= 64 ? 64 : 128;
-}
 static inline int wgrad_ksplit(int out_rows, int out_cols, int tokens, int bn) {
-    const int split_override = tuning().wgrad_blocks;   // tuning knob
     int tiles = ((out_rows + 127) / 128) * ((out_cols + bn - 1) / bn);
     // as many workgroups as are resident at once: two per CU (measured on dW[512][128], 1.9 M tokens: 0.51 ms at 512
     // workgroups vs 0.75 at 256); but at least 8192 tokens per K slice, or the partial tiles and their reduction
     // cost more than the extra parallelism brings (dW[128][128]: 0.32 ms at 256 slices, 0.42 at 512)
-    int want = imax(1, (split_override > 0 ? split_override : 512) / imax(1, tiles));
+    int want = imax(1, 512 / imax(1, tiles));
     const int slice_tokens = imax(64, tuning().wgrad_slice_tokens);   // (tests: small)
     int maxs = imax(1, tokens / slice_tokens);
     // problems whose 8192-token slices do not fill the chip once (RVT-Tiny on Gen1: 104 workgroups at stage 1, 24 at stage 2,
@@ -61,12 +54,6 @@ static void launch_wgrad(const ASrc& a, const BSrc& b, const BXf& bxf, float* ou
     if (colsum_out) fj.add(ws_cs, colsum_out, ns, (size_t)Mg, (size_t)Mg);
     launch_fold_jobs(fj, st);
 }
-
-#define DISPATCH_WGRAD_BN(N, ...)                                    \
-    do {                                                             \
-        if (wgrad_bn(N) == 64) { constexpr int BN = 64; __VA_ARGS__; } \
-        else { constexpr int BN = 128; __VA_ARGS__; }                \
-    } while (0)
 
 // Route of a bf16 "row, k" x "row, k" product: the 256 x 256 LDS-DMA ping-pong kernel (ppgemm.hpp) where its tile shape
 // divides the problem and there are enough rows to fill it, else the 128-row register-staged engine (gemm.hpp).

@@ -3,7 +3,7 @@
 The reference removes its per-op launch overhead with ``torch.compile(mode='reduce-overhead')`` (CUDA graphs under a
 tracing compiler; maxvit_rnn.py:43-51).  Here nothing is traced: every kernel behind include/rvt_hip.h takes an explicit
 stream, allocates nothing and synchronises nothing, so the step — prepack, weight pack, four stage-major forwards, the
-BPTT backward with its weight-gradient side stream, the gradient fold, (the RCCL all-reduces,) the fused optimizer — is
+BPTT backward, the gradient fold, (the RCCL all-reduces,) the fused optimizer — is
 captured once as it is issued and replayed as ONE graph launch.  The optimizer is torch's fused AdamW (capturable=True) or
 rvt_amd.optim.AdamW: gradient clip by value + AdamW + OneCycleLR as one launch of this library, with the step count and therefore
 the schedule position on the device, so a replay needs nothing refreshed by the host.  Shapes are static per (T, B, resolution) bucket, which

@@ -22,86 +22,6 @@ from . import ops, stage_driver, tuning
 from .weights import StageGrads, StageWeights
 
 
-
-class SideStream:
-    """Weight-gradient GEMMs are off the critical path of backward (nothing downstream reads dW until the optimizer) and
-    are read-only streams, while the input-gradient chain they hang off is write-heavy; running them on a second HIP
-    stream lets the two share the chip.  Ordering is by events in both directions: run() makes the side stream wait for
-    everything the main stream has issued so far (the producers of the operands), join() makes the main stream wait for
-    the side stream.  Operands are kept alive here until join() instead of being record_stream()-ed: a recorded block
-    sits in the caching allocator's event limbo after its last reference dies and the pool grows by gigabytes per stage
-    (measured: 280 GiB reserved for 75 GiB live, then allocator retries of seconds inside a step)."""
-    _streams = {}
-
-    def __init__(self, like: Tensor):
-        # off by default since round 2: with the fused stage-1 kernels the step on ONE stream costs exactly the sum of its
-        # kernels' isolated times (98.6 ms, profiles/r2/op_breakdown_serial_r2i.txt) and the second stream only adds
-        # contention (100.7 ms); tuning.route_wgrad_stream = 1 re-enables it.
-        # route_wgrad_stream = 2 (round 5): DEFERRED - the weight-gradient launches of a stage whose successor in the backward
-        # order opens with a per-step reverse ConvLSTM scan (42 launches of 23 - 90 tiles on 256 CUs) are queued and start on
-        # the side stream when that scan starts, i.e. they fill a chip that is two thirds idle instead of competing with full grids.
-        mode = tuning.get('route_wgrad_stream') if like.is_cuda else 0
-        self.enabled = mode in (1, 2)
-        self.defer_mode = mode == 2
-        self.deferring = False          # set per stage by the backward driver (rvt_amd/backbone.py)
-        self._queue = []
-        self._flushed = False
-        self._keep = []
-        if self.enabled:
-            key = like.device.index
-            if key not in SideStream._streams:
-                SideStream._streams[key] = torch.cuda.Stream(device=like.device)
-            self.stream = SideStream._streams[key]
-            self.main = torch.cuda.current_stream(like.device)
-
-    def run(self, fn, *operands):
-        if not self.enabled:
-            return fn()
-        if self.defer_mode:
-            if not self.deferring:
-                return fn()
-            self._queue.append(fn)
-            self._keep.extend(t for t in operands if t is not None)
-            return None
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        self._keep.extend(t for t in operands if t is not None)
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_event(ev)
-            return fn()
-
-    def flush(self) -> bool:
-        """Deferred mode: start the queued launches on the side stream, ordered after everything the main stream has issued."""
-        if not (self.enabled and self.defer_mode and self._queue):
-            return False
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_event(ev)
-            for fn in self._queue:
-                fn()
-        # the closures hold the last references to what their launches read (the stage's saved activations: backbone.py has
-        # already dropped ctx.svs[si]); they stay alive until join() has ordered the main stream behind the side stream -
-        # dropping them here would hand the blocks back to the caching allocator while the side-stream kernels are pending
-        self._keep.extend(self._queue)
-        self._queue = []
-        self._flushed = True
-        return True
-
-    def join(self):
-        if not self.enabled:
-            return
-        if self.defer_mode:
-            if self._flushed:
-                self.main.wait_stream(self.stream)
-                self._flushed = False
-                if not self._queue:
-                    self._keep.clear()
-            return
-        self.main.wait_stream(self.stream)
-        self._keep.clear()
-
-
 @dataclass
 class StageGeom:
     C: int
@@ -279,12 +199,11 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
 
 def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optional[Tensor], dc_last: Optional[Tensor],
                        T: int, B: int, need_input_grad: bool, prev_cot: Optional[Tensor],
-                       sg: StageGrads, pre: str, side: Optional[SideStream] = None,
-                       finalize=None) -> Tuple[Optional[Tensor], Tensor, Tensor]:
+                       sg: StageGrads, pre: str, finalize=None) -> Tuple[Optional[Tensor], Tensor, Tensor]:
     """dH: (T,B,H,W,C) cotangent of Hall[1:] (None = zeros); dc_last: (B,H,W,C) fp32 cotangent of Call[T].
     prev_cot: cotangent already attached to this stage's INPUT frames (T*B,H_in,W_in,Cin) (added to the conv dgrad).
     Parameter gradients are ACCUMULATED into the views of the stage's fp32 bucket `sg` (rvt_amd/weights.py); `finalize`
-    (LayerScale fold + conv unpack, two table launches) runs behind the weight-gradient GEMMs on their stream.
+    (LayerScale fold + conv unpack, two table launches) runs behind the last weight-gradient GEMM of the stage.
     Returns (d_input or None, dh0, dc0)."""
     F_ = T * B
     H, W, C = g.H, g.W, g.C
@@ -344,15 +263,10 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                 ops.lstm_dgrad(dz[t], sw.lstm_wt, dx[t], dhc[t])
                 ops.dwconv(dhc[t], wh, None, dws['k'], transpose=True, out=nxt)
             dh_rec = nxt
-    if side is None:
-        side = SideStream(dx)
-    h_seg = sv.Hall[:T].reshape(F_, H, W, C) if dws is None else sv.hconv.view(F_, H, W, C)
-
-    def lstm_wgrad_fn(dz=dz, h_seg=h_seg):          # (bound now: `dz` is deleted below and the launch may be deferred)
+    if not lstm_wgrad_done:
+        h_seg = sv.Hall[:T].reshape(F_, H, W, C) if dws is None else sv.hconv.view(F_, H, W, C)
         ops.lstm_wgrad(dz.view(F_, H, W, 4 * C), sv.xin_lstm, h_seg, G(pre + 'lstm.conv1x1.weight').view(4 * C, 2 * C),
                        G(pre + 'lstm.conv1x1.bias'))
-    if not lstm_wgrad_done:
-        side.run(lstm_wgrad_fn, dz, sv.xin_lstm, h_seg)
     dh0, dc0 = dh_rec, dc_rec
     dx = dx.view(F_, H, W, C)
     if dws is not None:
@@ -384,27 +298,21 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
             assert (s['hg'] is None) == (r.mlp_route == 1) and (s['qkv'] is None) == bool(r.attn_block)
             if r.mlp_route == 1:
                 # everything on chip: recompute, both input-gradient products, LayerNorm backward and the fc1 / fc2 weight
-                # gradients (accumulated in registers) in one kernel; nothing for the weight-gradient stream to do
-                # two launches, cut along the critical path: the input-gradient half here, the weight-gradient half (which
-                # needs all 2 x 64 x 256 accumulators) on the weight-gradient stream
-                # (round 4: ONE launch where the library supports it — the weight-gradient kernel hands dh to two waves that form
-                # dh W1, LayerNorm backward in the staging role; otherwise)
+                # gradients (accumulated in registers) on chip.  ONE launch where the library supports it (round 4: the
+                # weight-gradient kernel hands dh to two waves that form dh W1, LayerNorm backward in the staging role);
+                # otherwise two: the weight-gradient half (which needs all 2 x 64 x 256 accumulators), then the input-gradient half
                 if r.mlp_bwd_both:
                     dxmid = ops.mlp_bwd_recompute_both(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'], bw['fc2_wt'],
                                                        bw['fc1_wt'], dn2w, dn2b, G(bp + 'mlp.net.0.0.weight'),
                                                        G(bp + 'mlp.net.0.0.bias'), G(bp + 'S2'), G(bp + 'cs2'), g.eps)
                 else:
-                    def mlp_wgrad_fn(dx=dx, s=s, bw=bw, bp=bp):
-                        ops.mlp_bwd_recompute_wgrad(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'],
-                                                    bw['fc2_wt'], G(bp + 'mlp.net.0.0.weight'), G(bp + 'mlp.net.0.0.bias'),
-                                                    G(bp + 'S2'), G(bp + 'cs2'), g.eps)
-                    side.run(mlp_wgrad_fn, dx, s['xmid'])
+                    ops.mlp_bwd_recompute_wgrad(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'],
+                                                bw['fc2_wt'], G(bp + 'mlp.net.0.0.weight'), G(bp + 'mlp.net.0.0.bias'),
+                                                G(bp + 'S2'), G(bp + 'cs2'), g.eps)
                     dxmid = ops.mlp_bwd_recompute_dgrad(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'],
                                                         bw['fc2_wt'], bw['fc1_wt'], dn2w, dn2b, g.eps)
             else:
-                def fc2_wgrad_fn(dx=dx, s=s, bp=bp):
-                    ops.linear_wgrad(dx, s['hg'], G(bp + 'S2'), gelu_in=bool(r.mlp_store_pre), colsum_out=G(bp + 'cs2'))
-                side.run(fc2_wgrad_fn, dx, s['hg'])
+                ops.linear_wgrad(dx, s['hg'], G(bp + 'S2'), gelu_in=bool(r.mlp_store_pre), colsum_out=G(bp + 'cs2'))
                 fused = bool(r.mlp_bwd_dgrad)
                 if fused:       # fc2 dgrad * gp, fc1 dgrad and LayerNorm-2 backward (+ residual) in one kernel
                     dhd, dxmid = ops.mlp_bwd_dgrad(dx, s['hgp'], s['xmid'], bw['n2_w'], bw['fc2_wt'], bw['fc1_wt'], dn2w,
@@ -413,10 +321,9 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                     dhd = ops.linear_dgrad(dx, bw['fc2_wt'], gelu_pre=s['hg'])
                 else:
                     dhd = ops.linear_dgrad(dx, bw['fc2_wt'], mul=s['hgp'])
-                def fc1_wgrad_fn(dhd=dhd, s=s, bw=bw, bp=bp):
-                    v2 = s['v2'] if s['v2'] is not None else ops.layernorm_fwd(s['xmid'], bw['n2_w'], bw['n2_b'], g.eps)
-                    ops.linear_wgrad(dhd, v2, G(bp + 'mlp.net.0.0.weight'), colsum_out=G(bp + 'mlp.net.0.0.bias'))
-                side.run(fc1_wgrad_fn, dhd, s['xmid'])
+                v2 = s['v2'] if s['v2'] is not None else ops.layernorm_fwd(s['xmid'], bw['n2_w'], bw['n2_b'], g.eps)
+                ops.linear_wgrad(dhd, v2, G(bp + 'mlp.net.0.0.weight'), colsum_out=G(bp + 'mlp.net.0.0.bias'))
+                del v2
                 if not fused:
                     if r.dgrad_ln_fc1:     # fc1 input gradient + norm2 backward + residual: one launch
                         dxmid = ops.linear_dgrad_ln(dhd, bw['fc1_w'], s['xmid'], dx, bw['n2_w'], dn2w, dn2b, g.eps)
@@ -426,9 +333,7 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                         del dv2
                 del dhd
             # attention branch: xmid = xin + g1 * (a Wp^T + bp)
-            def proj_wgrad_fn(dxmid=dxmid, s=s, bp=bp):
-                ops.linear_wgrad(dxmid, s['a'], G(bp + 'S1'), colsum_out=G(bp + 'cs1'))
-            side.run(proj_wgrad_fn, dxmid, s['a'])
+            ops.linear_wgrad(dxmid, s['a'], G(bp + 'S1'), colsum_out=G(bp + 'cs1'))
             if r.attn_block:
                 # fused: proj / attention / qkv input gradients and the norm1 backward in one launch (from the block input)
                 has_n1 = bw['n1_w'] is not None
@@ -447,17 +352,13 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                                                      G(bp + 'norm1.bias') if has_n1 else None, F_, H, W, C, g.dim_head, g.ph, g.pw,
                                                      window, g.eps)
                 u = s['xin'] if u is None else u
-                def qkv_wgrad_fused_fn(dqkv=dqkv, u=u, bp=bp):
-                    ops.linear_wgrad(dqkv, u, G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
-                side.run(qkv_wgrad_fused_fn, dqkv, u)
+                ops.linear_wgrad(dqkv, u, G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
                 del dqkv, dxmid, u
                 continue
             da = ops.linear_dgrad(dxmid, bw['proj_wt'])
             dqkv = ops.attn_bwd(s['qkv'], da, F_, H, W, C, g.dim_head, g.ph, g.pw, window)
             del da
-            def qkv_wgrad_fn(dqkv=dqkv, s=s, bp=bp):
-                ops.linear_wgrad(dqkv, s['u'], G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
-            side.run(qkv_wgrad_fn, dqkv, s['xin'])
+            ops.linear_wgrad(dqkv, s['u'], G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
             if bi_flat == 0 and r.attn_preln:
                 # the stage's first block: qkv input gradient + residual cotangent carried through the down-sampling norm (one launch)
                 dy0_fused = ops.linear_dgrad_preln(dqkv, bw['qkv_w'], sv.y0, dxmid, sw.ln_w, G(pre + 'downsample_cf2cl.norm.weight'),
@@ -482,19 +383,16 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
     else:
         dy0 = ops.layernorm_bwd(sv.y0, sw.ln_w, dx, None, G(pre + 'downsample_cf2cl.norm.weight'),
                                 G(pre + 'downsample_cf2cl.norm.bias'), g.eps)
-    def conv_wgrad_fn(dy0=dy0):
-        if sv.inp.dtype == torch.uint8:
-            ops.stem_wgrad(sv.inp, dy0, G('raw/conv'), g.H_in, g.W_in)
-        else:
-            ops.conv_wgrad(sv.inp, dy0, G('raw/conv'), g.k, g.stride, g.pad)
-        if finalize is not None:
-            finalize()           # in stream order behind every weight-gradient GEMM of this stage
-    side.run(conv_wgrad_fn, sv.inp, dy0)
+    if sv.inp.dtype == torch.uint8:
+        ops.stem_wgrad(sv.inp, dy0, G('raw/conv'), g.H_in, g.W_in)
+    else:
+        ops.conv_wgrad(sv.inp, dy0, G('raw/conv'), g.k, g.stride, g.pad)
+    if finalize is not None:
+        finalize()               # in stream order behind every weight-gradient GEMM of this stage
     d_in = None
     if need_input_grad:
         if r.conv_dgrad4:
             d_in = ops.conv_dgrad4(dy0, sw.conv_wd4, prev_cot, g.H_in, g.W_in, g.Cin)      # one launch (2 x 2 pixel blocks)
         else:
             d_in = ops.conv_dgrad(dy0, sw.conv_wd, prev_cot, g.H_in, g.W_in, g.Cin, g.k, g.stride, g.pad)
-    side.join()             # every parameter gradient of this stage is final from here on (DDP hook, optimizer)
-    return d_in, dh0, dc0
+    return d_in, dh0, dc0        # every parameter gradient of this stage is final from here on (DDP hook, optimizer)

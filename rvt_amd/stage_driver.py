@@ -6,8 +6,8 @@
     reference modules/detection.py:231-255);
   * train_forward() / train_backward(): the training forward and the BPTT backward as one call each, where routes.driver_covers.
 
-rvt_amd/stage.py is the operator-by-operator host loop for everything else (token masks, DWS-ConvLSTM, the second weight-gradient
-stream, the saving fused-MLP flavour).  Python only allocates: outputs, saved activations and a grow-only workspace per stream."""
+rvt_amd/stage.py is the operator-by-operator host loop for everything else (token masks, DWS-ConvLSTM, the saving fused-MLP
+flavour).  Python only allocates: outputs, saved activations and a grow-only workspace per stream."""
 from __future__ import annotations
 
 import ctypes

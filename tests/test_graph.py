@@ -45,7 +45,7 @@ def test_c_abi_launches_capture_and_replay(dt):
 
 
 def test_training_step_graph_matches_eager():
-    """Whole step (forward_sequence + BPTT backward with the weight-gradient side stream + fused AdamW) captured once and
+    """Whole step (forward_sequence + BPTT backward + fused AdamW) captured once and
     replayed: parameters after 3 replays == parameters after 3 eager steps, bit for bit (same kernels, same order)."""
     from rvt_amd import RNNDetector, backbone_config
     from rvt_amd.graph import GraphedStep

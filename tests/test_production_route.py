@@ -276,63 +276,6 @@ def test_simota_tail_at_1mpx_batch_vs_oracle(production_route):
     assert float((det.cpu() - O.to_infer(pred)).abs().max()) <= 1e-3 * float(pred.abs().max())
 
 
-def test_deferred_weight_gradient_stream_gives_identical_gradients():
-    """tuning.route_wgrad_stream = 2 (round 5): the weight-gradient launches of stage 4 are queued and start on a second stream beside
-    the per-step reverse scan of stage 3.  Same kernels, same operands, same launch geometry: every gradient must equal the one-stream
-    route up to the order of the fp32 atomics that fold the LayerNorm parameter gradients (and the per-stage hooks must still see
-    complete buckets)."""
-    from rvt_amd import tuning as tn
-    res = {}
-    for mode in (0, 2):
-        with tn.override(route_wgrad_stream=mode):
-            m = _bench_model(torch.bfloat16, 'tiny', 'gen1')
-            seen = []
-            m._stage_grad_hook = lambda si, bucket, accumulated=False: seen.append((si, float(bucket.abs().sum())))
-            g = torch.Generator(device=DEV).manual_seed(3)
-            xs = torch.randint(0, 11, (4, 2, 20, 240, 304), generator=g, dtype=torch.uint8, device=DEV)
-            feats, _ = m.forward_sequence(xs, None)
-            torch.autograd.backward([feats[s] for s in (2, 3, 4)], [torch.ones_like(feats[s]) for s in (2, 3, 4)])
-            torch.cuda.synchronize()
-            res[mode] = ({k: p.grad.clone() for k, p in m.named_parameters()}, sorted(seen))
-    assert [s for s, _ in res[2][1]] == [0, 1, 2, 3]
-    for (s0, v0), (s2, v2) in zip(res[0][1], res[2][1]):
-        assert abs(v0 - v2) <= 1e-5 * abs(v0), (s0, v0, v2)
-    for k, a in res[0][0].items():
-        b = res[2][0][k]
-        assert float((a - b).abs().max()) <= 1e-5 * max(float(a.abs().max()), 1e-30), k
-
-
-def test_deferred_side_stream_keeps_operands_alive_until_join():
-    """SideStream.flush() launches the queued closures on the side stream; whatever they read must stay referenced until
-    join() has ordered the main stream behind them (the closures are the last owners of a stage's saved activations).  Checked on the
-    object level: a tensor owned only by a queued closure survives flush() and is released by join()."""
-    import gc
-    import weakref
-    from rvt_amd import tuning as tn
-    from rvt_amd.stage import SideStream
-    with tn.override(route_wgrad_stream=2):
-        like = torch.zeros(8, device=DEV)
-        side = SideStream(like)
-        assert side.enabled and side.defer_mode
-        side.deferring = True
-        owned = torch.ones(1 << 20, device=DEV)
-        out = torch.zeros(1, device=DEV)
-        ref = weakref.ref(owned)
-
-        def fn(owned=owned):
-            out.add_(owned.sum())
-        side.run(fn)                       # no operand list on purpose: the closure is the only owner (qkv_wgrad_fn reads s['u'] like this)
-        del owned, fn
-        assert side.flush()
-        gc.collect()
-        assert ref() is not None, 'flush() dropped the last reference to a tensor the side stream is still reading'
-        side.join()
-        gc.collect()
-        assert ref() is None
-        torch.cuda.synchronize()
-        assert float(out) == float(1 << 20)
-
-
 OP_BY_OP = dict(route_fused_mlp=0, route_mlp_bwd_fused=0, route_attn_block=0, route_lstm_scan=0, route_lstm_scan_wgrad=0, lstm_scan3=0,
                 mlp_stream=0, ln_linear=0, mlp_chain=0, dgrad_ln=0, route_conv_dgrad4=0, conv_wgrad_tn=0, attn_staged=0, stem=0, ppgemm=0)
 # relative L2 error of the production route against the op-by-op route, per stage: (features, parameter gradients); 1.5 x the worst

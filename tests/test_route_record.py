@@ -7,7 +7,7 @@ import inspect
 import pytest
 import torch
 
-from rvt_amd import _lib, stage, stage_driver, tuning
+from rvt_amd import _lib, backbone, stage, stage_driver, tuning
 from tests import casegen
 from tests import make_golden_launch_trace as LT
 from tests.backends import backend, emu_library  # noqa: F401
@@ -152,6 +152,8 @@ def test_planner_invariants(tun):
                                 assert r.driver_covers == 0, what
                             if dws:
                                 assert r.lstm_route == 0, what
+                            if save and not dws and not mask:   # the training driver leaves only the saving fused-MLP flavour to the host loop
+                                assert r.driver_covers == (r.mlp_route != 2), what
                             seen.add((r.lstm_route, r.mlp_route, r.attn_block))
         assert len(seen) > 4, seen          # (the grid reaches several routes: the invariants are not checked on one record 180 times)
     finally:
@@ -165,3 +167,5 @@ def test_backward_reads_nothing_but_the_record():
     assert 'tuning.get(' not in src and '_supported(' not in src and 'sv.routes' in src
     assert not any(hasattr(stage, n) for n in ('use_fused_mlp', 'use_attn_block', 'use_lstm_scan', 'use_lstm_scan3'))
     assert not hasattr(stage_driver, 'train_routes')
+    bsrc = inspect.getsource(backbone._BackboneSeqFn.backward)
+    assert 'tuning' not in bsrc and 'SideStream' not in bsrc and not hasattr(stage, 'SideStream')
