@@ -1,0 +1,253 @@
+"""Rounding models of the bf16 fused kernels: the YARDSTICK of the ceilings in tests/bounds.py (idiom of tests/test_optim.py and
+tests/test_bnact.py: fp64 truth, and a yardstick that is not the code under test).
+
+Each function restates one fused operation in plain torch on the CPU - always the CPU, so that the `emu` and the `hip` id of a test
+get the same yardstick - in fp32 arithmetic, and rounds to bf16 exactly where the kernel converts fp32 to bf16: a stored output, a
+saved tensor, or an MFMA operand built from an accumulator.  Nowhere else.  It takes the bf16 inputs the test hands to the kernel.
+What it returns are the values BEFORE the final storage rounding (the ceiling adds one bf16 ulp for outputs stored in bf16).
+
+`rounding=False, dtype=torch.float64` switches every rounding point off; the result must then equal the test's fp64 autograd truth
+to 1e-9 relative (`pin`, asserted once per case as tests/test_bnact.py `_Case.__init__` does), which pins the model's MATHEMATICS:
+only its rounding can differ from the truth.
+
+The backward passes are written out (no autograd): several kernels round a PRODUCT inside a reduction (the LayerNorm parameter
+gradients go through an MFMA against an identity operand, so du * xhat and du are converted to bf16 before they are summed), and the
+attention backward recomputes q / k / v with other bias placements than the forward - neither is a rounding of an autograd edge.  The
+forward roundings are what `t + (t.bfloat16().float() - t).detach()` would be and the gradient roundings what an identity Function
+with a rounding backward would be; written out they are just `_r(t)`.
+
+ROUNDING POINTS (kernel file : line of the conversion)
+
+mlp_half - LN -> fc1 -> GELU -> fc2 * gamma + residual
+    v2 = LN2(x), fc1 operand and saved tensor    mlp.hpp:260  mlp_chain.hpp:89 (forward, dgrad) :423 (wgrad / both)  mlp_stream.hpp:696
+    g = GELU(pre), fc2 operand and saved tensor  mlp.hpp:317  mlp_chain.hpp:153 :454  mlp_stream.hpp:206 :747;  mlp.hpp:791 (recompute)
+    gp = GELU'(pre), saved (`saved_gp`)          mlp.hpp:323 - rvt_mlp_bwd_dgrad multiplies by the STORED value (mlp.hpp:495)
+    (W2 gamma)^T, rounded by the host            rvt_amd/weights.py; the tests build it the same way
+    dh = dg * GELU'(pre), fc1-dgrad / dW1 operand, stored by rvt_mlp_bwd_dgrad      mlp.hpp:498 :792  mlp_chain.hpp:251 :455  mlp_stream.hpp:462 :748
+        (db1 sums the UNROUNDED products: mlp_chain.hpp:452, mlp_stream.hpp:746, mlp.hpp:789)
+    dv2 = dh W1 through a bf16 tile (`dv2_bf16`: rvt_mlp_bwd_recompute_both only)   mlp_chain.hpp:505
+    dv2 * xhat and dv2 before the column sums (`dln_bf16`: the chain / streamed input-gradient kernels)   mlp_chain.hpp:287-288  mlp_stream.hpp:536-537
+        (mlp.hpp:547 :831 and mlp_chain.hpp:525-526 sum in fp32)
+    stored outputs y, pre, dxmid: returned before their rounding (mlp.hpp:353 :325 :555 :839, mlp_chain.hpp:181 :302 :531, mlp_stream.hpp:262 :563)
+
+attn_half - [LN ->] qkv -> softmax(Q K^T) V -> proj * gamma + residual       (attn_block.hpp; acc_to_frags / arr_slot_frag convert)
+    u = LN1(x), qkv operand (and the `u` output of the backward)             :163
+    forward  q (+ bias), k (NO bias: softmax is invariant to it), v (NO bias: added to the output, rows of P sum to 1)   :273 :280 :283
+             the UN-normalised exp(scale (s - max)) as the P V operand        :299
+             a = P V / sum + bv, proj operand and saved tensor                :307 :314;   xmid stored :344
+    backward q (+ bias), k (no bias), v (+ bias)                              :554 :562 :534 :540 :537
+             dO = dxmid (Wp gamma), (Wp gamma)^T rounded by the host          :557 :565
+             P = softmax in fp32 (normalised), dS = P (dP - delta) scale, both as MFMA operands   :594-595 :603
+             dq, dk, dv: stored and the operand of du = dqkv Wqkv             :513 :516
+             LN / PRE: du * xhat and du before the column sums                :669-670;   dx stored :685 :693
+    `handover_bf16` is the two-launch route the PRE kernel replaces: dx = dxmid + du stored in bf16 (:693), then ln_bwd_kernel
+    (rowops.hpp:59-116: fp32 sums of the bf16 rows).
+
+dgrad_ln - dx = add + LN'(dy W; x) and, `inside`, dx = LN'(dy W + add; x)     (dgrad_ln.hpp)
+    du (+ add) rounded "as the two-launch chain stores it"                    :184 - AFTER the row sums s1 / s2 took the fp32 values (:180-182)
+    du * xhat before the column sums (du itself is already bf16)              :244-245;   dx stored :213
+    `fused=False` is the chain it replaces: du stored by the GEMM epilogue, then ln_bwd_kernel on the bf16 rows (rowops.hpp:59-116).
+
+ln_linear - u = LN(x) is the GEMM operand and the saved tensor (ln_linear.hpp:107-115, layernorm_fwd rowops.hpp:50); y stored (:134).
+linear / conv_fwd have no interior rounding point: fp32 accumulation of bf16 products, one storage rounding (gemm.hpp / ppgemm.hpp epilogues).
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+
+def _r(t, on=True):
+    """One fp32 -> bf16 conversion (round to nearest even, what v_cvt_pk_bf16_f32 and the emulator's cast do)."""
+    return t.bfloat16().to(t.dtype) if on else t
+
+
+def _prep(dtype, *ts):
+    return [None if t is None else t.detach().to('cpu', dtype) for t in ts]
+
+
+def _ln(x, eps):
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
+    return d * rstd, rstd
+
+
+def _ln_bwd(d, xhat, rstd, w, stats_from=None):
+    """rstd (d w - mean(d w) - xhat mean(d w xhat)); `stats_from`: the tensor the two row means are taken from (dgrad_ln.hpp:180)."""
+    gs = (d if stats_from is None else stats_from) * w
+    m1 = gs.mean(-1, keepdim=True)
+    m2 = (gs * xhat).mean(-1, keepdim=True)
+    return rstd * (d * w - m1 - xhat * m2)
+
+
+def _gelu_both(x):
+    phi = 0.5 * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0))))
+    return x * phi, phi + x * torch.exp(-0.5 * x * x) * (1.0 / math.sqrt(2.0 * math.pi))
+
+
+def pin(model64, truth, what):
+    """The model with its rounding off, in fp64, IS the test's fp64 truth (1e-9 relative to the tensor's max)."""
+    for k, want in truth.items():
+        got, want = model64[k], want.detach().double().cpu()
+        assert got.shape == want.shape, (what, k, got.shape, want.shape)
+        err, s = (got - want).abs().max().item(), max(want.abs().max().item(), 1.0)
+        assert err <= 1e-9 * s, f'{what}: model (rounding off, fp64) vs fp64 truth, {k}: {err:.3e} of {s:.3e}'
+
+
+# ------------------------------------------------------------------------------------------------------------------- MLP half
+def mlp_half(x, lw, lb, w1, b1, w2, b2, gam, dy=None, eps=1e-5, *, rounding=True, dtype=torch.float32, saved_gp=False,
+             dln_bf16=False, dv2_bf16=False):
+    """x [M][C], w1 [4C][C], w2 [C][4C], dy [M][C] -> dict of v2, pre, g, gp, y and (dy given) dh, dxmid, dln_w, dln_b, dW1, db1,
+    S2, cs2.  S2 = dy^T g and cs2 = colsum(dy) are the raw fc2 products (gamma is applied by the LayerScale fold)."""
+    x, lw, lb, w1, b1, w2, b2, gam, dy = _prep(dtype, x, lw, lb, w1, b1, w2, b2, gam, dy)
+    r = lambda t: _r(t, rounding)
+    xhat, rstd = _ln(x, eps)
+    v2 = xhat * lw + lb
+    v2r = r(v2)
+    pre = v2r @ w1.t() + b1
+    g, gp = _gelu_both(pre)
+    gr = r(g)
+    y = x + gam * (gr @ w2.t() + (b2 if b2 is not None else 0.0))
+    out = dict(v2=v2, pre=pre, g=g, gp=gp, y=y)
+    if dy is None:
+        return out
+    w2g = r(w2 * gam[:, None])
+    dh = (dy @ w2g) * (r(gp) if saved_gp else gp)
+    dhr = r(dh)
+    dv2 = dhr @ w1
+    if dv2_bf16:
+        dv2 = r(dv2)
+    out.update(dh=dh, dxmid=dy + _ln_bwd(dv2, xhat, rstd, lw),
+               dln_w=(r(dv2 * xhat) if dln_bf16 else dv2 * xhat).sum(0), dln_b=(r(dv2) if dln_bf16 else dv2).sum(0),
+               dW1=dhr.t() @ v2r, db1=dh.sum(0), S2=dy.t() @ gr, cs2=dy.sum(0))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- attention half
+def _to_parts(x, Fr, H, W, ph, pw, window):
+    """(F, H, W, c) -> (partitions, ph * pw, c): windows (maxvit.py:273-287) or the dilated grid (:290-304)."""
+    c = x.shape[-1]
+    if window:
+        t = x.reshape(Fr, H // ph, ph, W // pw, pw, c).permute(0, 1, 3, 2, 4, 5)
+    else:
+        t = x.reshape(Fr, ph, H // ph, pw, W // pw, c).permute(0, 2, 4, 1, 3, 5)
+    return t.reshape(-1, ph * pw, c)
+
+
+def _from_parts(t, Fr, H, W, ph, pw, window):
+    c = t.shape[-1]
+    t = t.reshape(Fr, H // ph, W // pw, ph, pw, c)
+    t = t.permute(0, 1, 3, 2, 4, 5) if window else t.permute(0, 3, 1, 4, 2, 5)
+    return t.reshape(Fr, H, W, c)
+
+
+def attn_half(x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm, geom, eps=1e-5, *, y0=None, rounding=True, dtype=torch.float32,
+              handover_bf16=False):
+    """geom = (F, H, W, C, dim_head, ph, pw, window).  ln_w None: no norm1.  y0 given (with ln_w = the weight of the norm in FRONT
+    of the block, ln_b unused): the PRE form, x = the block input as stored, dy0 = LN'(dxmid + du; y0).  The backward multiplies
+    dxmid by wpg_t^T = the host-rounded (Wp gamma) when rounding, by gamma * wp (what autograd does) when not.
+    -> dict of u, a, xmid, dqkv, dx (PRE: dy0), dln_w, dln_b."""
+    Fr, H, W, C, dh, ph, pw, window = geom
+    heads, scale = C // dh, dh ** -0.5
+    x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm, y0 = _prep(dtype, x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm, y0)
+    r = lambda t: _r(t, rounding)
+    part = lambda t: _to_parts(t.reshape(Fr, H, W, -1), Fr, H, W, ph, pw, window)
+    back = lambda t: _from_parts(t, Fr, H, W, ph, pw, window)
+    pre = y0 is not None
+    xt = part(x)
+    out = {}
+    if ln_w is not None and not pre:
+        xhat, rstd = _ln(xt, eps)
+        u = xhat * ln_w + ln_b
+        out['u'] = back(u)
+        ur = r(u)
+    else:
+        ur = xt
+    NP, L = xt.shape[0], xt.shape[1]
+    qkv = (ur @ wqkv.t()).reshape(NP, L, heads, 3, dh).permute(3, 0, 2, 1, 4)            # [3][NP][heads][L][dh], no bias yet
+    bq, _, bv = bqkv.reshape(heads, 3, dh).permute(1, 0, 2)[:, None, :, None, :]        # [3] x [1][heads][1][dh]; the k bias is dropped
+    # ---- forward (attn_block_fwd_kernel)
+    q, k, v = r(qkv[0] + bq), r(qkv[1]), r(qkv[2])
+    s = (q @ k.transpose(-1, -2)) * scale
+    e = torch.exp(s - s.max(-1, keepdim=True).values)
+    a = (r(e) @ v) / e.sum(-1, keepdim=True) + bv
+    a = a.permute(0, 2, 1, 3).reshape(NP, L, C)
+    out['a'] = back(a)
+    out['xmid'] = back(xt + gamma * (r(a) @ wp.t() + bp))
+    if dxm is None:
+        return out
+    # ---- backward (attn_block_bwd_kernel): everything recomputed from the block input
+    dt_ = part(dxm)
+    wpg = wpg_t.t() if rounding else gamma[:, None] * wp                                 # [c][a]
+    dO = r(dt_ @ wpg).reshape(NP, L, heads, dh).permute(0, 2, 1, 3)
+    q, k, v = r(qkv[0] + bq), r(qkv[1]), r(qkv[2] + bv)
+    p = torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1)
+    dp = dO @ v.transpose(-1, -2)
+    ds = p * (dp - (p * dp).sum(-1, keepdim=True)) * scale
+    pr, dsr = r(p), r(ds)
+    dq, dk, dv = dsr @ k, dsr.transpose(-1, -2) @ q, pr.transpose(-1, -2) @ dO
+    dqkv = torch.stack([dq, dk, dv], 0).permute(1, 3, 2, 0, 4).reshape(NP, L, 3 * C)
+    out['dqkv'] = back(dqkv)
+    du = r(dqkv) @ wqkv
+    if pre or ln_w is not None:
+        if pre:
+            xhat, rstd = _ln(part(y0), eps)
+            d = du + dt_
+            if handover_bf16:
+                d = r(d)
+            res = 0.0
+        else:
+            d, res = du, dt_
+        rr = (lambda t: t) if handover_bf16 else r
+        out.update(dx=back(res + _ln_bwd(d, xhat, rstd, ln_w)), dln_w=rr(d * xhat).sum((0, 1)), dln_b=rr(d).sum((0, 1)))
+    else:
+        out['dx'] = back(dt_ + du)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------ LN + linear family
+def ln_linear(x, lw, lb, w, b, eps=1e-5, *, rounding=True, dtype=torch.float32):
+    """u = LN(x), y = u W^T + b  (w [N][C]) -> dict of u, y."""
+    x, lw, lb, w, b = _prep(dtype, x, lw, lb, w, b)
+    xhat, _ = _ln(x, eps)
+    u = xhat * lw + lb
+    return dict(u=u, y=_r(u, rounding) @ w.t() + b)
+
+
+def linear(x, w, b=None, *, rounding=True, dtype=torch.float32):
+    """y = x W^T + b: fp32 accumulation of the bf16 products, nothing rounded before the store (`rounding` has nothing to switch)."""
+    x, w, b = _prep(dtype, x, w, b)
+    return dict(y=x @ w.t() + (b if b is not None else 0.0))
+
+
+def wgrad(dy, x, *, rounding=True, dtype=torch.float32):
+    """dW = dy^T x and the column sums of dy, both kept in fp32 (ppgemm_tn.hpp): as `linear`, no rounding point at all."""
+    dy, x = _prep(dtype, dy, x)
+    return dict(dW=dy.t() @ x, colsum=dy.sum(0))
+
+
+def dgrad_ln(dy, w, x, add, lw, eps=1e-5, *, inside=False, fused=True, rounding=True, dtype=torch.float32):
+    """dy [M][K], w [K][C], x [M][C] = the LayerNorm input, add [M][C] or None -> dict of dx, dln_w, dln_b.
+    inside: the added cotangent enters the norm (rvt_linear_dgrad_preln).  fused = False: the two launches (GEMM epilogue stores
+    du [+ add] in bf16, ln_bwd_kernel reads it back)."""
+    dy, w, x, add, lw = _prep(dtype, dy, w, x, add, lw)
+    r = lambda t: _r(t, rounding)
+    xhat, rstd = _ln(x, eps)
+    du = dy @ w
+    res = 0.0
+    if add is not None:
+        if inside:
+            du = du + add
+        else:
+            res = add
+    dur = r(du)
+    if fused:
+        return dict(dx=res + _ln_bwd(dur, xhat, rstd, lw, stats_from=du), dln_w=r(dur * xhat).sum(0), dln_b=dur.sum(0))
+    return dict(dx=res + _ln_bwd(dur, xhat, rstd, lw), dln_w=(dur * xhat).sum(0), dln_b=dur.sum(0))
+
+
+def conv_fwd(x, w, stride, pad, *, rounding=True, dtype=torch.float32):
+    """x (F, H, W, Cin) channels-last, w (Cout, Cin, k, k) -> y (F, Ho, Wo, Cout); as `linear`, no interior rounding point."""
+    x, w = _prep(dtype, x, w)
+    return dict(y=F.conv2d(x.permute(0, 3, 1, 2), w, None, stride, pad).permute(0, 2, 3, 1))

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from rvt_amd import ops, tuning, weights
-from tests import bounds
+from tests import bf16_model, bounds
 from tests.backends import backend  # noqa: F401
 
 DTYPES = [torch.float32, torch.bfloat16]
@@ -19,21 +19,43 @@ def rnd(shape, dev, dt, seed, scale=1.0):
     return (torch.randn(shape, generator=g) * scale).to(dt).to(dev)
 
 
-def close(got, want, dt, what, scale=None, f32_mult=1.0):
+def close(got, want, dt, what, scale=None, f32_mult=1.0, model=None, stored_bf16=None, factor=2, ceiling=None):
     """fp32: |got - want|_max <= 2e-5 * f32_mult of the reference scale.  bf16: the bound MEASURED for this very check (1.5 x the
-    error seen on the backend, tests/bounds.py; 2e-2 without an entry) - no multipliers."""
+    error seen on the backend, tests/bounds.py) - no multipliers - AND, given `model` (the value of tests/bf16_model.py before the
+    storage rounding) or a ready `ceiling` (kernel against kernel: the sum of both sides'), the independent ceiling of tests/bounds.py:
+    slack = max(factor * max|model - want|, 2e-4 * max|want|), |got - want| <= slack for an output stored in fp32 and, element-wise,
+    <= 2^-8 |want| + slack for one stored in bf16 (`stored_bf16`; default: the dtype of `got`).  Returns the ceiling (bf16 runs)."""
+    if stored_bf16 is None:
+        stored_bf16 = got.dtype == torch.bfloat16
     got = got.detach().double().cpu()
     want = want.detach().double().cpu()
     s = scale if scale is not None else max(want.abs().max().item(), 1e-6)
     err = (got - want).abs().max().item() / s
     if dt == torch.bfloat16:
-        bounds.check(err, what)
-    else:
-        assert err <= TOL[dt] * f32_mult, f'{what}: rel err {err:.3e} (tol {TOL[dt] * f32_mult:.1e})'
+        if model is not None:
+            assert ceiling is None
+            ceiling = bounds.ceiling(want, model, stored_bf16, factor)
+        bounds.check(err, what, got, want, s, ceiling)
+        return ceiling
+    assert err <= TOL[dt] * f32_mult, f'{what}: rel err {err:.3e} (tol {TOL[dt] * f32_mult:.1e})'
+    return None
 
 
 def f64(t):
     return t.detach().double().cpu()
+
+
+def modelled(fn, truth, dt, *args, **kw):
+    """The rounding model of a bf16 case (tests/bf16_model.py: fp32 on the CPU, rounded where the kernel rounds), after its
+    mathematics is pinned to the test's fp64 truth: rounding off, in fp64, it IS `truth` to 1e-9.  fp32 runs have no model."""
+    if dt != torch.bfloat16:
+        return None
+    bf16_model.pin(fn(*args, rounding=False, dtype=torch.float64, **kw), truth, fn.__name__)
+    return fn(*args, **kw)
+
+
+def part(m, k, mult=1.0):
+    return None if m is None else m[k] * mult
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -117,8 +139,11 @@ def test_ppgemm_tn_routes(backend, M, N, K):
         xs, hs = x[:, :C].contiguous(), x[:, C:].contiguous()
         dw3, db3 = torch.zeros(N, K, device=backend), torch.zeros(N, device=backend)
         ops.lstm_wgrad(dy, xs, hs, dw3, db3)
-        close(dw3, f64(dy).t() @ f64(x), dt, 'ppgemm_tn lstm dW')
-        close(db3, f64(dy).sum(0), dt, 'ppgemm_tn lstm colsum', f32_mult=0.2)
+        # (the C = 128 case joined after the table was recorded: these two checks carry the ceiling of tests/bounds.py, whose model
+        #  of an fp32-accumulated, fp32-stored product is the fp32 product itself)
+        m = modelled(bf16_model.wgrad, dict(dW=f64(dy).t() @ f64(x), colsum=f64(dy).sum(0)), dt, dy, x)
+        close(dw3, f64(dy).t() @ f64(x), dt, 'ppgemm_tn lstm dW', model=m['dW'])
+        close(db3, f64(dy).sum(0), dt, 'ppgemm_tn lstm colsum', f32_mult=0.2, model=m['colsum'])
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -161,24 +186,27 @@ def test_mlp_fused(backend, dt, C, M):
     h = F.gelu(pre)
     want = xr + f64(gam) * (h @ f64(w2).t() + f64(b2))
     want.backward(f64(dy))
-    close(y, want, dt, 'mlp_fwd fused')
-    close(y_inf, want, dt, 'mlp_fwd fused, nothing saved')
-    close(v2_saved, v2, dt, 'mlp_fwd saved LayerNorm output')
-    close(g, h, dt, 'mlp_fwd g')
     hp = f64(pre.detach()).requires_grad_(True)
     F.gelu(hp).sum().backward()
-    close(gp, hp.grad, dt, 'mlp_fwd gp')
-    # against the op-by-op HIP chain it replaces
+    # the rounding model: rvt_mlp_bwd_dgrad multiplies by the STORED GELU' and sums the LayerNorm parameter gradients in fp32
+    m = modelled(bf16_model.mlp_half, dict(y=want, v2=v2, pre=pre, g=h, gp=hp.grad, dh=pre.grad, dxmid=xr.grad, dln_w=lwr.grad, dln_b=lbr.grad),
+                 dt, x, lw, lb, w1, b1, w2, b2, gam, dy, 1e-5, saved_gp=True)
+    c_y = close(y, want, dt, 'mlp_fwd fused', model=part(m, 'y'))
+    close(y_inf, want, dt, 'mlp_fwd fused, nothing saved', model=part(m, 'y'))
+    close(v2_saved, v2, dt, 'mlp_fwd saved LayerNorm output', model=part(m, 'v2'))
+    close(g, h, dt, 'mlp_fwd g', model=part(m, 'g'))
+    close(gp, hp.grad, dt, 'mlp_fwd gp', model=part(m, 'gp'))
+    # against the op-by-op HIP chain it replaces (same rounding points: LN output and GELU stored in bf16 between the launches)
     v2h = ops.layernorm_fwd(x, lw, lb, 1e-5)
     g2, gp2 = ops.linear_gelu_fwd(v2h, w1, b1, want_grad=True)
     y2 = ops.linear_scale_res_fwd(g2, w2, b2, gam, x)
-    close(y, y2.double(), dt, 'mlp_fwd fused vs chain')
+    close(y, y2.double(), dt, 'mlp_fwd fused vs chain', ceiling=c_y + c_y if c_y else None)
     # round 4: the pre-activation-only flavour (what the C = 128 training forward keeps) and the backward that consumes it:
     # GELU on load in the fc2 weight gradient, GELU' in the epilogue of the fc2 input gradient
     y_pre, hpre, none_gp, _ = ops.mlp_fwd(x, lw, lb, w1, b1, w2, b2, gam, 1e-5, want_pre=True, want_v2=True)
     assert none_gp is None
-    close(y_pre, want, dt, 'mlp_fwd fused (pre-activation saved)')
-    close(hpre, pre.detach(), dt, 'mlp_fwd saved pre-activation')
+    close(y_pre, want, dt, 'mlp_fwd fused (pre-activation saved)', model=part(m, 'y'))
+    close(hpre, pre.detach(), dt, 'mlp_fwd saved pre-activation', model=part(m, 'pre'))
     s2 = torch.zeros(C, 4 * C, device=backend)
     ops.linear_wgrad(dy, hpre, s2, gelu_in=True)
     close(s2, f64(dy).t() @ h.detach(), dt, 'fc2 weight gradient from the pre-activation', f32_mult=2.0)
@@ -190,10 +218,10 @@ def test_mlp_fused(backend, dt, C, M):
     w1_t = f64(w1).t().to(dt).contiguous().to(backend)
     dlw, dlb = torch.zeros(C, device=backend), torch.zeros(C, device=backend)
     dh, dxm = ops.mlp_bwd_dgrad(dy, gp, x, lw, w2g_t, w1_t, dlw, dlb, 1e-5)
-    close(dh, pre.grad, dt, 'mlp_bwd dh', f32_mult=2.0)
-    close(dxm, xr.grad, dt, 'mlp_bwd dxmid', f32_mult=2.0)
-    close(dlw, lwr.grad, dt, 'mlp_bwd dln_w', f32_mult=2.0)
-    close(dlb, lbr.grad, dt, 'mlp_bwd dln_b', f32_mult=2.0)
+    close(dh, pre.grad, dt, 'mlp_bwd dh', f32_mult=2.0, model=part(m, 'dh'))
+    close(dxm, xr.grad, dt, 'mlp_bwd dxmid', f32_mult=2.0, model=part(m, 'dxmid'))
+    close(dlw, lwr.grad, dt, 'mlp_bwd dln_w', f32_mult=2.0, model=part(m, 'dln_w'))
+    close(dlb, lbr.grad, dt, 'mlp_bwd dln_b', f32_mult=2.0, model=part(m, 'dln_b'))
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -276,19 +304,22 @@ def test_linear_dgrad_ln(backend, C, K, M):
     xr, lwr, lbr = f64(x).requires_grad_(True), f64(lw).requires_grad_(True), torch.zeros(C, dtype=torch.float64, requires_grad=True)
     u = F.layer_norm(xr, (C,), lwr, lbr, 1e-5)
     (u @ f64(w).t()).backward(f64(dy))
-    close(dx, xr.grad + f64(dres), dt, 'dgrad_ln dx')
-    close(dw, lwr.grad, dt, 'dgrad_ln dln_w')
-    close(db, lbr.grad, dt, 'dgrad_ln dln_b')
+    truth = dict(dx=xr.grad + f64(dres), dln_w=lwr.grad, dln_b=lbr.grad)
+    m = modelled(bf16_model.dgrad_ln, truth, dt, dy, w, x, dres, lw, 1e-5)
+    c_dx = close(dx, truth['dx'], dt, 'dgrad_ln dx', model=m['dx'])
+    c_dw = close(dw, lwr.grad, dt, 'dgrad_ln dln_w', model=m['dln_w'])
+    close(db, lbr.grad, dt, 'dgrad_ln dln_b', model=m['dln_b'])
     # the chain: du (rounded to bf16) then the LayerNorm backward
     dw2, db2 = torch.zeros(C, device=backend), torch.zeros(C, device=backend)
     du = ops.linear_dgrad(dy, w.t().contiguous())
     dx2 = ops.layernorm_bwd(x, lw, du, dres, dw2, db2, 1e-5)
-    close(dx, dx2.double(), dt, 'dgrad_ln vs chain dx')
-    close(dw, dw2.double(), dt, 'dgrad_ln vs chain dln_w')
+    mc = modelled(bf16_model.dgrad_ln, truth, dt, dy, w, x, dres, lw, 1e-5, fused=False)
+    close(dx, dx2.double(), dt, 'dgrad_ln vs chain dx', ceiling=c_dx + bounds.ceiling(truth['dx'], mc['dx'], True, 2))
+    close(dw, dw2.double(), dt, 'dgrad_ln vs chain dln_w', ceiling=c_dw + bounds.ceiling(lwr.grad, mc['dln_w'], False, 2))
     # accumulation into existing parameter gradients, no residual
     dx3 = ops.linear_dgrad_ln(dy, w, x, None, lw, dw, db, 1e-5)
-    close(dw, 2 * lwr.grad, dt, 'dgrad_ln dln_w accumulates')
-    close(dx3, xr.grad, dt, 'dgrad_ln dx, no residual')
+    close(dw, 2 * lwr.grad, dt, 'dgrad_ln dln_w accumulates', model=2 * m['dln_w'])
+    close(dx3, xr.grad, dt, 'dgrad_ln dx, no residual', model=bf16_model.dgrad_ln(dy, w, x, None, lw, 1e-5)['dx'])
 
 
 @pytest.mark.parametrize('C,K', [(64, 192), (128, 384)])
@@ -306,15 +337,16 @@ def test_linear_dgrad_preln(backend, C, K, M):
     yr, lwr, lbr = f64(y0).requires_grad_(True), f64(lw).requires_grad_(True), torch.zeros(C, dtype=torch.float64, requires_grad=True)
     u = F.layer_norm(yr, (C,), lwr, lbr, 1e-5)
     ((u @ f64(w).t() * f64(dy)).sum() + (u * f64(add)).sum()).backward()
-    close(out, yr.grad, dt, 'dgrad_preln dy0')
-    close(dw, lwr.grad, dt, 'dgrad_preln dln_w')
-    close(db, lbr.grad, dt, 'dgrad_preln dln_b')
+    truth = dict(dx=yr.grad, dln_w=lwr.grad, dln_b=lbr.grad)
+    m = modelled(bf16_model.dgrad_ln, truth, dt, dy, w, y0, add, lw, 1e-5, inside=True)
+    c = {k: close(got, truth[k], dt, f'dgrad_preln {name}', model=m[k])
+         for k, name, got in (('dx', 'dy0', out), ('dln_w', 'dln_w', dw), ('dln_b', 'dln_b', db))}
     dw2, db2 = torch.zeros(C, device=backend), torch.zeros(C, device=backend)
     dx = ops.linear_dgrad(dy, w.t().contiguous(), add=add)
     out2 = ops.layernorm_bwd(y0, lw, dx, None, dw2, db2, 1e-5)
-    close(out, out2.double(), dt, 'dgrad_preln vs chain dy0')
-    close(dw, dw2.double(), dt, 'dgrad_preln vs chain dln_w')
-    close(db, db2.double(), dt, 'dgrad_preln vs chain dln_b')
+    mc = modelled(bf16_model.dgrad_ln, truth, dt, dy, w, y0, add, lw, 1e-5, inside=True, fused=False)
+    for k, name, got, other in (('dx', 'dy0', out, out2), ('dln_w', 'dln_w', dw, dw2), ('dln_b', 'dln_b', db, db2)):
+        close(got, other.double(), dt, f'dgrad_preln vs chain {name}', ceiling=c[k] + bounds.ceiling(truth[k], mc[k], k == 'dx', 2))
 
 
 def ref_attention(qkv, Fr, H, W, C, dh, ph, pw, window):
@@ -408,21 +440,27 @@ def test_attn_block_fused(backend, dt, window, ln, case):
     a_r = ref_attention(qkv_r, Fr, H, W, C, dh, ph, pw, window)
     wpg = (f64(wpg_t).t() / f64(gamma)[:, None])          # = the (rounded) proj weight the backward kernel sees
     xmid_r = xr + f64(gamma) * (a_r @ f64(wp).t() + f64(bp))
-    close(a, a_r, dt, 'attn_block a')
-    close(xmid, xmid_r, dt, 'attn_block xmid')
     xmid_r.backward(f64(dxm))
+    # the rounding model; everything downstream of the softmax (hardware exp2, reciprocal of the row sum) takes the factor 4
+    truth = dict(a=a_r, xmid=xmid_r, dqkv=qkv_r.grad, dx=xr.grad)
+    if ln:
+        truth.update(u=u_r, dln_w=lw.grad, dln_b=lb.grad)
+    m = modelled(bf16_model.attn_half, truth, dt, x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm,
+                 (Fr, H, W, C, dh, ph, pw, window), eps)
+    close(a, a_r, dt, 'attn_block a', model=part(m, 'a'), factor=4)
+    close(xmid, xmid_r, dt, 'attn_block xmid', model=part(m, 'xmid'), factor=4)
 
     if ph * pw > 64:               # three 32-token blocks per partition: forward only (training takes the op-by-op chain)
         return
     dln_w = torch.zeros(C, dtype=torch.float32, device=backend) if ln else None
     dln_b = torch.zeros(C, dtype=torch.float32, device=backend) if ln else None
     dx, dqkv, u = ops.attn_block_bwd(x, dxm, ln_w, ln_b, wqkv, bqkv, wpg_t, dln_w, dln_b, Fr, H, W, C, dh, ph, pw, window, eps)
-    close(dqkv, qkv_r.grad, dt, 'attn_block dqkv', f32_mult=2.0)
-    close(dx, xr.grad, dt, 'attn_block dx', f32_mult=2.0)
+    close(dqkv, qkv_r.grad, dt, 'attn_block dqkv', f32_mult=2.0, model=part(m, 'dqkv'), factor=4)
+    close(dx, xr.grad, dt, 'attn_block dx', f32_mult=2.0, model=part(m, 'dx'), factor=4)
     if ln:
-        close(u, u_r, dt, 'attn_block u')
-        close(dln_w, lw.grad, dt, 'attn_block dln_w', f32_mult=4.0)
-        close(dln_b, lb.grad, dt, 'attn_block dln_b', f32_mult=4.0)
+        close(u, u_r, dt, 'attn_block u', model=part(m, 'u'))
+        close(dln_w, lw.grad, dt, 'attn_block dln_w', f32_mult=4.0, model=part(m, 'dln_w'), factor=4)
+        close(dln_b, lb.grad, dt, 'attn_block dln_b', f32_mult=4.0, model=part(m, 'dln_b'), factor=4)
     else:
         assert u is None
 
@@ -463,17 +501,23 @@ def test_attn_block_bwd_preln(backend, dt, window, case):
     z = lambda: torch.zeros(C, dtype=torch.float32, device=backend)
     dlw, dlb, dlw2, dlb2 = z(), z(), z(), z()
     dy0, dqkv = ops.attn_block_bwd_preln(x, y0, dxm, ln_w, wqkv, bqkv, wpg_t, dlw, dlb, Fr, H, W, C, dh, ph, pw, window, eps)
-    close(dqkv, qkv_r.grad, dt, 'attn_block_preln dqkv', f32_mult=2.0)
-    close(dy0, yr.grad, dt, 'attn_block_preln dy0', f32_mult=2.0)
-    close(dlw, lw.grad, dt, 'attn_block_preln dln_w', f32_mult=4.0)
-    close(dlb, lb.grad, dt, 'attn_block_preln dln_b', f32_mult=4.0)
+    # the rounding model (every output is downstream of the softmax: factor 4); `handover_bf16` is the two-launch route
+    truth = dict(dqkv=qkv_r.grad, dx=yr.grad, dln_w=lw.grad, dln_b=lb.grad)
+    margs = (x, ln_w, None, wqkv, bqkv, f64(wpg_t).t() / f64(gamma)[:, None], bp, gamma, wpg_t, dxm, (Fr, H, W, C, dh, ph, pw, window), eps)
+    m = modelled(bf16_model.attn_half, truth, dt, *margs, y0=y0)
+    m2 = modelled(bf16_model.attn_half, truth, dt, *margs, y0=y0, handover_bf16=True)
+    close(dqkv, qkv_r.grad, dt, 'attn_block_preln dqkv', f32_mult=2.0, model=part(m, 'dqkv'), factor=4)
+    c_dy0 = close(dy0, yr.grad, dt, 'attn_block_preln dy0', f32_mult=2.0, model=part(m, 'dx'), factor=4)
+    c_dlw = close(dlw, lw.grad, dt, 'attn_block_preln dln_w', f32_mult=4.0, model=part(m, 'dln_w'), factor=4)
+    c_dlb = close(dlb, lb.grad, dt, 'attn_block_preln dln_b', f32_mult=4.0, model=part(m, 'dln_b'), factor=4)
     # the two launches it replaces (dx rounded to the storage type in between)
     dx, dqkv2, u = ops.attn_block_bwd(x, dxm, None, None, wqkv, bqkv, wpg_t, None, None, Fr, H, W, C, dh, ph, pw, window, eps)
     dy0_2 = ops.layernorm_bwd(y0, ln_w, dx, None, dlw2, dlb2, eps)
     assert u is None and torch.equal(dqkv, dqkv2)
-    close(dy0, dy0_2.double(), dt, 'attn_block_preln dy0 vs two launches', f32_mult=2.0)
-    close(dlw, dlw2.double(), dt, 'attn_block_preln dln_w vs two launches', f32_mult=4.0)
-    close(dlb, dlb2.double(), dt, 'attn_block_preln dln_b vs two launches', f32_mult=4.0)
+    two = (lambda c, k: c + bounds.ceiling(truth[k], m2[k], k == 'dx', 4)) if m else (lambda c, k: None)
+    close(dy0, dy0_2.double(), dt, 'attn_block_preln dy0 vs two launches', f32_mult=2.0, ceiling=two(c_dy0, 'dx'))
+    close(dlw, dlw2.double(), dt, 'attn_block_preln dln_w vs two launches', f32_mult=4.0, ceiling=two(c_dlw, 'dln_w'))
+    close(dlb, dlb2.double(), dt, 'attn_block_preln dln_b vs two launches', f32_mult=4.0, ceiling=two(c_dlb, 'dln_b'))
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -669,8 +713,8 @@ def test_conv_fwd_pp(backend, case):
         y = ops.conv_fwd(x, wp, 3, 2, 1)
     with tuning.override(conv_fwd_pp=0):
         y0 = ops.conv_fwd(x, wp, 3, 2, 1)
-    close(y, want, dt, 'conv_fwd_pp')
-    close(y, f64(y0), dt, 'conv_fwd_pp vs the 128-row engine', f32_mult=0.5)
+    c_y = close(y, want, dt, 'conv_fwd_pp', model=modelled(bf16_model.conv_fwd, dict(y=want), dt, x, w, 2, 1)['y'])
+    close(y, f64(y0), dt, 'conv_fwd_pp vs the 128-row engine', f32_mult=0.5, ceiling=c_y + c_y)
 
 
 CONV_WGRAD_TN_CASES = [  # F, H, W, Cin, Cout, k, stride, pad
@@ -767,19 +811,23 @@ def test_mlp_bwd_recompute(backend, dt, M):
         ops.mlp_bwd_recompute_wgrad(dy, x, lw, lb, w1, b1, w2g_t, dw1, db1, s2, cs2, 1e-5)
         return d
     dxm = run()
-    close(dxm, xr.grad, dt, 'mlp_bwd_fused dxmid')
-    close(dlw, lwr.grad, dt, 'mlp_bwd_fused dln_w', f32_mult=2.0)
-    close(dlb, lbr.grad, dt, 'mlp_bwd_fused dln_b', f32_mult=2.0)
-    close(dw1, w1r.grad, dt, 'mlp_bwd_fused dW1', f32_mult=2.0)
-    close(db1, b1r.grad, dt, 'mlp_bwd_fused db1', f32_mult=2.0)
+    # the rounding model of the chain kernels: the input-gradient kernel sums the LayerNorm parameter gradients through bf16 operands
+    m = modelled(bf16_model.mlp_half, dict(y=want, g=g, dxmid=xr.grad, dln_w=lwr.grad, dln_b=lbr.grad, dW1=w1r.grad, db1=b1r.grad,
+                                           S2=f64(dy).t() @ g.detach(), cs2=f64(dy).sum(0)),
+                 dt, x, lw, lb, w1, b1, w2, b2, gam, dy, 1e-5, dln_bf16=True)
+    close(dxm, xr.grad, dt, 'mlp_bwd_fused dxmid', model=part(m, 'dxmid'))
+    close(dlw, lwr.grad, dt, 'mlp_bwd_fused dln_w', f32_mult=2.0, model=part(m, 'dln_w'))
+    close(dlb, lbr.grad, dt, 'mlp_bwd_fused dln_b', f32_mult=2.0, model=part(m, 'dln_b'))
+    close(dw1, w1r.grad, dt, 'mlp_bwd_fused dW1', f32_mult=2.0, model=part(m, 'dW1'))
+    close(db1, b1r.grad, dt, 'mlp_bwd_fused db1', f32_mult=2.0, model=part(m, 'db1'))
     # raw fc2 products: S2 = dy^T g, cs2 = colsum(dy)  (gamma is applied by the LayerScale fold)
-    close(s2, f64(dy).t() @ g.detach(), dt, 'mlp_bwd_fused S2', f32_mult=2.0)
-    close(cs2, f64(dy).sum(0), dt, 'mlp_bwd_fused cs2')
+    close(s2, f64(dy).t() @ g.detach(), dt, 'mlp_bwd_fused S2', f32_mult=2.0, model=part(m, 'S2'))
+    close(cs2, f64(dy).sum(0), dt, 'mlp_bwd_fused cs2', model=part(m, 'cs2'))
     # accumulation semantics (+=) of every parameter-gradient output
     dxm2 = run()
     assert torch.equal(dxm2.cpu(), dxm.cpu())
-    close(dw1, 2 * w1r.grad, dt, 'mlp_bwd_fused dW1 accumulate', f32_mult=2.0)
-    close(cs2, 2 * f64(dy).sum(0), dt, 'mlp_bwd_fused cs2 accumulate')
+    close(dw1, 2 * w1r.grad, dt, 'mlp_bwd_fused dW1 accumulate', f32_mult=2.0, model=part(m, 'dW1', 2))
+    close(cs2, 2 * f64(dy).sum(0), dt, 'mlp_bwd_fused cs2 accumulate', model=part(m, 'cs2', 2))
 
 
 @pytest.mark.parametrize('M', [130, 1000, 5000, 31, 33, 63, 65, 129, 257])
@@ -806,24 +854,30 @@ def test_mlp_bwd_recompute_both(backend, M):
         z = lambda *s: torch.zeros(*s, device=backend)
         dlw, dlb, dw1, db1, s2, cs2 = z(C), z(C), z(4 * C, C), z(4 * C), z(C, 4 * C), z(C)
         dxm = ops.mlp_bwd_recompute_both(dy, x, lw, lb, w1, b1, w2g_t, w1_t, dlw, dlb, dw1, db1, s2, cs2, 1e-5)
-        close(dxm, xr.grad, dt, 'mlp_bwd_both dxmid', f32_mult=2.0)
-        close(dlw, lwr.grad, dt, 'mlp_bwd_both dln_w', f32_mult=4.0)
-        close(dlb, lbr.grad, dt, 'mlp_bwd_both dln_b', f32_mult=4.0)
-        close(dw1, w1r.grad, dt, 'mlp_bwd_both dW1', f32_mult=4.0)
-        close(db1, b1r.grad, dt, 'mlp_bwd_both db1', f32_mult=4.0)
-        close(s2, f64(dy).t() @ g.detach(), dt, 'mlp_bwd_both S2', f32_mult=4.0)
-        close(cs2, f64(dy).sum(0), dt, 'mlp_bwd_both cs2', f32_mult=2.0)
+        # the rounding model: dh W1 passes through a bf16 tile, the LayerNorm parameter gradients are summed in fp32
+        truth = dict(g=g, dxmid=xr.grad, dln_w=lwr.grad, dln_b=lbr.grad, dW1=w1r.grad, db1=b1r.grad, S2=f64(dy).t() @ g.detach(),
+                     cs2=f64(dy).sum(0))
+        m = modelled(bf16_model.mlp_half, truth, dt, x, lw, lb, w1, b1, w2, None, gam, dy, 1e-5, dv2_bf16=True)
+        c_dxm = close(dxm, xr.grad, dt, 'mlp_bwd_both dxmid', f32_mult=2.0, model=m['dxmid'])
+        close(dlw, lwr.grad, dt, 'mlp_bwd_both dln_w', f32_mult=4.0, model=m['dln_w'])
+        close(dlb, lbr.grad, dt, 'mlp_bwd_both dln_b', f32_mult=4.0, model=m['dln_b'])
+        close(dw1, w1r.grad, dt, 'mlp_bwd_both dW1', f32_mult=4.0, model=m['dW1'])
+        close(db1, b1r.grad, dt, 'mlp_bwd_both db1', f32_mult=4.0, model=m['db1'])
+        close(s2, f64(dy).t() @ g.detach(), dt, 'mlp_bwd_both S2', f32_mult=4.0, model=m['S2'])
+        close(cs2, f64(dy).sum(0), dt, 'mlp_bwd_both cs2', f32_mult=2.0, model=m['cs2'])
         # against the two-launch route: weight-gradient side identical (same code), input gradient within bf16 rounding
         dlw2, dlb2, dw12, db12, s22, cs22 = z(C), z(C), z(4 * C, C), z(4 * C), z(C, 4 * C), z(C)
         d2 = ops.mlp_bwd_recompute_dgrad(dy, x, lw, lb, w1, b1, w2g_t, w1_t, dlw2, dlb2, 1e-5)
         ops.mlp_bwd_recompute_wgrad(dy, x, lw, lb, w1, b1, w2g_t, dw12, db12, s22, cs22, 1e-5)
         assert torch.equal(dw1.cpu(), dw12.cpu()) and torch.equal(s2.cpu(), s22.cpu()) and torch.equal(cs2.cpu(), cs22.cpu())
-        close(dxm, d2.double(), dt, 'mlp_bwd_both dxmid vs the two-launch route')
+        m2 = bf16_model.mlp_half(x, lw, lb, w1, b1, w2, None, gam, dy, 1e-5, dln_bf16=True)      # the two-launch route keeps dh W1 in fp32
+        close(dxm, d2.double(), dt, 'mlp_bwd_both dxmid vs the two-launch route',
+              ceiling=c_dxm + bounds.ceiling(xr.grad, m2['dxmid'], True, 2))
         # accumulation semantics and run-to-run reproducibility of the input gradient
         dxm3 = ops.mlp_bwd_recompute_both(dy, x, lw, lb, w1, b1, w2g_t, w1_t, dlw, dlb, dw1, db1, s2, cs2, 1e-5)
         assert torch.equal(dxm3.cpu(), dxm.cpu())
-        close(dw1, 2 * w1r.grad, dt, 'mlp_bwd_both dW1 accumulate', f32_mult=4.0)
-        close(dlw, 2 * lwr.grad, dt, 'mlp_bwd_both dln_w accumulate', f32_mult=4.0)
+        close(dw1, 2 * w1r.grad, dt, 'mlp_bwd_both dW1 accumulate', f32_mult=4.0, model=2 * m['dW1'])
+        close(dlw, 2 * lwr.grad, dt, 'mlp_bwd_both dln_w accumulate', f32_mult=4.0, model=2 * m['dln_w'])
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -856,11 +910,12 @@ def test_mlp_stream_fwd(backend, dt, M, resident):
         y = ops.mlp_fwd(x, lw, lb, w1, b1, w2, b2, gam, 1e-5, want_grad=False)[0]
     v2 = F.layer_norm(f64(x), (C,), f64(lw), f64(lb), 1e-5)
     want = f64(x) + f64(gam) * (F.gelu(v2 @ f64(w1).t() + f64(b1)) @ f64(w2).t() + f64(b2))
-    close(y, want, dt, 'mlp_fwd streamed')
+    m = modelled(bf16_model.mlp_half, dict(y=want), dt, x, lw, lb, w1, b1, w2, b2, gam, None, 1e-5)
+    c_y = close(y, want, dt, 'mlp_fwd streamed', model=part(m, 'y'))
     if dt == torch.bfloat16:
         with tuning.override(mlp_stream=0):
             y0 = ops.mlp_fwd(x, lw, lb, w1, b1, w2, b2, gam, 1e-5, want_grad=False)[0]
-        close(y, y0.double(), dt, 'mlp_fwd streamed vs LDS-staged')
+        close(y, y0.double(), dt, 'mlp_fwd streamed vs LDS-staged', ceiling=c_y + c_y)      # (the same rounding points on both sides)
 
 
 @pytest.mark.parametrize('M,resident,want_u', [(1000, 2, True), (300, 0, True), (2049, 3, False), (31, 0, True), (33, 0, True), (63, 0, False),
@@ -876,24 +931,31 @@ def test_ln_linear_fwd(backend, M, resident, want_u):
     w, b = rnd((N, C), backend, dt, 4, 0.2), rnd((N,), backend, torch.float32, 5, 0.2)
     with tuning.override(chain_resident=resident):
         u, y = ops.ln_linear_fwd(x, lw, lb, w, b, 1e-5, want_u=want_u)
-        y_again = ops.ln_linear_fwd(x, lw, lb, w, b, 1e-5, want_u=not want_u)[1]
+        u_again, y_again = ops.ln_linear_fwd(x, lw, lb, w, b, 1e-5, want_u=not want_u)
     assert torch.equal(y.cpu(), y_again.cpu())
     u0 = ops.layernorm_fwd(x, lw, lb, 1e-5)
     y0 = ops.linear_fwd(u0, w, b)
+    u_r = F.layer_norm(f64(x), (C,), f64(lw), f64(lb), 1e-5)
+    m = modelled(bf16_model.ln_linear, dict(u=u_r, y=u_r @ f64(w).t() + f64(b)), dt, x, lw, lb, w, b, 1e-5)
     if want_u:
-        close(u, F.layer_norm(f64(x), (C,), f64(lw), f64(lb), 1e-5), dt, 'ln_linear u')
+        close(u, u_r, dt, 'ln_linear u', model=m['u'])
         assert (u.float() - u0.float()).abs().max().item() <= 2 ** -6 * u0.float().abs().max().item()      # one bf16 ulp
     else:
         assert u is None
-    # y against the fp64 product of the ROUNDED u (what both routes multiply), then against the op-by-op route
-    ur = f64(u if want_u else u0)
-    close(y, ur @ f64(w).t() + f64(b), dt, 'ln_linear y')
-    close(y, y0.double(), dt, 'ln_linear y vs layernorm_fwd + linear_fwd', f32_mult=2.0)
+    # y against the fp64 product of the ROUNDED u the kernel multiplies (want_u = False: the u of the bit-equal want_u = True launch; the
+    # u0 of rvt_layernorm_fwd may differ from it by one bf16 ulp, which is not an error of y), then against the op-by-op route
+    ur = f64(u if want_u else u_again)
+    want_y = ur @ f64(w).t() + f64(b)
+    close(y, want_y, dt, 'ln_linear y', model=modelled(bf16_model.linear, dict(y=want_y), dt, ur, w, b)['y'])
+    # (the two routes against their common truth, the product of the UNROUNDED LayerNorm output; the same rounding points on both sides)
+    c_full = bounds.ceiling(u_r @ f64(w).t() + f64(b), m['y'], True, 2)
+    close(y, y0.double(), dt, 'ln_linear y vs layernorm_fwd + linear_fwd', f32_mult=2.0, ceiling=c_full + c_full)
     # no LayerNorm (first block of a stage): the plain product through the same kernel
     un, yn = ops.ln_linear_fwd(x, None, None, w, b, 1e-5, want_u=want_u)
     assert un is None
-    close(yn, f64(x) @ f64(w).t() + f64(b), dt, 'ln_linear y (no LayerNorm)')
-    close(yn, ops.linear_fwd(x, w, b).double(), dt, 'ln_linear y (no LayerNorm) vs linear_fwd', f32_mult=2.0)
+    want_n = f64(x) @ f64(w).t() + f64(b)
+    c_n = close(yn, want_n, dt, 'ln_linear y (no LayerNorm)', model=modelled(bf16_model.linear, dict(y=want_n), dt, x, w, b)['y'])
+    close(yn, ops.linear_fwd(x, w, b).double(), dt, 'ln_linear y (no LayerNorm) vs linear_fwd', f32_mult=2.0, ceiling=c_n + c_n)
     with tuning.override(ln_linear=0):
         assert not ops.ln_linear_supported(dt, C, N)
 
@@ -942,8 +1004,12 @@ def _mlp_case(backend, dt, M, C=128):
     want.backward(f64(dy))
     w2g_t = (f64(w2) * f64(gam)[:, None]).t().to(dt).contiguous().to(backend)
     w1_t = f64(w1).t().to(dt).contiguous().to(backend)
+    # the rounding model of the streamed kernels (the input-gradient kernel sums the LayerNorm parameter gradients through bf16 operands)
+    m = modelled(bf16_model.mlp_half, dict(y=want, g=g, dxmid=xr.grad, dln_w=lwr.grad, dln_b=lbr.grad, dW1=w1r.grad, db1=b1r.grad,
+                                           S2=f64(dy).t() @ g.detach(), cs2=f64(dy).sum(0)),
+                 dt, x, lw, lb, w1, b1, w2, b2, gam, dy, 1e-5, dln_bf16=True)
     return dict(x=x, lw=lw, lb=lb, w1=w1, b1=b1, w2=w2, b2=b2, gam=gam, dy=dy, w2g_t=w2g_t, w1_t=w1_t, xr=xr, lwr=lwr, lbr=lbr,
-                w1r=w1r, b1r=b1r, g=g.detach(), want=want.detach())
+                w1r=w1r, b1r=b1r, g=g.detach(), want=want.detach(), m=m)
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -955,9 +1021,9 @@ def test_mlp_stream_bwd_dgrad(backend, dt, M, resident):
     dlw, dlb = torch.zeros(C, device=backend), torch.zeros(C, device=backend)
     with tuning.override(mlp_stream=1, chain_resident=resident):
         dxm = ops.mlp_bwd_recompute_dgrad(c['dy'], c['x'], c['lw'], c['lb'], c['w1'], c['b1'], c['w2g_t'], c['w1_t'], dlw, dlb, 1e-5)
-    close(dxm, c['xr'].grad, dt, 'mlp_stream dxmid')
-    close(dlw, c['lwr'].grad, dt, 'mlp_stream dln_w', f32_mult=2.0)
-    close(dlb, c['lbr'].grad, dt, 'mlp_stream dln_b', f32_mult=2.0)
+    close(dxm, c['xr'].grad, dt, 'mlp_stream dxmid', model=part(c['m'], 'dxmid'))
+    close(dlw, c['lwr'].grad, dt, 'mlp_stream dln_w', f32_mult=2.0, model=part(c['m'], 'dln_w'))
+    close(dlb, c['lbr'].grad, dt, 'mlp_stream dln_b', f32_mult=2.0, model=part(c['m'], 'dln_b'))
 
 
 @pytest.mark.parametrize('dt', DTYPES)
@@ -975,7 +1041,7 @@ def test_mlp_stream_bwd_wgrad(backend, dt, M, grid):
         s2, cs2 = torch.zeros(C, 4 * C, device=backend), torch.zeros(C, device=backend)
         for _ in range(2):
             ops.mlp_bwd_recompute_wgrad(c['dy'], c['x'], c['lw'], c['lb'], c['w1'], c['b1'], c['w2g_t'], dw1, db1, s2, cs2, 1e-5)
-    close(dw1, 2 * c['w1r'].grad, dt, 'mlp_stream dW1', f32_mult=2.0)
-    close(db1, 2 * c['b1r'].grad, dt, 'mlp_stream db1', f32_mult=2.0)
-    close(s2, 2 * f64(c['dy']).t() @ c['g'], dt, 'mlp_stream S2', f32_mult=2.0)
-    close(cs2, 2 * f64(c['dy']).sum(0), dt, 'mlp_stream cs2')
+    close(dw1, 2 * c['w1r'].grad, dt, 'mlp_stream dW1', f32_mult=2.0, model=part(c['m'], 'dW1', 2))
+    close(db1, 2 * c['b1r'].grad, dt, 'mlp_stream db1', f32_mult=2.0, model=part(c['m'], 'db1', 2))
+    close(s2, 2 * f64(c['dy']).t() @ c['g'], dt, 'mlp_stream S2', f32_mult=2.0, model=part(c['m'], 'S2', 2))
+    close(cs2, 2 * f64(c['dy']).sum(0), dt, 'mlp_stream cs2', model=part(c['m'], 'cs2', 2))
