@@ -23,6 +23,7 @@
  *       rvt_stage_seq_fwd (+ _ws_bytes)                one call per backbone stage and sequence (no-grad forward)
  *       rvt_stacked_histogram                          event stream -> input tensor (row f4)
  *       rvt_event_sequence (+ _ws_bytes)               B raw event streams -> a whole (T, B, 2*bins, H', W') window sequence, slicing + half-scale
+ *       rvt_event_time_repair / rvt_event_decode_dat (+ rvt_event_prep_ws_bytes)   timestamp repair in place; packed Prophesee records -> stream
  *       rvt_mixed_density_stack                        event stream -> the int8 (bins, H, W) mixed-density stack of one window
  *       rvt_event_sequence_mixed (+ _ws_bytes)         B raw event streams -> a whole int8 (T, B, bins, H', W') mixed-density sequence
  *       rvt_yolox_decode / rvt_simota_loss (+ _ws_bytes) / rvt_yolox_decode_bwd        detection tail (row f3)
@@ -655,7 +656,7 @@ typedef struct RvtEventStream {
     const void* x;            /* n coordinates / polarities each */
     const void* y;
     const void* p;
-    const long long* t;       /* n timestamps in microseconds, NON-DECREASING (the reference reader's timestamp repair is the caller's) */
+    const long long* t;       /* n timestamps in microseconds, NON-DECREASING (rvt_event_time_repair / rvt_event_decode_dat below make them so) */
     long long n;
     const long long* ts_end;  /* the T window end timestamps of that sample (rows may share one array) */
 } RvtEventStream;
@@ -663,6 +664,32 @@ size_t rvt_event_sequence_ws_bytes(int bins, int H, int W, int downsample_by_2, 
 int rvt_event_sequence(const RvtEventStream* streams, int B, int T, int coord_bytes, long long window_us, long long window_events, int bins,
                        int H, int W, int downsample_by_2, int count_cutoff, int fastmode, long long* bounds, void* scratch,
                        int windows_in_flight, int count_blocks, unsigned char* out, void* stream);
+
+/* What comes before the event stream (rvt_amd/csrc/evprep.hpp; host mirrors rvt_amd.representations.repair_time and
+ * rvt_amd.recordings.DatDecoder): the reference reader's timestamp repair (scripts/genx/preprocess_dataset.py:163-172, _correct_time)
+ * and the decode of packed Prophesee Event2D records (utils/evaluation/prophesee/io/dat_events_tools.py:41-50, load_td_data).
+ * rvt_event_sequence keeps its precondition (t non-decreasing); these entries are what establishes it.  Integer work: bit-exact.
+ *
+ * Repair: t_out[i] = max(c, t[0], ..., t[i]) over the n timestamps of a row, c = carry[b] when carry is non-null, else 0 (the
+ *   reference starts at 0, so negative timestamps become 0).  With carry, carry[b] = max(c, every t) afterwards: a producer that
+ *   delivers a stream in chunks gets exactly the repair of the concatenated stream.  carry int64 [B].
+ * Two launches, grid (blocks_per_stream, B), each workgroup one contiguous span of its stream; no workgroup waits for another.
+ *   The first reduces the spans to maxima in ws and parks the carry-in there (the only reader of carry), the second scans and
+ *   writes carry (its only writer).  blocks_per_stream 0..4096, 0 = sized by the library; ws: rvt_event_prep_ws_bytes(B,
+ *   blocks_per_stream) bytes, 8-byte aligned, any contents; with K = that size / (8 * B) - 1 workgroups per stream,
+ *   repaired (optional) int64 [B][K]: workgroup k of stream b WRITES the number of timestamps it changed into [b][k].
+ * rvt_event_time_repair: in place on the t arrays of the B rows (n read on the device); only changed timestamps are stored.
+ * rvt_event_decode_dat: records = DEVICE array of B device pointers to packed records {uint32 t; int32 w}, each 8-byte aligned;
+ *   n_records int64 [B] on the device.  n = min(n_records[b], capacity) records are decoded from index 0 into the x, y, p, t
+ *   arrays row b points at (coord_bytes = 2, 4 or 8 for x, y, p) and n is written into row b: x = w & 16383, y = (w >> 14) & 16383,
+ *   p = (w >> 28) & 1, t zero-extended.  Nothing behind index n is written.  A captured graph replays after the host rewrote
+ *   records and n_records in place.  repair != 0: the timestamps are repaired in the same pass (records read twice, stream
+ *   written once); repair == 0: one launch, carry and ws are not touched (ws may be null).  16-byte accesses where a base is 16-byte aligned. */
+size_t rvt_event_prep_ws_bytes(int B, int blocks_per_stream);
+int rvt_event_time_repair(const RvtEventStream* streams, int B, long long* carry, long long* repaired, void* ws, int blocks_per_stream,
+                          void* stream);
+int rvt_event_decode_dat(const void* const* records, const long long* n_records, long long capacity, RvtEventStream* streams, int B,
+                         int coord_bytes, int repair, long long* carry, long long* repaired, void* ws, int blocks_per_stream, void* stream);
 
 /* The reference's second representation, MixedDensityEventStack (data/utils/representations.py:130-218, selected by
  * scripts/genx/conf_preprocess/representation/mixeddensity_stack.yaml, built in scripts/genx/preprocess_dataset.py:663-679), on the

@@ -2,10 +2,12 @@
 // slicing and half-scale down-sampling on the device (evseq.hpp; reference scripts/genx/preprocess_dataset.py:480-534 and
 // data/utils/representations.py:130-218).  Compiled without fused multiply-add contraction and without fast-math (Makefile): the
 // bin rules are one correctly rounded fp32 division and one product (histogram) or that division's exponent (mixed density).
+// Also what comes before the stream (evprep.hpp): the decode of packed Prophesee records and the reader's timestamp repair.
 #include <stdint.h>
 
 #include "host.hpp"
 #include "evseq.hpp"
+#include "evprep.hpp"
 
 using namespace rvt;
 
@@ -81,7 +83,68 @@ static int evseq_run(const char* what, int rep, const RvtEventStream* streams, i
     return check_launch(what);
 }
 
+// workgroups per stream when the caller leaves the choice to the library: about 2048 over the batch
+static int evprep_blocks(int B, int blocks_per_stream) {
+    return blocks_per_stream > 0 ? blocks_per_stream : imax(8, imin(1024, 2048 / B));
+}
+
+static int evprep_check(const char* what, const void* streams, int B, const void* carry, const void* repaired, const void* ws,
+                        bool need_ws, int blocks_per_stream) {
+    RVT_CHECK(streams && (ws || !need_ws), "%s: null argument", what);
+    RVT_CHECK(B >= 1 && B <= 65535, "%s: B=%d outside 1..65535", what, B);
+    RVT_CHECK(blocks_per_stream >= 0 && blocks_per_stream <= EVPREP_MAX_BLOCKS, "%s: blocks_per_stream=%d outside 0..%d", what,
+              blocks_per_stream, EVPREP_MAX_BLOCKS);
+    RVT_CHECK((((uintptr_t)streams | (uintptr_t)carry | (uintptr_t)repaired | (uintptr_t)ws) & 7) == 0,
+              "%s: streams, carry, repaired and ws must be 8-byte aligned", what);
+    return 0;
+}
+
+template <class CT>
+static void evprep_launch_decode(dim3 grid, hipStream_t st, EvStream* table, const void* const* records, const long long* n_records,
+                                 long long capacity, int repair, long long* carry, long long* repaired, const long long* ws) {
+    hipLaunchKernelGGL((evprep_scan_kernel<EVPREP_DECODE, CT>), grid, dim3(EVPREP_THREADS), 0, st, table, records, n_records, capacity, repair,
+                       carry, repaired, ws);
+}
+
 extern "C" {
+
+size_t rvt_event_prep_ws_bytes(int B, int blocks_per_stream) {
+    if (B < 1 || B > 65535 || blocks_per_stream < 0 || blocks_per_stream > EVPREP_MAX_BLOCKS) return 0;
+    return (size_t)B * (evprep_blocks(B, blocks_per_stream) + 1) * sizeof(long long);
+}
+
+int rvt_event_time_repair(const RvtEventStream* streams, int B, long long* carry, long long* repaired, void* ws, int blocks_per_stream,
+                          void* stream) {
+    if (evprep_check("event_time_repair", streams, B, carry, repaired, ws, true, blocks_per_stream)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    // (the rows are const for the caller: this entry writes the timestamps they point at, never the rows)
+    EvStream* table = const_cast<EvStream*>(static_cast<const EvStream*>(streams));
+    const dim3 grid((unsigned)evprep_blocks(B, blocks_per_stream), (unsigned)B);
+    hipLaunchKernelGGL(evprep_reduce_kernel<EVPREP_REPAIR>, grid, dim3(EVPREP_THREADS), 0, st, (const EvStream*)table,
+                       (const void* const*)nullptr, (const long long*)nullptr, 0LL, (const long long*)carry, (long long*)ws);
+    hipLaunchKernelGGL((evprep_scan_kernel<EVPREP_REPAIR, short>), grid, dim3(EVPREP_THREADS), 0, st, table, (const void* const*)nullptr,
+                       (const long long*)nullptr, 0LL, 1, carry, repaired, (const long long*)ws);
+    return check_launch("event_time_repair");
+}
+
+int rvt_event_decode_dat(const void* const* records, const long long* n_records, long long capacity, RvtEventStream* streams, int B,
+                         int coord_bytes, int repair, long long* carry, long long* repaired, void* ws, int blocks_per_stream, void* stream) {
+    if (evprep_check("event_decode_dat", streams, B, carry, repaired, ws, repair != 0, blocks_per_stream)) return 1;
+    RVT_CHECK(records && n_records && (((uintptr_t)records | (uintptr_t)n_records) & 7) == 0,
+              "event_decode_dat: records / n_records null or not 8-byte aligned");
+    RVT_CHECK(capacity >= 0, "event_decode_dat: capacity=%lld is negative", capacity);
+    RVT_CHECK(coord_bytes == 2 || coord_bytes == 4 || coord_bytes == 8, "event_decode_dat: coord_bytes=%d is not 2, 4 or 8", coord_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    EvStream* table = static_cast<EvStream*>(streams);
+    const dim3 grid((unsigned)evprep_blocks(B, blocks_per_stream), (unsigned)B);
+    if (repair)
+        hipLaunchKernelGGL(evprep_reduce_kernel<EVPREP_DECODE>, grid, dim3(EVPREP_THREADS), 0, st, (const EvStream*)table, records, n_records,
+                           capacity, (const long long*)carry, (long long*)ws);
+    if (coord_bytes == 2) evprep_launch_decode<short>(grid, st, table, records, n_records, capacity, repair ? 1 : 0, carry, repaired, (const long long*)ws);
+    else if (coord_bytes == 4) evprep_launch_decode<int>(grid, st, table, records, n_records, capacity, repair ? 1 : 0, carry, repaired, (const long long*)ws);
+    else evprep_launch_decode<long long>(grid, st, table, records, n_records, capacity, repair ? 1 : 0, carry, repaired, (const long long*)ws);
+    return check_launch("event_decode_dat");
+}
 
 size_t rvt_event_sequence_ws_bytes(int bins, int H, int W, int downsample_by_2, int windows_in_flight) {
     if (bins < 1 || H < 1 || W < 1 || windows_in_flight < 1) return 0;

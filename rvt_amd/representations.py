@@ -35,9 +35,14 @@ the reference's own fp32 ``log`` quotient rounds to an integer for events a few 
 bin too high (span 2^24, offset 8 388 606: reference bin 9, exact bin 8); the device returns the mathematically exact bin there.
 int8 planes go straight into ``RNNDetector.forward`` / ``forward_sequence`` (no float32 copy).
 
-Out of scope: reading H5 files; the reader's timestamp repair (``_correct_time``): ``t`` must be
-non-decreasing, which is the caller's to guarantee (the searches and the bin rule assume it, as the reference does).
-There is no PyTorch fallback: a missing kernel raises.
+``t`` must be non-decreasing when the windows are sliced (the searches and the bin rule assume it, as the reference does).
+The reference reader's repair (``H5Reader._correct_time``, preprocess_dataset.py:163-172: ``t[i] = max(0, t[0..i])``) is
+``repair_time(streams_or_table, carry=None, out_repaired=False)`` here (rvt_event_time_repair, rvt_amd/csrc/evprep.hpp), in place
+on the device, and ``EventSequenceBuilder(..., repair_time=True)`` runs it over the table ahead of the bounds launch.  With a
+``carry`` tensor (int64 ``[B]``) a stream delivered in chunks gets the repair of the concatenated stream.  Raw Prophesee
+recordings come in through ``rvt_amd.recordings``.
+
+Out of scope: reading H5 files.  There is no PyTorch fallback: a missing kernel raises.
 """
 from __future__ import annotations
 
@@ -151,7 +156,7 @@ class EventTable:
 class EventSequenceBuilder:
     def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int] = None, fastmode: bool = True,
                  downsample_by_2: bool = False, window_us: Optional[int] = None, window_events: Optional[int] = None,
-                 max_windows_in_flight: Optional[int] = None, representation: str = 'stacked_histogram'):
+                 max_windows_in_flight: Optional[int] = None, representation: str = 'stacked_histogram', repair_time: bool = False):
         if representation not in REPRESENTATIONS:
             raise ValueError(f'representation={representation!r} is not one of {REPRESENTATIONS}')
         mixed = representation == 'mixed_density'
@@ -182,7 +187,9 @@ class EventSequenceBuilder:
         self.fastmode, self.downsample_by_2 = bool(fastmode), bool(downsample_by_2)
         self.window_us, self.window_events = window_us, window_events
         self.max_windows_in_flight = max_windows_in_flight
+        self.repair_time = bool(repair_time)
         self._scratch = None
+        self._prep_ws = None
 
     def get_shape(self) -> Tuple[int, int, int]:
         """(2*bins, H', W') of one window, after the down-sampling; (bins, H', W') for the mixed-density stack."""
@@ -254,8 +261,12 @@ class EventSequenceBuilder:
     def windows_in_flight(self, windows: int) -> int:
         return min(windows, self.max_windows_in_flight or DEFAULT_WINDOWS_IN_FLIGHT)
 
-    def workspace(self, device, windows: int) -> torch.Tensor:
-        """The zeroed scratch images (the call keeps them zero); allocate ahead of a graph capture by calling this once."""
+    def workspace(self, device, windows: int, B: Optional[int] = None) -> torch.Tensor:
+        """The zeroed scratch images (the call keeps them zero); allocate ahead of a graph capture by calling this once.
+        With repair_time, B streams: the repair's workspace as well."""
+        if self.repair_time and B is not None and (self._prep_ws is None or not same_device(self._prep_ws.device, device)
+                                                   or self._prep_ws.numel() < prep_ws_elems(B)):
+            self._prep_ws = torch.empty(prep_ws_elems(B), dtype=torch.int64, device=device)
         C, H, W = self.get_shape()
         lib = L.get_lib()
         ws_bytes = lib.rvt_event_sequence_mixed_ws_bytes if self.mixed else lib.rvt_event_sequence_ws_bytes
@@ -276,7 +287,9 @@ class EventSequenceBuilder:
             bounds_out = torch.empty(B, T, 2, dtype=torch.int64, device=dev)
         elif tuple(bounds_out.shape) != (B, T, 2) or bounds_out.dtype != torch.int64 or bounds_out.device != dev or not bounds_out.is_contiguous():
             raise ValueError(f'bounds_out must be contiguous int64 {(B, T, 2)} on {dev}, got {bounds_out.dtype} {tuple(bounds_out.shape)}')
-        scratch = self.workspace(dev, B * T)
+        scratch = self.workspace(dev, B * T, B)
+        if self.repair_time:                                   # in place, no carry: every table is a whole stream
+            L.call('rvt_event_time_repair', L.ptr(table.dev), B, None, None, L.ptr(self._prep_ws), 0, L.stream_of(out))
         # workgroups per window: the grid cannot follow bounds that live on the device, but never needs more than the capacity gives
         count_blocks = max(1, min(256, -(-table.capacity // 8192)))
         if self.mixed:
@@ -294,3 +307,62 @@ class EventSequenceBuilder:
         """streams: B tuples (x, y, p, t) of device tensors; ts_end_us int64 [T] or [B][T] -> (planes uint8 (T, B, C, H', W'),
         bounds int64 [B][T][2]); int8 planes for the mixed-density stack."""
         return self.build_from_table(self.make_table(streams, ts_end_us), out, bounds_out)
+
+
+# ---- timestamp repair (rvt_amd/csrc/evprep.hpp)
+def same_device(a, b) -> bool:
+    """Do two device specifications name one device?  'cuda' without an index is the current device."""
+    def resolve(d):
+        d = torch.device(d)
+        if d.type != 'cuda':
+            return d.type, d.index or 0
+        return d.type, torch.cuda.current_device() if d.index is None else d.index
+    return resolve(a) == resolve(b)
+
+
+def prep_ws_elems(B: int, blocks_per_stream: int = 0) -> int:
+    """int64 elements of the workspace rvt_event_time_repair / rvt_event_decode_dat need for B streams."""
+    n = L.get_lib().rvt_event_prep_ws_bytes(int(B), int(blocks_per_stream)) // 8
+    if n < 1:
+        raise ValueError(f'B={B}, blocks_per_stream={blocks_per_stream} out of range')
+    return n
+
+
+def prep_blocks(B: int, blocks_per_stream: int = 0) -> int:
+    """Workgroups per stream of those entries (the second dimension of their ``repaired`` output)."""
+    return prep_ws_elems(B, blocks_per_stream) // B - 1
+
+
+def check_carry(carry: Optional[torch.Tensor], B: int, dev) -> None:
+    if carry is not None and (not torch.is_tensor(carry) or carry.dtype != torch.int64 or tuple(carry.shape) != (B,) or carry.device != dev
+                              or not carry.is_contiguous()):
+        raise ValueError(f'carry must be a contiguous int64 [{B}] tensor on {dev}')
+
+
+def repair_time(streams_or_table: Union[EventTable, Sequence[Stream]], carry: Optional[torch.Tensor] = None, out_repaired: bool = False,
+                blocks_per_stream: int = 0, ws: Optional[torch.Tensor] = None):
+    """Make the timestamps of B streams non-decreasing, in place: ``t[i] = max(c, t[0..i])`` with ``c = carry[b]``, or 0 without a
+    carry (the reference reader's ``_correct_time``).  streams_or_table: B tuples ``(x, y, p, t)`` or an ``EventTable`` (its counts
+    are honoured).  carry int64 ``[B]`` receives ``max(c, every t)``: chunks repaired one after the other with one carry equal the
+    repair of the concatenated stream.  out_repaired: return int64 ``[B][K]`` counts of changed timestamps (sum over K per stream),
+    else None.  ws: an int64 workspace of ``prep_ws_elems(B, blocks_per_stream)`` elements, for callers that capture a graph."""
+    if isinstance(streams_or_table, EventTable):
+        table = streams_or_table
+    else:
+        streams = [tuple(s) for s in streams_or_table]
+        if not streams:
+            raise ValueError('streams is empty')
+        t0 = streams[0][3]
+        # (the window ends are not read by the repair: any int64 tensor stands in for them)
+        table = EventSequenceBuilder(1, 1, 1, window_us=1).make_table(streams, torch.zeros(1, dtype=torch.int64, device=t0.device))
+    B, dev = table.B, table.dev.device
+    check_carry(carry, B, dev)
+    need = prep_ws_elems(B, blocks_per_stream)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.int64, device=dev)
+    elif ws.dtype != torch.int64 or ws.numel() < need or ws.device != dev or not ws.is_contiguous():
+        raise ValueError(f'ws must be a contiguous int64 tensor of at least {need} elements on {dev}')
+    repaired = torch.empty(B, prep_blocks(B, blocks_per_stream), dtype=torch.int64, device=dev) if out_repaired else None
+    L.call('rvt_event_time_repair', L.ptr(table.dev), B, L.ptr(carry), L.ptr(repaired), L.ptr(ws), int(blocks_per_stream),
+           L.stream_of(table.dev))
+    return repaired
