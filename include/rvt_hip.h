@@ -30,6 +30,7 @@
  *       rvt_yolox_postprocess (+ _ws_bytes)            eval-mode detections -> score filter + batched NMS
  *       rvt_yolox_detect (+ _ws_bytes)                 head maps -> decode + score filter + batched NMS, one launch
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
+ *       rvt_frames_pack (+ _ws_bytes) / rvt_frames_unpack   byte planes <-> bitmap + non-zero bytes, unpacked by frame index (the compact store)
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *       rvt_optim_step                                 value clip + AdamW + OneCycle schedule of every parameter, one call per step
@@ -751,6 +752,41 @@ int rvt_event_sequence_mixed(const RvtEventStream* streams, int B, int T, int co
 int rvt_augment_planes(const void* in, void* out, const int* table, int F, int B, int C, int H, int W, void* stream);
 int rvt_augment_labels(const float* rows, const int* count, const float* table, int F, int B, int G, float* rows_out, int* count_out,
                        float* yolox_out, void* stream);
+
+/* Sparse frame cache (rvt_amd/csrc/framecache.hpp; host mirror rvt_amd/framecache.py): a lossless codec for byte planes that are
+ * mostly zero, the device counterpart of the reference's compressed pre-processed store (data/genx_utils/sequence_base.py:92-102).
+ * Built event tensors are kept as a bitmap plus their non-zero bytes and fetched back by frame index.  Integer work: bit-exact.
+ *
+ * Format, version 1.  A frame is E bytes (uint8, or int8 seen as uint8), 1 <= E < 2^31, a multiple of nothing; a packed set holds F
+ * frames of one E.  A group is 64 consecutive bytes of a frame, Gf = ceil(E / 64); a segment is 64 consecutive groups (4096
+ * bytes), Sf = ceil(Gf / 64).
+ *   masks      uint64 [F][Gf]      bit i of group g is set iff byte 64 g + i of the frame exists and is non-zero (the bits of the last
+ *                                  group beyond E are 0)
+ *   seg_offset uint32 [F][Sf + 1]  exclusive prefix sum of the per-segment non-zero counts of the frame; the last entry is the frame's count
+ *   value_base int64  [F + 1]      exclusive prefix sum of the frames' counts; value_base[F] is the total, nnz
+ *   values     uint8  [capacity]   the non-zero bytes of all frames, frame order then byte order, no padding
+ *   status     int32  [1]          bit 0: pack ran out of capacity;  bit 1: unpack met an index outside [-1, F)
+ * Packed size: 8 Gf F + 4 (Sf + 1) F + 8 (F + 1) + nnz bytes.
+ *
+ * rvt_frames_pack: frames [F][E] -> masks, seg_offset, value_base, values, status.  Four launches on the stream (masks + counts,
+ *   the two prefix sums, value compaction; three when capacity is 0), no host synchronisation, no allocation; ws:
+ *   rvt_frames_pack_ws_bytes(F, E) bytes (0 = F or E out of range), 4-byte aligned, any contents.  status is WRITTEN: 1 when
+ *   nnz > capacity, else 0.  Out of capacity, masks, seg_offset and value_base are still complete (value_base[F] is the room a retry
+ *   needs) and exactly the value bytes below `capacity` are written.  Nothing behind values[min(nnz, capacity)] is written, and a
+ *   run's first and last bytes leave by byte stores: memory next to the run is never read and rewritten.  16-byte loads when a frame
+ *   starts on a 16-byte boundary (frames aligned and E % 16 == 0), byte loads otherwise.
+ * rvt_frames_unpack: out [Fout][E], frame i = frame index[i] of the packed set (index int64 [Fout] on the device; NULL = frames
+ *   0 .. Fout-1 in order).  index -1 writes a zero frame (the padded tail of a stream); any other index outside [0, F) writes a zero
+ *   frame and ORS bit 1 into status (nothing else touches status: clear it before the call to read it afterwards).  One launch, no
+ *   workspace; replays in a hipGraph after the packed arrays and the index were rewritten in place.  Reads of values stay inside
+ *   [0, values_len) whatever the arrays hold; out is written as whole aligned 16-byte lines with byte stores only at the ends of a
+ *   4096-byte segment that does not start or end on one, so out may sit at any byte address and nothing outside out[Fout][E] is
+ *   written.  masks / value_base / index 8-byte, seg_offset / status 4-byte aligned. */
+size_t rvt_frames_pack_ws_bytes(long long F, long long E);
+int rvt_frames_pack(const void* frames, long long F, long long E, void* masks, void* seg_offset, void* value_base, void* values,
+                    long long capacity, void* status, void* ws, size_t ws_bytes, void* stream);
+int rvt_frames_unpack(const void* masks, const void* seg_offset, const void* value_base, const void* values, long long values_len,
+                      long long F, long long E, const long long* index, long long Fout, void* out, void* status, void* stream);
 
 /* The optimizer step on the device (rvt_amd/csrc/optim.hpp; host mirror rvt_amd/optim.py): gradient clipping by value, AdamW
  * (decoupled weight decay, no amsgrad) and the OneCycle learning-rate schedule of every parameter of every parameter group in one

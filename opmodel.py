@@ -193,6 +193,12 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, 1.0 * F * (max_det * 7 * 4 + 4 + G * 7 * 4 + 4 + 8) + 24.0 * F * a.rec_stride + 80.0, 0.0
     if name == 'rvt_coco_accumulate':                            # permutation + the two mask planes read twice (count, emit); table out
         return 0.0, 2.0 * 24 * a.n_slots + 10 * 101 * a.num_classes * 4 * 8.0, 0.0
+    # sparse frame cache: no nnz among the arguments, so a launch is priced at what its arrays admit (pack: every byte non-zero up to
+    # `capacity`; unpack: the whole values array read).  frames_pack_bytes / frames_unpack_bytes take the measured nnz.
+    if name == 'rvt_frames_pack':
+        return 0.0, frames_pack_bytes(a.F, a.E, min(a.capacity, a.F * a.E)), 0.0
+    if name == 'rvt_frames_unpack':
+        return 0.0, frames_unpack_bytes(a.Fout, a.E, a.values_len), 0.0
     return None
 
 
@@ -212,6 +218,25 @@ def augment_planes_bytes(F: int, C: int, H: int, W: int, windows) -> float:
         read = {1: zh * zw, 2: zh * W}.get(mode, H * W)
         total += C * (H * W + read)
     return total
+
+
+def _frames_meta_bytes(E: int) -> int:
+    """masks + seg_offset + one value_base entry of one frame of E bytes (format version 1, include/rvt_hip.h)."""
+    Gf = (E + 63) // 64
+    Sf = (Gf + 63) // 64
+    return 8 * Gf + 4 * (Sf + 1) + 8
+
+
+def frames_pack_bytes(F: int, E: int, nnz: int) -> float:
+    """HBM bytes of one rvt_frames_pack when nnz is known: the dense frames read twice (masks, then compaction) and the packed set
+    (8 Gf F + 4 (Sf + 1) F + 8 (F + 1) + nnz) written once.  The workspace (4 bytes per segment, written and read) is not counted."""
+    return 2.0 * F * E + F * _frames_meta_bytes(E) + 8 + nnz
+
+
+def frames_unpack_bytes(Fout: int, E: int, nnz: int) -> float:
+    """HBM bytes of one rvt_frames_unpack that fetches Fout frames holding nnz non-zero bytes between them: their masks, seg_offset
+    rows, value_base entries and index entries read, their values read, the dense frames written."""
+    return 1.0 * Fout * E + Fout * (_frames_meta_bytes(E) + 8) + nnz
 
 
 def executed(name: str, args) -> Optional[float]:

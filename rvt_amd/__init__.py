@@ -5,3 +5,5 @@ from .detector import YoloXDetector  # noqa: F401,E402  (backbone + PAFPN + head
 from .postprocess import postprocess, postprocess_padded  # noqa: F401,E402  (detection post-processing: score filter + batched NMS)
 from .evaluation import DetectionEvaluator, PropheseeEvaluator  # noqa: F401,E402  (Prophesee / COCO mAP of the detections, on the device)
 from . import optim  # noqa: F401,E402  (optimizer step on the device: value clip + AdamW + OneCycleLR in one launch)
+from . import framecache  # noqa: F401,E402  (sparse frame cache: event tensors packed on the device, unpacked by frame index)
+from .framecache import PackedFrames, pack_frames, unpack_frames  # noqa: F401,E402

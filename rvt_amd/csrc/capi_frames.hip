@@ -1,0 +1,79 @@
+// extern "C" entry points, part 16: the sparse frame cache (framecache.hpp): byte planes packed to bitmap + non-zero bytes on the
+// device and unpacked by frame index.  Integer work: bit-exact.
+#include <stdint.h>
+
+#include "host.hpp"
+#include "framecache.hpp"
+
+using namespace rvt;
+
+namespace {
+struct FrameGeom { long long Gf, Sf; };
+static inline FrameGeom frame_geom(long long E) {
+    const long long Gf = (E + FC_GROUP - 1) / FC_GROUP;
+    return FrameGeom{Gf, (Gf + 63) / 64};
+}
+static inline bool frames_shape_ok(long long F, long long E) { return F >= 1 && F <= 0x7fffffffLL && E >= 1 && E < (1LL << 31); }
+// one wave per segment, FC_WAVES of them per workgroup
+static inline bool frames_grid(long long waves, dim3& grid) {
+    const long long blocks = (waves + FC_WAVES - 1) / FC_WAVES;
+    if (blocks > 0x7fffffffLL) return false;
+    grid = dim3((unsigned)blocks);
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+size_t rvt_frames_pack_ws_bytes(long long F, long long E) {
+    if (!frames_shape_ok(F, E)) return 0;
+    const FrameGeom g = frame_geom(E);
+    return (((size_t)F * (size_t)g.Sf + (size_t)F) * 4 + 15) & ~(size_t)15;   // the segments' counts, then the frames'
+}
+
+int rvt_frames_pack(const void* frames, long long F, long long E, void* masks, void* seg_offset, void* value_base, void* values,
+                    long long capacity, void* status, void* ws, size_t ws_bytes, void* stream) {
+    RVT_CHECK(frames && masks && seg_offset && value_base && status && ws, "frames_pack: null argument");
+    RVT_CHECK(frames_shape_ok(F, E), "frames_pack: F=%lld frames of E=%lld bytes outside the supported range (F >= 1, 1 <= E < 2^31)", F, E);
+    RVT_CHECK(capacity >= 0 && (values || capacity == 0), "frames_pack: capacity=%lld without a values array", capacity);
+    RVT_CHECK(ws_bytes >= rvt_frames_pack_ws_bytes(F, E), "frames_pack: workspace of %zu bytes, rvt_frames_pack_ws_bytes says %zu", ws_bytes,
+              rvt_frames_pack_ws_bytes(F, E));
+    RVT_CHECK(((uintptr_t)masks & 7) == 0 && ((uintptr_t)value_base & 7) == 0 && ((uintptr_t)seg_offset & 3) == 0 &&
+              ((uintptr_t)status & 3) == 0 && ((uintptr_t)ws & 3) == 0, "frames_pack: masks / value_base need 8-byte, seg_offset / status / ws 4-byte alignment");
+    const FrameGeom g = frame_geom(E);
+    dim3 grid;
+    RVT_CHECK(frames_grid(F * g.Sf, grid), "frames_pack: F=%lld frames of %lld segments exceed the grid", F, g.Sf);
+    unsigned* seg_count = (unsigned*)ws;
+    unsigned* frame_count = seg_count + (size_t)F * (size_t)g.Sf;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(frames_mask_kernel, grid, dim3(FC_THREADS), 0, st, (const unsigned char*)frames, F, E, g.Gf, g.Sf,
+                       (unsigned long long*)masks, seg_count);
+    hipLaunchKernelGGL(frames_seg_scan_kernel, dim3((unsigned)F), dim3(FC_THREADS), 0, st, (const unsigned*)seg_count, g.Sf,
+                       (unsigned*)seg_offset, frame_count);
+    hipLaunchKernelGGL(frames_base_scan_kernel, dim3(1), dim3(FC_THREADS), 0, st, (const unsigned*)frame_count, F, capacity,
+                       (long long*)value_base, (int*)status);
+    if (capacity > 0)
+        hipLaunchKernelGGL(frames_compact_kernel, grid, dim3(FC_THREADS), 0, st, (const unsigned char*)frames, F, E, g.Sf,
+                           (const unsigned*)seg_offset, (const long long*)value_base, (unsigned char*)values, capacity);
+    return check_launch("frames_pack");
+}
+
+int rvt_frames_unpack(const void* masks, const void* seg_offset, const void* value_base, const void* values, long long values_len,
+                      long long F, long long E, const long long* index, long long Fout, void* out, void* status, void* stream) {
+    RVT_CHECK(masks && seg_offset && value_base && out && status, "frames_unpack: null argument");
+    RVT_CHECK(frames_shape_ok(F, E) && Fout >= 1, "frames_unpack: F=%lld, Fout=%lld frames of E=%lld bytes outside the supported range", F, Fout, E);
+    RVT_CHECK(values_len >= 0 && (values || values_len == 0), "frames_unpack: values_len=%lld without a values array", values_len);
+    RVT_CHECK(index || Fout <= F, "frames_unpack: without an index Fout=%lld must not exceed F=%lld", Fout, F);
+    RVT_CHECK(((uintptr_t)masks & 7) == 0 && ((uintptr_t)value_base & 7) == 0 && ((uintptr_t)index & 7) == 0 &&
+              ((uintptr_t)seg_offset & 3) == 0 && ((uintptr_t)status & 3) == 0,
+              "frames_unpack: masks / value_base / index need 8-byte, seg_offset / status 4-byte alignment");
+    const FrameGeom g = frame_geom(E);
+    dim3 grid;
+    RVT_CHECK(Fout <= 0x7fffffffLL && frames_grid(Fout * g.Sf, grid), "frames_unpack: Fout=%lld frames of %lld segments exceed the grid", Fout, g.Sf);
+    hipLaunchKernelGGL(frames_unpack_kernel, grid, dim3(FC_THREADS), 0, (hipStream_t)stream, (const unsigned long long*)masks,
+                       (const unsigned*)seg_offset, (const long long*)value_base, (const unsigned char*)values, values_len, F, E, g.Gf, g.Sf,
+                       index, Fout, (unsigned char*)out, (int*)status);
+    return check_launch("frames_unpack");
+}
+
+}  // extern "C"
