@@ -31,6 +31,7 @@
  *       rvt_yolox_detect (+ _ws_bytes)                 head maps -> decode + score filter + batched NMS, one launch
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
  *       rvt_frames_pack (+ _ws_bytes) / rvt_frames_unpack   byte planes <-> bitmap + non-zero bytes, unpacked by frame index (the compact store)
+ *       rvt_frames_unpack_augment                      packed frames by index -> flipped / zoomed planes, unpack + augmentation in one launch
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *       rvt_optim_step                                 value clip + AdamW + OneCycle schedule of every parameter, one call per step
@@ -781,12 +782,25 @@ int rvt_augment_labels(const float* rows, const int* count, const float* table, 
  *   workspace; replays in a hipGraph after the packed arrays and the index were rewritten in place.  Reads of values stay inside
  *   [0, values_len) whatever the arrays hold; out is written as whole aligned 16-byte lines with byte stores only at the ends of a
  *   4096-byte segment that does not start or end on one, so out may sit at any byte address and nothing outside out[Fout][E] is
- *   written.  masks / value_base / index 8-byte, seg_offset / status 4-byte aligned. */
+ *   written.  masks / value_base / index 8-byte, seg_offset / status 4-byte aligned.
+ * rvt_frames_unpack_augment: out [Fout][C][H][W] = rvt_augment_planes(rvt_frames_unpack(..., index), table), bit for bit, in one
+ *   launch and without the dense tensor between the two (rvt_amd/csrc/frames_augment.hpp).  E must equal C*H*W.  Output frame i is
+ *   packed frame index[i] (NULL = frame i) transformed by table row i % B; the table is rvt_augment_planes' int32 [B][8] (flip,
+ *   mode, x0, y0, zh, zw, 0, 0) and is clamped into the frame in the same way.  index -1 writes a zero frame whatever the table
+ *   says; any other index outside [0, F) writes a zero frame and ORS bit 1 into status.  Several output frames may name one packed
+ *   frame under different table rows.  Bytes are moved, never interpreted (an int8 store works as uint8).  One launch, no workspace,
+ *   no allocation, no host synchronisation; replays in a hipGraph after index, table and the packed arrays were rewritten in
+ *   place.  Reads of values stay inside [0, values_len) and mask bits behind a frame's end are ignored whatever the arrays hold;
+ *   nothing outside out[Fout][E] is written.  16-byte stores when W % 16 == 0 and out is 16-byte aligned, byte accesses otherwise.
+ *   Supported: 1 <= W <= 2048, C*H <= 2^24; masks / value_base / index 8-byte, seg_offset / status / table 4-byte aligned. */
 size_t rvt_frames_pack_ws_bytes(long long F, long long E);
 int rvt_frames_pack(const void* frames, long long F, long long E, void* masks, void* seg_offset, void* value_base, void* values,
                     long long capacity, void* status, void* ws, size_t ws_bytes, void* stream);
 int rvt_frames_unpack(const void* masks, const void* seg_offset, const void* value_base, const void* values, long long values_len,
                       long long F, long long E, const long long* index, long long Fout, void* out, void* status, void* stream);
+int rvt_frames_unpack_augment(const void* masks, const void* seg_offset, const void* value_base, const void* values,
+                              long long values_len, long long F, long long E, const long long* index, long long Fout,
+                              const int* table, int B, int C, int H, int W, void* out, void* status, void* stream);
 
 /* The optimizer step on the device (rvt_amd/csrc/optim.hpp; host mirror rvt_amd/optim.py): gradient clipping by value, AdamW
  * (decoupled weight decay, no amsgrad) and the OneCycle learning-rate schedule of every parameter of every parameter group in one

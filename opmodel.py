@@ -199,6 +199,8 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, frames_pack_bytes(a.F, a.E, min(a.capacity, a.F * a.E)), 0.0
     if name == 'rvt_frames_unpack':
         return 0.0, frames_unpack_bytes(a.Fout, a.E, a.values_len), 0.0
+    if name == 'rvt_frames_unpack_augment':                      # the same bound, plus the table; the windows live in the device table
+        return 0.0, frames_unpack_augment_bytes(a.Fout, a.E, a.values_len, a.B), 0.0
     return None
 
 
@@ -237,6 +239,12 @@ def frames_unpack_bytes(Fout: int, E: int, nnz: int) -> float:
     """HBM bytes of one rvt_frames_unpack that fetches Fout frames holding nnz non-zero bytes between them: their masks, seg_offset
     rows, value_base entries and index entries read, their values read, the dense frames written."""
     return 1.0 * Fout * E + Fout * (_frames_meta_bytes(E) + 8) + nnz
+
+
+def frames_unpack_augment_bytes(Fout: int, E: int, nnz: int, B: int) -> float:
+    """HBM bytes of one rvt_frames_unpack_augment: what frames_unpack_bytes counts (the dense frames written once, the fetched
+    frames' metadata and their nnz value bytes read) plus the int32 [B][8] table.  No dense intermediate is written or read."""
+    return frames_unpack_bytes(Fout, E, nnz) + 32.0 * B
 
 
 def executed(name: str, args) -> Optional[float]:

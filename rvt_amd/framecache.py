@@ -7,6 +7,7 @@ event tensors built once stay small, and a sampler fetches frames by index.
 
   * ``pack_frames(x)``: a uint8 / int8 tensor ``(..., C, H, W)`` -> ``PackedFrames`` (four launches, no host synchronisation).
   * ``unpack_frames(packed, index)``: frames by index -> ``index.shape + (C, H, W)``; ``-1`` is a zero frame.  One launch.
+  * ``unpack_augment(packed, index, planes_table)``: the same followed by ``augment.augment_planes``, in one launch, bit for bit.
   * ``PackedFrames.slice`` / ``concat`` / ``save`` / ``load``: host side, plain numpy / CPU torch, no kernel.  ``load`` validates
     the arrays before anything reaches a kernel.
 
@@ -302,4 +303,36 @@ def unpack_frames(packed: PackedFrames, index: Optional[Tensor] = None, out: Opt
     L.call('rvt_frames_unpack', L.ptr(packed.masks), L.ptr(packed.seg_offset), L.ptr(packed.value_base),
            L.ptr(packed.values) if n else None, n, F, E, None if index is None else L.ptr(index), Fout, L.ptr(out), L.ptr(packed.status),
            L.stream_of(out))
+    return out
+
+
+def unpack_augment(packed: PackedFrames, index: Tensor, planes_table: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """`augment_planes(unpack_frames(packed, index), planes_table)` in one launch, bit for bit, without the dense tensor between
+    the two (rvt_frames_unpack_augment).  index: int64 (T, B) on the device of `packed`, -1 = a zero frame whatever the table says,
+    any other index outside [0, F) a zero frame and the status bit `packed.check()` raises on; planes_table: the int32 [B][8]
+    table of `augment.make_tables` / `write_tables`, sample b = column b of the index.  Returns index.shape + frame_shape of
+    packed.dtype (bytes are moved, never interpreted); with `out` given nothing is allocated."""
+    F, E = _check_set(packed)
+    dev = packed.device
+    if len(packed.frame_shape) != 3:
+        raise ValueError(f'frames must be (C, H, W) planes, the packed set holds {packed.frame_shape}')
+    if planes_table.dtype != torch.int32 or planes_table.dim() != 2 or planes_table.shape[1] != 8:
+        raise ValueError('planes_table must be int32 [B][8]')
+    if planes_table.device != dev or not planes_table.is_contiguous():
+        raise ValueError(f'planes_table must be contiguous on {dev}')
+    B = planes_table.shape[0]
+    if index.dtype != torch.int64 or index.device != dev or not index.is_contiguous():
+        raise ValueError(f'index must be a contiguous int64 tensor on {dev}')
+    if index.dim() != 2 or index.shape[1] != B or index.shape[0] < 1 or B < 1:
+        raise ValueError(f'index must be (T, B={B}) like the rows of planes_table, got {tuple(index.shape)}')
+    C, H, W = packed.frame_shape
+    shape = tuple(index.shape) + (C, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=packed.dtype, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != packed.dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f'out must be contiguous {packed.dtype} {shape} on {dev}')
+    n = packed.values.numel()
+    L.call('rvt_frames_unpack_augment', L.ptr(packed.masks), L.ptr(packed.seg_offset), L.ptr(packed.value_base),
+           L.ptr(packed.values) if n else None, n, F, E, L.ptr(index), index.numel(), L.ptr(planes_table), B, C, H, W, L.ptr(out),
+           L.ptr(packed.status), L.stream_of(out))
     return out
