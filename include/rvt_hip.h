@@ -32,6 +32,7 @@
  *       rvt_augment_planes / rvt_augment_labels        training-time flip / zoom of event planes and box labels
  *       rvt_frames_pack (+ _ws_bytes) / rvt_frames_unpack   byte planes <-> bitmap + non-zero bytes, unpacked by frame index (the compact store)
  *       rvt_frames_unpack_augment                      packed frames by index -> flipped / zoomed planes, unpack + augmentation in one launch
+ *       rvt_frames_gather                              packed frames by address, from device or pinned host stores, into one packed set
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *       rvt_optim_step                                 value clip + AdamW + OneCycle schedule of every parameter, one call per step
@@ -766,7 +767,8 @@ int rvt_augment_labels(const float* rows, const int* count, const float* table, 
  *   seg_offset uint32 [F][Sf + 1]  exclusive prefix sum of the per-segment non-zero counts of the frame; the last entry is the frame's count
  *   value_base int64  [F + 1]      exclusive prefix sum of the frames' counts; value_base[F] is the total, nnz
  *   values     uint8  [capacity]   the non-zero bytes of all frames, frame order then byte order, no padding
- *   status     int32  [1]          bit 0: pack ran out of capacity;  bit 1: unpack met an index outside [-1, F)
+ *   status     int32  [1]          bit 0: pack / gather ran out of capacity;  bit 1: unpack met an index outside [-1, F);
+ *                                  bit 2: gather met a table row whose count is outside [0, E]
  * Packed size: 8 Gf F + 4 (Sf + 1) F + 8 (F + 1) + nnz bytes.
  *
  * rvt_frames_pack: frames [F][E] -> masks, seg_offset, value_base, values, status.  Four launches on the stream (masks + counts,
@@ -792,7 +794,22 @@ int rvt_augment_labels(const float* rows, const int* count, const float* table, 
  *   no allocation, no host synchronisation; replays in a hipGraph after index, table and the packed arrays were rewritten in
  *   place.  Reads of values stay inside [0, values_len) and mask bits behind a frame's end are ignored whatever the arrays hold;
  *   nothing outside out[Fout][E] is written.  16-byte stores when W % 16 == 0 and out is 16-byte aligned, byte accesses otherwise.
- *   Supported: 1 <= W <= 2048, C*H <= 2^24; masks / value_base / index 8-byte, seg_offset / status / table 4-byte aligned. */
+ *   Supported: 1 <= W <= 2048, C*H <= 2^24; masks / value_base / index 8-byte, seg_offset / status / table 4-byte aligned.
+ * rvt_frames_gather: n frames named by address, out of any number of packed sets of one E, into the packed set masks [n][Gf],
+ *   seg_offset [n][Sf + 1], value_base [n + 1], values [capacity] on the device (rvt_amd/csrc/frames_gather.hpp): bit for bit the
+ *   concatenation of the single-frame slices in table order.  table: int64 [n][4] in DEVICE memory, 8-byte aligned, row f =
+ *   {address of the frame's Gf masks (8-byte aligned), address of its Sf + 1 seg_offset entries (4-byte aligned), address of its
+ *   first value byte (any; may be 0 when the count is 0), its count of non-zero bytes}.  The addresses may point into memory of the
+ *   same device or into PINNED host memory (never pageable memory); rows may name any mix of sets in any order and one frame twice.
+ *   value_base is the exclusive prefix sum of the counts, made on the device; values are back to back.  status is WRITTEN: bit 0
+ *   when the total exceeds capacity (value_base is still complete and exactly the value bytes below capacity are written), bit 2
+ *   when a row's count was outside [0, E] (it is taken as 0).  Nothing outside values[0, min(total, capacity)) and the n rows of
+ *   the three other arrays (n + 1 entries of value_base) is written; the first and last bytes of a frame's values leave by byte
+ *   stores (memory beside a run is never read and rewritten) and no byte outside a frame's masks, seg_offset row and count value
+ *   bytes is read.  Two launches on the stream (the prefix sum, then the copy on at most max_blocks workgroups, 0 = the default,
+ *   walked in fixed-size pieces), no workspace, no allocation, no host synchronisation, no workgroup waits for another; replays in
+ *   a hipGraph after the table was rewritten in place.  n = 0 returns 0 and launches nothing.  masks / value_base 8-byte,
+ *   seg_offset / status 4-byte aligned; values at any byte address. */
 size_t rvt_frames_pack_ws_bytes(long long F, long long E);
 int rvt_frames_pack(const void* frames, long long F, long long E, void* masks, void* seg_offset, void* value_base, void* values,
                     long long capacity, void* status, void* ws, size_t ws_bytes, void* stream);
@@ -801,6 +818,8 @@ int rvt_frames_unpack(const void* masks, const void* seg_offset, const void* val
 int rvt_frames_unpack_augment(const void* masks, const void* seg_offset, const void* value_base, const void* values,
                               long long values_len, long long F, long long E, const long long* index, long long Fout,
                               const int* table, int B, int C, int H, int W, void* out, void* status, void* stream);
+int rvt_frames_gather(const long long* table, long long n, long long E, void* masks, void* seg_offset, void* value_base, void* values,
+                      long long capacity, void* status, int max_blocks, void* stream);
 
 /* The optimizer step on the device (rvt_amd/csrc/optim.hpp; host mirror rvt_amd/optim.py): gradient clipping by value, AdamW
  * (decoupled weight decay, no amsgrad) and the OneCycle learning-rate schedule of every parameter of every parameter group in one

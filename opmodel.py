@@ -201,6 +201,8 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, frames_unpack_bytes(a.Fout, a.E, a.values_len), 0.0
     if name == 'rvt_frames_unpack_augment':                      # the same bound, plus the table; the windows live in the device table
         return 0.0, frames_unpack_augment_bytes(a.Fout, a.E, a.values_len, a.B), 0.0
+    if name == 'rvt_frames_gather':                              # the counts live in the device table: every frame full up to `capacity`
+        return 0.0, frames_gather_bytes(a.n, a.E, min(a.capacity, a.n * a.E)), 0.0
     return None
 
 
@@ -245,6 +247,13 @@ def frames_unpack_augment_bytes(Fout: int, E: int, nnz: int, B: int) -> float:
     """HBM bytes of one rvt_frames_unpack_augment: what frames_unpack_bytes counts (the dense frames written once, the fetched
     frames' metadata and their nnz value bytes read) plus the int32 [B][8] table.  No dense intermediate is written or read."""
     return frames_unpack_bytes(Fout, E, nnz) + 32.0 * B
+
+
+def frames_gather_bytes(n: int, E: int, nnz: int) -> float:
+    """Bytes of one rvt_frames_gather that fetches n frames holding nnz non-zero bytes between them: their packed bytes (masks,
+    seg_offset rows, value_base, values: 8 Gf n + 4 (Sf + 1) n + 8 (n + 1) + nnz) read once and written once, plus the int64 [n][4]
+    table.  The reads cross the host link when the stores are pinned host memory; the writes are HBM's."""
+    return 2.0 * (n * _frames_meta_bytes(E) + 8 + nnz) + 32.0 * n
 
 
 def executed(name: str, args) -> Optional[float]:

@@ -1,10 +1,12 @@
 // extern "C" entry points, part 16: the sparse frame cache (framecache.hpp): byte planes packed to bitmap + non-zero bytes on the
-// device and unpacked by frame index, plain or through the training augmentation (frames_augment.hpp).  Integer work: bit-exact.
+// device and unpacked by frame index, plain or through the training augmentation (frames_augment.hpp), and gathered by address
+// out of several packed stores, pinned host memory included (frames_gather.hpp).  Integer work: bit-exact.
 #include <stdint.h>
 
 #include "host.hpp"
 #include "framecache.hpp"
 #include "frames_augment.hpp"
+#include "frames_gather.hpp"
 
 using namespace rvt;
 
@@ -106,6 +108,32 @@ int rvt_frames_unpack_augment(const void* masks, const void* seg_offset, const v
                            (const unsigned char*)values, values_len, F, E, g.Gf, g.Sf, index, table, B, C, H, W, chunks, (unsigned char*)out,
                            (int*)status);
     return check_launch("frames_unpack_augment");
+}
+
+int rvt_frames_gather(const long long* table, long long n, long long E, void* masks, void* seg_offset, void* value_base, void* values,
+                      long long capacity, void* status, int max_blocks, void* stream) {
+    RVT_CHECK(n >= 0 && n <= 0x7fffffffLL && E >= 1 && E < (1LL << 31), "frames_gather: n=%lld frames of E=%lld bytes outside the supported range (n >= 0, 1 <= E < 2^31)", n, E);
+    if (n == 0) return 0;
+    RVT_CHECK(table && masks && seg_offset && value_base && status, "frames_gather: null argument");
+    RVT_CHECK(capacity >= 0 && (values || capacity == 0), "frames_gather: capacity=%lld without a values array", capacity);
+    RVT_CHECK(max_blocks >= 0, "frames_gather: max_blocks=%d is negative (0 = the default)", max_blocks);
+    RVT_CHECK(((uintptr_t)table & 7) == 0 && ((uintptr_t)masks & 7) == 0 && ((uintptr_t)value_base & 7) == 0 &&
+              ((uintptr_t)seg_offset & 3) == 0 && ((uintptr_t)status & 3) == 0,
+              "frames_gather: table / masks / value_base need 8-byte, seg_offset / status 4-byte alignment");
+    const FrameGeom g = frame_geom(E);
+    // pieces of the copy: masks and seg_offset of every frame, and the value bytes the destination has room for
+    const long long MU = (g.Gf * 8 + GA_PIECE - 1) / GA_PIECE, SU = ((g.Sf + 1) * 4 + GA_PIECE - 1) / GA_PIECE;
+    const long long room = capacity < n * E ? capacity : n * E;
+    const long long units = n * (MU + SU) + (room > 0 ? (15 + room + GA_PIECE - 1) / GA_PIECE : 0);
+    long long blocks = (units + FC_WAVES - 1) / FC_WAVES;
+    const long long cap_blocks = max_blocks > 0 ? max_blocks : GA_DEFAULT_BLOCKS;
+    if (blocks > cap_blocks) blocks = cap_blocks;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(frames_gather_scan_kernel, dim3(1), dim3(FC_THREADS), 0, st, table, n, E, capacity, (long long*)value_base,
+                       (int*)status);
+    hipLaunchKernelGGL(frames_gather_copy_kernel, dim3((unsigned)blocks), dim3(FC_THREADS), 0, st, table, n, E, g.Gf, g.Sf,
+                       (unsigned long long*)masks, (unsigned*)seg_offset, (const long long*)value_base, (unsigned char*)values, capacity);
+    return check_launch("frames_gather");
 }
 
 }  // extern "C"

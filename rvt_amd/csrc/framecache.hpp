@@ -7,7 +7,8 @@
 //   seg_offset uint32 [F][Sf + 1] exclusive prefix sum of the segments' non-zero counts of the frame; the last entry is the frame's count
 //   value_base int64  [F + 1]     exclusive prefix sum of the frames' counts; value_base[F] = nnz
 //   values     uint8  [capacity]  the non-zero bytes, frame order then byte order, no padding
-//   status     int32  [1]         bit 0: pack ran out of capacity (written by pack);  bit 1: unpack met an index outside [-1, F) (or-ed in)
+//   status     int32  [1]         bit 0: pack ran out of capacity (written by pack);  bit 1: unpack met an index outside [-1, F) (or-ed in);
+//                                 bit 2: gather met a table row whose count is outside [0, E] (frames_gather.hpp, which writes bits 0 and 2)
 //
 // One wave owns one segment, in every kernel; a workgroup is four such waves that share nothing.  No workgroup waits for another:
 // the launches of a pack follow each other on the stream, which is the only ordering used.

@@ -10,6 +10,8 @@ event tensors built once stay small, and a sampler fetches frames by index.
   * ``unpack_augment(packed, index, planes_table)``: the same followed by ``augment.augment_planes``, in one launch, bit for bit.
   * ``PackedFrames.slice`` / ``concat`` / ``save`` / ``load``: host side, plain numpy / CPU torch, no kernel.  ``load`` validates
     the arrays before anything reaches a kernel.
+  * ``FrameGather(stores, device)`` / ``gather_frames(stores, global_index)``: frames of several packed sets, on the device or in
+    pinned host memory, fetched by the device into one packed set (one call, no packed byte through host code).
 
 Intended flow: ``load`` a recording's packed frames into pinned host memory, ``slice`` and ``concat`` the frames a batch needs,
 one ``to(device)``, then one ``unpack_frames`` with an index laid out ``(T, B)``.
@@ -33,7 +35,8 @@ from . import _lib as L
 VERSION = 1
 GROUP_BYTES = 64
 SEGMENT_BYTES = 64 * GROUP_BYTES
-STATUS_CAPACITY, STATUS_INDEX = 1, 2
+STATUS_CAPACITY, STATUS_INDEX, STATUS_COUNT = 1, 2, 4
+GATHER_COLS = 4                                                  # int64 columns of a gather table row: masks, seg_offset, values, count
 _DTYPES = {'uint8': torch.uint8, 'int8': torch.int8}
 
 
@@ -93,6 +96,8 @@ class PackedFrames:
             raise RuntimeError(f'pack_frames ran out of capacity: {self.nnz()} non-zero bytes, room for {self.values.numel()}')
         if st & STATUS_INDEX:
             raise RuntimeError(f'unpack_frames met an index outside [-1, {self.num_frames})')
+        if st & STATUS_COUNT:
+            raise RuntimeError(f'gather_frames met a table row whose count is outside [0, {self.frame_bytes}] (taken as 0)')
         if st:
             raise RuntimeError(f'unknown frame-cache status {st}')
         return self
@@ -336,3 +341,134 @@ def unpack_augment(packed: PackedFrames, index: Tensor, planes_table: Tensor, ou
            L.ptr(packed.values) if n else None, n, F, E, L.ptr(index), index.numel(), L.ptr(planes_table), B, C, H, W, L.ptr(out),
            L.ptr(packed.status), L.stream_of(out))
     return out
+
+
+# ---- gather: frames by address out of several stores, pinned host memory included ----
+class FrameGather:
+    """The frames of `stores` (PackedFrames of one frame shape and dtype, on `device` or in pinned host memory) under one global
+    frame numbering, store after store, fetched by the device itself (rvt_frames_gather, rvt_amd/csrc/frames_gather.hpp): the
+    host writes one int64 [4] row per frame (`table`), the launch copies masks, seg_offset rows and value bytes straight from
+    where they lie into a packed set on the device and makes its value_base.  Keeps a reference to every source tensor: the
+    kernel reads raw addresses, so the stores must neither be freed nor moved while a launch can still run."""
+
+    def __init__(self, stores: Sequence[PackedFrames], device):
+        stores = list(stores)
+        if not stores:
+            raise ValueError('no packed sets to gather from')
+        self.device = dev = torch.device(device)
+        if dev.type == 'cuda' and dev.index is None:
+            self.device = dev = torch.device('cuda', torch.cuda.current_device())
+        self.frame_shape, self.dtype = tuple(stores[0].frame_shape), stores[0].dtype
+        E = self.frame_bytes = math.prod(self.frame_shape)
+        Gf, Sf = geometry(E)
+        self._keep, rows = [], []
+        for k, s in enumerate(stores):
+            if tuple(s.frame_shape) != self.frame_shape or s.dtype != self.dtype:
+                raise ValueError(f'store {k} holds {s.dtype} frames {tuple(s.frame_shape)}, store 0 {self.dtype} frames {self.frame_shape}')
+            _check_set(s)
+            for name, t in (('masks', s.masks), ('seg_offset', s.seg_offset), ('values', s.values)):
+                if t.device.type == 'cpu':
+                    if dev.type != 'cpu' and t.numel() and not t.is_pinned():      # (an empty array is never read)
+                        raise ValueError(f'store {k}: {name} lies in pageable host memory; the device reads pinned memory only (pin_memory())')
+                elif t.device != dev:
+                    raise ValueError(f'store {k}: {name} is on {t.device}, the gather runs on {dev}')
+            vb = s.value_base.cpu().numpy()
+            if int(vb[-1]) > s.values.numel():
+                raise ValueError(f'store {k}: values hold {s.values.numel()} bytes of {int(vb[-1])}: the pack ran out of capacity')
+            F = s.num_frames
+            f = np.arange(F, dtype=np.int64)
+            r = np.empty((F, GATHER_COLS), dtype=np.int64)
+            r[:, 0] = s.masks.data_ptr() + 8 * Gf * f
+            r[:, 1] = s.seg_offset.data_ptr() + 4 * (Sf + 1) * f
+            r[:, 2] = s.values.data_ptr() + vb[:-1]
+            r[:, 3] = np.diff(vb)
+            rows.append(r)
+            self._keep.append((s.masks, s.seg_offset, s.values))
+        self.base = np.concatenate(([0], np.cumsum([r.shape[0] for r in rows]))).astype(np.int64)      # global number of each store's frame 0
+        self._rows = np.concatenate(rows)
+        self.value_base = np.concatenate(([0], np.cumsum(self._rows[:, 3]))).astype(np.int64)                # of the concatenated stores
+        self.max_count = int(self._rows[:, 3].max()) if len(self._rows) else 0
+
+    @property
+    def num_frames(self) -> int:
+        return int(self.base[-1])
+
+    def table(self, global_index, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """int64 [n][4] rows of the frames `global_index` names, in its (flattened) order; into out[:n] when given."""
+        idx = np.asarray(global_index, dtype=np.int64).reshape(-1)
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= self.num_frames):
+            raise IndexError(f'frame index outside [0, {self.num_frames})')
+        if out is None:
+            return self._rows[idx]
+        return np.take(self._rows, idx, axis=0, out=out[:idx.size])
+
+    def _check_out(self, out: PackedFrames, n: int) -> None:
+        if tuple(out.frame_shape) != self.frame_shape or out.dtype != self.dtype:
+            raise ValueError(f'out holds {out.dtype} frames {tuple(out.frame_shape)}, the stores {self.dtype} frames {self.frame_shape}')
+        _check_set(out)
+        if out.device != self.device:
+            raise ValueError(f'out is on {out.device}, the gather runs on {self.device}')
+        if out.num_frames < n:
+            raise ValueError(f'out has rows for {out.num_frames} frames, {n} are asked for')
+
+    def launch(self, table_dev: Tensor, n: int, out: PackedFrames, max_blocks: int = 0) -> PackedFrames:
+        """The launch alone, on the current stream: table_dev holds the n rows already (or will, by a copy enqueued before on the
+        same stream).  Writes rows [0, n) of out.masks / seg_offset, out.value_base[0 .. n], the value bytes and out.status."""
+        self._check_out(out, n)
+        if table_dev.dtype != torch.int64 or table_dev.device != self.device or not table_dev.is_contiguous() or table_dev.numel() < GATHER_COLS * n:
+            raise ValueError(f'table_dev must be a contiguous int64 tensor of at least {GATHER_COLS * n} entries on {self.device}')
+        cap = out.values.numel()
+        L.call('rvt_frames_gather', L.ptr(table_dev), n, self.frame_bytes, L.ptr(out.masks), L.ptr(out.seg_offset), L.ptr(out.value_base),
+               L.ptr(out.values) if cap else None, cap, L.ptr(out.status), int(max_blocks), L.stream_of(out.masks))
+        return out
+
+    def gather(self, global_index, out: PackedFrames, table_dev: Optional[Tensor] = None, max_blocks: int = 0,
+               rows: Optional[np.ndarray] = None) -> PackedFrames:
+        """Frames `global_index` (any shape, flattened) into rows [0, n) of `out`, on the current stream; returns out.  rows: the
+        int64 [n][4] table itself instead of an index (global_index None).  table_dev: a device int64 buffer the rows are copied to
+        (none given: one is allocated).  Does not synchronise: out.check() says whether out.values had room."""
+        if rows is None:
+            rows = self.table(global_index)
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.ndim != 2 or rows.shape[1] != GATHER_COLS:
+                raise ValueError(f'rows must be int64 [n][{GATHER_COLS}], got {rows.shape}')
+        n = rows.shape[0]
+        self._check_out(out, n)
+        if n == 0:
+            return out
+        host = torch.from_numpy(rows.reshape(-1))
+        if table_dev is None:
+            table_dev = host.to(self.device)
+        else:
+            if table_dev.dtype != torch.int64 or table_dev.device != self.device or table_dev.dim() != 1 or table_dev.numel() < host.numel():
+                raise ValueError(f'table_dev must be a flat int64 tensor of at least {host.numel()} entries on {self.device}')
+            table_dev[:host.numel()].copy_(host)
+        return self.launch(table_dev, n, out, max_blocks)
+
+    def empty(self, n: int, capacity: int) -> PackedFrames:
+        """An uninitialised packed set on the device with rows for n frames and room for `capacity` value bytes."""
+        Gf, Sf = geometry(self.frame_bytes)
+        dev = self.device
+        return PackedFrames(self.frame_shape, self.dtype, torch.empty(n, Gf, dtype=torch.int64, device=dev),
+                            torch.empty(n, Sf + 1, dtype=torch.int32, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev),
+                            torch.empty(capacity, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def gather_frames(stores: Sequence[PackedFrames], global_index, out: Optional[PackedFrames] = None) -> PackedFrames:
+    """One-shot FrameGather: frames `global_index` of the concatenation of `stores` as a packed set on the device of `out`
+    (none given: on the stores' device, the current GPU for host stores, sized exactly)."""
+    stores = list(stores)
+    if out is not None:
+        dev = out.device
+    elif stores and stores[0].device.type == 'cuda':
+        dev = stores[0].device
+    elif L.is_emulator():
+        dev = torch.device('cpu')
+    else:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    g = FrameGather(stores, dev)
+    rows = g.table(global_index)
+    if out is None:
+        out = g.empty(rows.shape[0], int(rows[:, 3].sum()))
+    return g.gather(None, out, rows=rows)

@@ -277,31 +277,45 @@ class _Buffers:
 
 
 class _Staging:
-    """Host residency: a pinned packed set of T * B frames and its device twin, sized for the densest frames of the stores."""
+    """Host residency: a packed set of T * B frames on the device, sized for the densest frames of the stores, and what fills it:
+    staging='copy' a pinned twin of the set, staging='gather' a pinned int64 [T * B][4] table and its device twin."""
 
-    def __init__(self, n_frames, E, frame_shape, dtype, cap, dev, pin):
+    def __init__(self, n_frames, E, frame_shape, dtype, cap, dev, pin, gather=False):
         Gf, Sf = fc.geometry(E)
 
         def host(*shape, dt):
             t = torch.zeros(*shape, dtype=dt)
             return t.pin_memory() if pin else t
-        self.host = PackedFrames(tuple(frame_shape), dtype, host(n_frames, Gf, dt=torch.int64), host(n_frames, Sf + 1, dt=torch.int32),
-                                 host(n_frames + 1, dt=torch.int64), host(max(cap, 1), dt=torch.uint8), torch.zeros(1, dtype=torch.int32))
-        self.dev = self.host._map(lambda t: torch.zeros_like(t, device=dev))
+
+        def packed(make):
+            return PackedFrames(tuple(frame_shape), dtype, make(n_frames, Gf, dt=torch.int64), make(n_frames, Sf + 1, dt=torch.int32),
+                                make(n_frames + 1, dt=torch.int64), make(max(cap, 1), dt=torch.uint8), make(1, dt=torch.int32))
+        self.dev = packed(lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev))
+        self.host = self.table_host = self.table_dev = None
+        if gather:
+            self.table_host = host(n_frames * fc.GATHER_COLS, dt=torch.int64)
+            self.table_rows = self.table_host.numpy().reshape(n_frames, fc.GATHER_COLS)        # the same memory, for numpy to fill
+            self.table_dev = torch.zeros(n_frames * fc.GATHER_COLS, dtype=torch.int64, device=dev)
+        else:
+            self.host = packed(host)
         self.ready = torch.cuda.Event() if dev.type == 'cuda' else None
 
 
 class BatchLoader:
     """Iterable; one iteration is an epoch.  The batch is described in the module docstring, the index rules are the functions above.
     resident: 'device' keeps the concatenated packed stores in device memory, 'host' keeps them pinned on the host and stages the
-    frames of the next batch on a side stream.  fused: None / False = unpack_frames + augment_planes (the measured faster route),
+    frames of the next batch on a side stream: staging='copy' collects them on the host into a pinned set and copies that,
+    staging='gather' writes one table row per frame and lets the device fetch them from the pinned stores (framecache.FrameGather);
+    None = 'gather', the measured faster one; the batches are the same bit for bit.
+    fused: None / False = unpack_frames + augment_planes (the measured faster route),
     True = unpack_augment (one launch, no dense intermediate).  seed: the epoch's random order comes from seed + epoch (the same on
     every rank); the streams' permutations and the augmentation draws use torch's global generator, seeded likewise when given."""
 
     def __init__(self, stores: Sequence[SequenceStore], batch_size: int, sequence_length: int, mode: DatasetSamplingMode,
                  dataset_mode: Mode, augm_config: Any = None, dataset_hw: Optional[Tuple[int, int]] = None, device=None,
                  resident: str = 'device', weighted_sampling: bool = False, only_load_end_labels: bool = False, w_random: float = 1,
-                 w_stream: float = 1, rank: int = 0, world_size: int = 1, seed: Optional[int] = None, fused: Optional[bool] = None):
+                 w_stream: float = 1, rank: int = 0, world_size: int = 1, seed: Optional[int] = None, fused: Optional[bool] = None,
+                 staging: Optional[str] = None):
         self.stores = list(stores)
         if not self.stores:
             raise ValueError('no sequence stores')
@@ -313,6 +327,13 @@ class BatchLoader:
             raise ValueError('MIXED sampling is a training mode')
         if resident not in ('device', 'host'):
             raise ValueError(f"resident must be 'device' or 'host', got {resident!r}")
+        if staging not in (None, 'copy', 'gather'):
+            raise ValueError(f"staging must be None, 'copy' or 'gather', got {staging!r}")
+        if staging is not None and resident != 'host':
+            raise ValueError(f"staging={staging!r} names how host-resident stores reach the device: it needs resident='host'")
+        # the default is the measured one (profiles/frames_gather_bench.txt): at both shapes and all three fills the gather's host
+        # time is lower (1 Mpx, 5 %: 1.7 ms against 55 ms) and its time until the set is ready is not higher (6.7 ms against 55 ms)
+        self.staging = (staging or 'gather') if resident == 'host' else None
         assert world_size > rank >= 0
         self.rank, self.world_size, self.seed, self.epoch = rank, world_size, seed, 0
         self.weighted_sampling, self.only_load_end_labels = weighted_sampling, only_load_end_labels
@@ -385,9 +406,12 @@ class BatchLoader:
                     s.frames = s.frames.pin_memory()
             cap = max(int(np.diff(s.frames.value_base.numpy()).max()) for s in self.stores)
             self.side = torch.cuda.Stream(device=dev) if pin else None
+            gather = self.staging == 'gather'
+            self.gatherer = fc.FrameGather([s.frames for s in self.stores], dev) if gather else None
+            self.gather_blocks = 0                               # 0 = the library's default grid cap
             for p in self.parts.values():
                 n = self.T * p['B']
-                p['staging'] = [_Staging(n, E, self.frame_shape, self.dtype, n * cap, dev, pin) for _ in range(2)]
+                p['staging'] = [_Staging(n, E, self.frame_shape, self.dtype, n * cap, dev, pin, gather) for _ in range(2)]
 
     # ---- orders ----
     def _generator(self) -> Optional[torch.Generator]:
@@ -499,6 +523,30 @@ class BatchLoader:
                 d.copy_(s)
         return st, local
 
+    def _stage_gather(self, p: dict, idx: np.ndarray):
+        """Host residency, staging='gather': one table row per frame the batch names, and one gather launch on the side stream that
+        fetches them from the pinned stores into the device set.  Returns (staging set, local index)."""
+        st = p['staging'][p['flip']]
+        need = np.unique(idx[idx >= 0])
+        local = np.full_like(idx, -1)
+        local[idx >= 0] = np.searchsorted(need, idx[idx >= 0])
+        n = len(need)
+        if st.ready is not None:
+            st.ready.synchronize()                               # the table's previous copy has left the pinned buffer (long done: no wait)
+        if n:
+            self.gatherer.table(need, out=st.table_rows)
+        if self.side is not None:
+            self.side.wait_stream(torch.cuda.current_stream(self.device))        # the set's previous reader is done
+            with torch.cuda.stream(self.side):
+                if n:
+                    st.table_dev[:n * fc.GATHER_COLS].copy_(st.table_host[:n * fc.GATHER_COLS], non_blocking=True)
+                    self.gatherer.launch(st.table_dev, n, st.dev, self.gather_blocks)
+                st.ready.record(self.side)
+        elif n:
+            st.table_dev[:n * fc.GATHER_COLS].copy_(st.table_host[:n * fc.GATHER_COLS])
+            self.gatherer.launch(st.table_dev, n, st.dev, self.gather_blocks)
+        return st, local
+
     def _plan(self, part: DatasetSamplingMode, samples: List[Sample]) -> dict:
         """Steps 1-3 on the host: indices and label rows, the draw, and (host residency) the staging copy."""
         p = self.parts[part]
@@ -507,7 +555,7 @@ class BatchLoader:
         rows, count = A.pack_labels([[s.labels[t] for s in samples] for t in range(self.T)], G=self.G)
         plan = dict(part=part, samples=samples, states=states, rows=rows, count=count, index=idx, packed=None)
         if self.resident == 'host':
-            st, plan['index'] = self._stage(p, idx)
+            st, plan['index'] = (self._stage_gather if self.staging == 'gather' else self._stage)(p, idx)
             plan['packed'] = st
         return plan
 

@@ -1,0 +1,357 @@
+"""rvt_frames_gather (rvt_amd/csrc/frames_gather.hpp, framecache.FrameGather / gather_frames): frames named by address, out of
+several packed stores, into one packed set on the device.  Every comparison is bit for bit.  The yardsticks are not the code
+under test: the numpy restatement of the format (tests/framecache_ref.py) builds the stores, and the host-side `slice` / `concat`
+say what a gather must produce.  Shapes are those of tests/test_framecache.py."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import opmodel
+from rvt_amd import _header, _lib, framecache as fc
+from rvt_amd.framecache import FrameGather, PackedFrames, gather_frames, unpack_frames
+from tests import framecache_ref as ref
+from tests.backends import backend  # noqa: F401
+from tests.test_framecache import SHAPES, _edge_frames, _packed_from
+
+DTYPES = {'uint8': (np.uint8, torch.uint8), 'int8': (np.int8, torch.int8)}
+CANARY = 0x5A
+
+
+@functools.lru_cache(maxsize=None)
+def _frames(E, dtype):
+    """Three recordings' frames as uint8 [F][E]: the edge frames (6), only all-zero frames (3: an empty `values`), sparse ones (7)."""
+    rng = np.random.default_rng(7 * E + 1)
+    sparse = rng.integers(1, 256, size=(7, E), dtype=np.uint8) * (rng.random((7, E)) < 0.03)
+    sparse[0, E // 2] = 200
+    xs = (_edge_frames(E, DTYPES[dtype][0]), np.zeros((3, E), dtype=np.uint8), sparse)
+    for x in xs:
+        x.setflags(write=False)
+    return xs
+
+
+@functools.lru_cache(maxsize=None)
+def _host_stores(E, dtype):
+    """The host packed sets of `_frames` (never written to) and their frames one behind the other."""
+    xs = _frames(E, dtype)
+    stores = tuple(_packed_from(ref.encode(x), SHAPES[E], DTYPES[dtype][1], 'cpu') for x in xs)
+    assert stores[1].values.numel() == 0
+    return stores, np.concatenate(xs)
+
+
+def _want(stores, idx):
+    """concat of the single-frame slices in index order: what the gather must equal."""
+    base = np.concatenate(([0], np.cumsum([s.num_frames for s in stores])))
+    parts = []
+    for i in idx:
+        k = int(np.searchsorted(base, i, side='right')) - 1
+        parts.append(stores[k].slice(int(i - base[k]), int(i - base[k]) + 1))
+    return fc.concat(parts)
+
+
+def _assert_set(got: PackedFrames, want: PackedFrames, n=None):
+    n = want.num_frames if n is None else n
+    nnz = int(want.value_base[-1])
+    assert torch.equal(got.masks[:n].cpu(), want.masks) and torch.equal(got.seg_offset[:n].cpu(), want.seg_offset)
+    assert torch.equal(got.value_base[:n + 1].cpu(), want.value_base)
+    assert torch.equal(got.values[:nnz].cpu(), want.values[:nnz])
+
+
+def _patterns(F_total):
+    rng = np.random.default_rng(3)
+    return {'run': np.arange(10, 14), 'permutation': rng.permutation(F_total), 'twice': np.array([3, 9, 3, 7, 15, 9, 0]),
+            'one': np.array([12]), 'one_empty': np.array([7])}
+
+
+# ---- 1. equality with slice + concat -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('dtype', list(DTYPES))
+@pytest.mark.parametrize('E', list(SHAPES))
+def test_gather_equals_slice_concat(backend, E, dtype):
+    host, x = _host_stores(E, dtype)
+    stores = [s.to(backend) for s in host]
+    g = FrameGather(stores, backend)
+    assert g.num_frames == 16 and g.base.tolist() == [0, 6, 9, 16]
+    for name, idx in _patterns(16).items():
+        want = _want(host, idx)
+        got = gather_frames(stores, idx)
+        assert got.num_frames == len(idx) and got.frame_shape == SHAPES[E] and got.dtype == DTYPES[dtype][1] and got.device == backend
+        got.check()
+        _assert_set(got, want)
+        assert got.values.numel() == want.nnz()
+        y = unpack_frames(got)
+        assert y.dtype == DTYPES[dtype][1], name
+        assert np.array_equal(y.cpu().numpy().view(np.uint8).reshape(len(idx), E), x[idx]), name
+        # the same through a kept FrameGather, a preallocated set with spare rows and a table buffer of its own
+        out = g.empty(len(idx) + 2, want.nnz() + 5)
+        tab = torch.zeros(4 * (len(idx) + 1), dtype=torch.int64, device=backend)
+        assert g.gather(idx.reshape(1, -1), out, table_dev=tab, max_blocks=1) is out
+        out.check()
+        _assert_set(out, want)
+        assert np.array_equal(tab[:4 * len(idx)].cpu().numpy().reshape(-1, 4), g.table(idx))
+
+
+# ---- 2. every relative alignment of a frame's source and destination value offsets --------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _alignment_case():
+    """A store whose frames hold the counts at which the line logic can go wrong, and an order of rows that names it 16 times with
+    one byte of shift per round: (frames, host store, index)."""
+    E = 4097
+    counts = [0, 1, 15, 16, 17, 31, 33, 4097] + [1] * 15 + [2, 3, 5]       # the fillers walk the source offset through every residue
+    assert sum(counts) % 2 == 1                        # an odd total: 16 rounds shift the destination through every residue
+    rng = np.random.default_rng(12)
+    x = np.zeros((len(counts), E), dtype=np.uint8)
+    for f, c in enumerate(counts):
+        x[f, rng.choice(E, size=c, replace=False)] = rng.integers(1, 256, size=c)
+    x.setflags(write=False)
+    store = _packed_from(ref.encode(x), SHAPES[E], torch.uint8, 'cpu')
+    return x, store, np.tile(np.arange(len(counts)), 16)
+
+
+def test_alignment_sweep(backend):
+    x, host, idx = _alignment_case()
+    store = host.to(backend)
+    want = _want([host], idx)
+    out = FrameGather([store], backend).empty(len(idx), want.nnz())
+    got = gather_frames([store], idx, out=out)
+    got.check()
+    src_vb, dst_vb, cnt = host.value_base.numpy(), want.value_base.numpy(), np.diff(host.value_base.numpy())
+    pairs = {(int((store.values.data_ptr() + src_vb[i]) % 16), int((out.values.data_ptr() + dst_vb[r]) % 16))
+             for r, i in enumerate(idx) if cnt[i] > 0}
+    assert len(pairs) == 256, sorted(set((a, b) for a in range(16) for b in range(16)) - pairs)
+    assert {int(cnt[i]) for i in idx} >= {0, 1, 15, 16, 17, 31, 33, 4097}
+    _assert_set(got, want)
+    assert np.array_equal(unpack_frames(got).cpu().numpy().reshape(len(idx), -1), x[idx])
+
+
+# ---- 3. capacity, bad counts and the write discipline -------------------------------------------------------------------------------
+def _guarded(n, E, cap, dev, aligned):
+    """A packed set of n frames whose four arrays (and status) are views into canary-filled buffers, at 16-byte aligned addresses or
+    at the least alignment each array admits (values: odd).  Returns (set, check) where check() asserts the canaries."""
+    Gf, Sf = fc.geometry(E)
+    lead8, lead4, lead1 = (2, 4, 16) if aligned else (1, 1, 3)
+    fill64 = int.from_bytes(bytes([CANARY] * 8), 'little', signed=True)
+    fill32 = int.from_bytes(bytes([CANARY] * 4), 'little', signed=True)
+    bm = torch.full((n * Gf + 8,), fill64, dtype=torch.int64, device=dev)
+    bs = torch.full((n * (Sf + 1) + 16,), fill32, dtype=torch.int32, device=dev)
+    bb = torch.full((n + 1 + 8,), fill64, dtype=torch.int64, device=dev)
+    bv = torch.full((cap + 64,), CANARY, dtype=torch.uint8, device=dev)
+    bt = torch.full((3,), fill32, dtype=torch.int32, device=dev)
+    for t, lead, size in ((bm, lead8, 8), (bs, lead4, 4), (bb, lead8, 8), (bv, lead1, 1)):
+        assert (t.data_ptr() + lead * size) % 16 == (0 if aligned else (lead * size) % 16)
+    out = PackedFrames(SHAPES[E], torch.uint8, bm[lead8:lead8 + n * Gf].view(n, Gf), bs[lead4:lead4 + n * (Sf + 1)].view(n, Sf + 1),
+                       bb[lead8:lead8 + n + 1], bv[lead1:lead1 + cap], bt[1:2])
+
+    def check(written=cap):
+        """The canaries around the arrays, and behind the `written` first value bytes."""
+        assert (bm[:lead8] == fill64).all() and (bm[lead8 + n * Gf:] == fill64).all(), 'masks'
+        assert (bs[:lead4] == fill32).all() and (bs[lead4 + n * (Sf + 1):] == fill32).all(), 'seg_offset'
+        assert (bb[:lead8] == fill64).all() and (bb[lead8 + n + 1:] == fill64).all(), 'value_base'
+        assert (bv[:lead1] == CANARY).all() and (bv[lead1 + written:] == CANARY).all(), 'values'
+        assert int(bt[0]) == fill32 and int(bt[2]) == fill32, 'status'
+    return out, check
+
+
+@pytest.mark.parametrize('aligned', [True, False], ids=['aligned16', 'odd'])
+def test_capacity_and_canaries(backend, aligned):
+    E = 4097
+    host, _ = _host_stores(E, 'uint8')
+    stores = [s.to(backend) for s in host]
+    idx = _patterns(16)['permutation']
+    want = _want(host, idx)
+    total = want.nnz()
+    g = FrameGather(stores, backend)
+    # one byte short: bit 0, value_base complete, exactly the bytes below capacity written
+    out, canaries = _guarded(len(idx), E, total - 1, backend, aligned)
+    g.gather(idx, out)
+    assert int(out.status[0]) == fc.STATUS_CAPACITY
+    with pytest.raises(RuntimeError, match='capacity'):
+        out.check()
+    assert out.nnz() == total
+    assert torch.equal(out.masks.cpu(), want.masks) and torch.equal(out.seg_offset.cpu(), want.seg_offset)
+    assert torch.equal(out.value_base.cpu(), want.value_base)
+    assert torch.equal(out.values.cpu(), want.values[:total - 1])
+    canaries()
+    # room for all: clean
+    out, canaries = _guarded(len(idx), E, total, backend, aligned)
+    g.gather(idx, out)
+    out.check()
+    _assert_set(out, want)
+    canaries()
+    # no room at all: the three other arrays are still complete
+    out, canaries = _guarded(len(idx), E, 0, backend, aligned)
+    g.gather(idx, out)
+    assert int(out.status[0]) == fc.STATUS_CAPACITY and out.nnz() == total and torch.equal(out.masks.cpu(), want.masks)
+    canaries()
+
+
+@pytest.mark.parametrize('bad', ['minus1', 'E_plus_1'])
+def test_bad_count_is_taken_as_zero(backend, bad):
+    E = 4097
+    host, _ = _host_stores(E, 'uint8')
+    stores = [s.to(backend) for s in host]
+    idx = np.array([9, 0, 12, 2, 15])
+    g = FrameGather(stores, backend)
+    rows = g.table(idx)
+    assert rows.shape == (5, 4) and rows.dtype == np.int64 and rows[1, 3] == E        # frame 0 is dense
+    rows[1, 3] = -1 if bad == 'minus1' else E + 1
+    want = _want(host, idx)
+    counts = np.diff(want.value_base.numpy())
+    keep = np.ones(want.nnz(), dtype=bool)
+    keep[int(want.value_base[1]):int(want.value_base[2])] = False
+    counts[1] = 0
+    out, canaries = _guarded(len(idx), E, int(counts.sum()) + 7, backend, False)
+    g.gather(None, out, rows=rows)
+    assert int(out.status[0]) == fc.STATUS_COUNT
+    with pytest.raises(RuntimeError, match='count is outside'):
+        out.check()
+    assert torch.equal(out.masks.cpu(), want.masks) and torch.equal(out.seg_offset.cpu(), want.seg_offset)
+    assert np.array_equal(out.value_base.cpu().numpy(), np.concatenate(([0], np.cumsum(counts))))
+    assert np.array_equal(out.values[:int(counts.sum())].cpu().numpy(), want.values.numpy()[keep])
+    canaries(written=int(counts.sum()))
+
+
+def test_no_frames_touch_nothing(backend):
+    E = 4097
+    host, _ = _host_stores(E, 'uint8')
+    g = FrameGather([s.to(backend) for s in host], backend)
+    out, canaries = _guarded(2, E, 9, backend, True)
+    before = [t.clone() for t in (out.masks, out.seg_offset, out.value_base, out.values, out.status)]
+    assert g.gather(np.zeros(0, dtype=np.int64), out) is out                           # the host returns before the library
+    assert g.launch(torch.zeros(4, dtype=torch.int64, device=backend), 0, out) is out   # the library returns 0 without a launch
+    assert all(torch.equal(a, b) for a, b in zip(before, (out.masks, out.seg_offset, out.value_base, out.values, out.status)))
+    canaries()
+
+
+# ---- 4. the feature's real path: pinned host stores, a device destination (GPU only) -------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize('E', [4097, 3840])
+def test_pinned_sources(E):
+    _lib._install_test_library(None)
+    dev = torch.device('cuda', 0)
+    host, x = _host_stores(E, 'uint8')
+    stores = [s.pin_memory() for s in host]
+    assert all(s.masks.is_pinned() and s.seg_offset.is_pinned() for s in stores)
+    g = FrameGather(stores, dev)
+    for idx in _patterns(16).values():
+        want = _want(host, idx)
+        out = g.gather(idx, g.empty(len(idx), want.nnz()))
+        out.check()
+        _assert_set(out, want)
+        assert np.array_equal(unpack_frames(out).cpu().numpy().reshape(len(idx), E), x[idx])
+    mixed = [stores[0], host[1].to(dev), stores[2]]                                     # device and pinned stores in one table
+    idx = _patterns(16)['permutation']
+    _assert_set(gather_frames(mixed, idx).check(), _want(host, idx))
+
+
+@pytest.mark.gpu
+def test_graph_replay_follows_the_table():
+    _lib._install_test_library(None)
+    dev = torch.device('cuda', 0)
+    E = 8257
+    host, x = _host_stores(E, 'uint8')
+    g = FrameGather([s.pin_memory() for s in host], dev)
+    n = 6
+    orders = [np.array([0, 9, 10, 3, 6, 15]), np.array([12, 7, 2, 2, 14, 5]), np.array([8, 4, 13, 11, 1, 0])]
+    out = g.empty(n, n * E)
+    table = torch.zeros(4 * n, dtype=torch.int64, device=dev)
+    index = torch.tensor([[5, 0, -1], [2, 2, 4]], device=dev)
+    dense = torch.empty(tuple(index.shape) + SHAPES[E], dtype=torch.uint8, device=dev)
+    table.copy_(torch.from_numpy(g.table(orders[0]).reshape(-1)))
+    g.launch(table, n, out)                                                           # eager warm-up
+    unpack_frames(out, index, out=dense)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        g.launch(table, n, out)
+        unpack_frames(out, index, out=dense)
+    for order in orders[1:]:
+        table.copy_(torch.from_numpy(g.table(order).reshape(-1)))                     # other frames of other stores, the same addresses
+        for t in (out.masks, out.seg_offset, out.value_base):
+            t.fill_(-1)
+        out.values.fill_(0)
+        dense.fill_(0xA5)
+        graph.replay()
+        torch.cuda.synchronize()
+        out.check()
+        _assert_set(out, _want(host, order))
+        want = np.zeros((index.numel(), E), dtype=np.uint8)
+        for j, i in enumerate(index.reshape(-1).tolist()):
+            if i >= 0:
+                want[j] = x[order[i]]
+        assert np.array_equal(dense.cpu().numpy().reshape(-1, E), want)
+
+
+# ---- 5. guards: raised before any launch -----------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_pageable_source_never_reaches_the_kernel():
+    host, _ = _host_stores(4097, 'uint8')
+    assert not host[0].masks.is_pinned()
+    calls, orig = [], _lib.call
+    _lib.call = lambda *a: calls.append(a)
+    try:
+        with pytest.raises(ValueError, match='pageable'):
+            FrameGather(host, torch.device('cuda', 0))
+        with pytest.raises(ValueError, match='pageable'):
+            gather_frames([host[0].pin_memory(), host[2]], [0], out=FrameGather([host[1].to('cuda:0')], 'cuda:0').empty(1, 1))
+    finally:
+        _lib.call = orig
+    assert calls == []
+
+
+def test_guards():
+    host, _ = _host_stores(4097, 'uint8')
+    g = FrameGather(host, 'cpu')
+    for bad in ([16], [-1], [0, 3, 99]):
+        with pytest.raises(IndexError, match='outside'):
+            g.table(bad)
+    assert g.table([]).shape == (0, 4)
+    other, _ = _host_stores(4096, 'uint8')
+    with pytest.raises(ValueError, match='frames'):
+        FrameGather([host[0], other[0]], 'cpu')
+    signed, _ = _host_stores(4097, 'int8')
+    with pytest.raises(ValueError, match='int8'):
+        FrameGather([host[0], signed[0]], 'cpu')
+    with pytest.raises(ValueError, match='no packed sets'):
+        FrameGather([], 'cpu')
+    with pytest.raises(ValueError, match='rows for 2 frames, 3 are asked for'):
+        g.gather([0, 1, 2], g.empty(2, 100))
+    with pytest.raises(ValueError, match='out holds'):
+        g.gather([0], FrameGather(other, 'cpu').empty(1, 100))
+    with pytest.raises(ValueError, match=r'rows must be int64 \[n\]\[4\]'):
+        g.gather(None, g.empty(2, 100), rows=np.zeros((2, 3), dtype=np.int64))
+    # the table is numpy only: rows of a large index come from one fancy index of precomputed rows
+    rows = g.table(np.arange(16))
+    assert np.array_equal(rows[:, 3], np.concatenate([np.diff(s.value_base.numpy()) for s in host]))
+    assert np.array_equal(g.value_base, np.concatenate(([0], np.cumsum(rows[:, 3]))))
+    Gf, Sf = fc.geometry(4097)
+    assert rows[7, 0] == host[1].masks.data_ptr() + 8 * Gf and rows[10, 1] == host[2].seg_offset.data_ptr() + 4 * (Sf + 1)
+    assert rows[11, 2] == host[2].values.data_ptr() + int(host[2].value_base[2])
+
+
+# ---- 6. pricing ----------------------------------------------------------------------------------------------------------------------------
+def test_opmodel_prices_a_recorded_gather(backend):
+    E = 8257
+    host, _ = _host_stores(E, 'uint8')
+    stores = [s.to(backend) for s in host]
+    idx = _patterns(16)['twice']
+    calls, orig = [], _lib.call
+
+    def rec(name, *args):
+        calls.append((name, args))
+        return orig(name, *args)
+    _lib.call = rec
+    try:
+        got = gather_frames(stores, idx)                  # sized exactly: capacity = nnz, which the model reads as the bound
+    finally:
+        _lib.call = orig
+    (name, args), = calls
+    assert name == 'rvt_frames_gather'
+    assert _header.PROTOS[name].argnames == ('table', 'n', 'E', 'masks', 'seg_offset', 'value_base', 'values', 'capacity', 'status',
+                                             'max_blocks', 'stream')
+    n, nnz = len(idx), got.check().nnz()
+    Gf, Sf = fc.geometry(E)
+    assert opmodel.frames_gather_bytes(n, E, nnz) == 2.0 * fc.packed_nbytes(n, E, nnz) + 32.0 * n
+    assert fc.packed_nbytes(n, E, nnz) == n * (8 * Gf + 4 * (Sf + 1)) + 8 * (n + 1) + nnz == ref.nbytes(n, E, nnz)
+    assert opmodel.model(name, args) == (0.0, opmodel.frames_gather_bytes(n, E, nnz))
+    assert opmodel.executed(name, args) == 0.0
