@@ -4,7 +4,9 @@
  * operator boundary a maintainer would bind.  Each one replaces the ATen op sequence of the
  * cited reference lines.  This header is the ONLY statement of the boundary: the prototypes, the host-side records and
  * the rows of every device table (RvtPackDesc, RvtLayerScaleDesc, RvtOptimChunk, RvtOptimGroup, RvtEventStream) with the
- * enumerators a host needs to fill them are declared here; rvt_amd/_header.py derives the ctypes binding and the numpy
+ * enumerators a host needs to fill them are declared here, and so are the records the DEVICE writes and a host only reads back
+ * (RvtGradStat, RvtGradStatHead: typedef'd WITHOUT a struct tag, which is how the reader tells the two directions apart);
+ * rvt_amd/_header.py derives the ctypes binding and the numpy
  * row layouts from this text, and nothing restates a layout or an argument position elsewhere.  Plain pointers and sizes only:
  *   - every pointer is a DEVICE pointer unless stated otherwise;
  *   - `dtype` selects the storage / MFMA input type of activations and weights:
@@ -36,6 +38,7 @@
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *       rvt_optim_step                                 value clip + AdamW + OneCycle schedule of every parameter, one call per step
+ *       rvt_grad_stats (+ _ws_bytes) / rvt_optim_step_guarded   per-tensor gradient statistics + a non-finite verdict into a device ring; the step that obeys it
  *   Operator level — every other entry below: one launch each, what the stage driver sequences and what the Python mirror
  *       (rvt_amd/stage.py, the training backward) calls directly.  Stable and tested one by one (tests/test_kernels.py), but a host
  *       that only runs the model needs none of them; the `*_supported` / `*_ws_*` queries say which fused forms exist for a shape.
@@ -857,6 +860,48 @@ typedef struct RvtOptimGroup {
 } RvtOptimGroup;
 int rvt_optim_step(const RvtOptimChunk* chunks, int n_chunks, const RvtOptimGroup* groups, int n_groups, long long* step, int max_blocks,
                    void* stream);
+
+/* Gradient statistics and the non-finite guard on the device (rvt_amd/csrc/gradstats.hpp; host mirror rvt_amd/optim.py: GradMonitor;
+ * reference callbacks/gradflow.py `GradFlowLogCallback` and the GradScaler step-skip of `precision: 16`).  rvt_grad_stats reduces the
+ * fp32 gradient and parameter pieces of the optimizer's own chunk table: two launches, no host synchronisation, no allocation,
+ * no floating-point atomics; the result is bit-reproducible and does not depend on max_blocks.
+ *   Partial pass: workgroups stride over the chunks (max_blocks as in rvt_optim_step).  A chunk whose g and p are 16-byte aligned
+ *     moves in 16-byte loads, any other element by element.  An element is NON-FINITE when (bits & 0x7f800000) == 0x7f800000.  Over
+ *     the finite gradient elements, in double: sum |g|, sum g^2; in float: max |g|; int32 count of the non-finite ones.  sum p^2 in
+ *     double runs over the finite PARAMETER elements (a parameter's norm does not depend on its gradient).  One RvtGradStat per
+ *     chunk into ws (rvt_grad_stats_ws_bytes(n_chunks) bytes, 8-byte aligned, the caller's).
+ *   Fold pass: one workgroup.  tensor_first: int32 [n_tensors + 1] on the device, tensor t owns the chunks tensor_first[t] ..
+ *     tensor_first[t + 1] - 1 (consecutive in the table; an empty range gives a row of zeros with nonfinite = -1).  The rows of the
+ *     tensors go to stats[slot * stat_stride + t], the totals to heads[slot], slot = *step % ring with *step the optimizer's device
+ *     counter READ ON THE DEVICE (the call does not change it): a replayed graph fills slot after slot by itself.
+ *   scalars: HOST array of n_scalars <= RVT_GRADSTAT_MAX_SCALARS device pointers to fp32 values (loss terms, ...), read by the call;
+ *     the values they point to are read by the launch and copied into the slot's head.  NULL with n_scalars = 0.
+ *   verdict: long long [2] on the device.  verdict[0] = the non-finite total of the latest observation (written here);
+ *     verdict[1] = steps skipped so far (written by rvt_optim_step_guarded only).
+ * rvt_optim_step_guarded is rvt_optim_step, bit for bit, when verdict[0] == 0.  Otherwise no p, m or v is written, *step stays, and
+ * the trailing one-thread launch adds 1 to verdict[1]: a skipped step advances neither the bias correction nor the schedule. */
+enum { RVT_GRADSTAT_MAX_SCALARS = 8 };
+typedef struct {
+    double abs_sum;           /* sum |g| over the finite gradient elements */
+    double sq_sum;            /* sum g^2 over the finite gradient elements */
+    double param_sq_sum;      /* sum p^2 over the finite parameter elements */
+    float abs_max;            /* max |g| over the finite gradient elements, 0 when there is none */
+    int nonfinite;            /* inf / NaN gradient elements; -1: the tensor had no chunk in this observation */
+} RvtGradStat;
+typedef struct {
+    long long step;           /* *step at the observation = optimizer steps done before it */
+    long long nonfinite;      /* total over the tensors */
+    double sq_sum;            /* total over the tensors, in tensor order */
+    float abs_max;            /* over the tensors */
+    int n_scalars;
+    float scalars[8];         /* RVT_GRADSTAT_MAX_SCALARS; the entries from n_scalars on are 0 */
+} RvtGradStatHead;
+size_t rvt_grad_stats_ws_bytes(int n_chunks);
+int rvt_grad_stats(const RvtOptimChunk* chunks, int n_chunks, const int* tensor_first, int n_tensors, const long long* step,
+                   const float* const* scalars, int n_scalars, RvtGradStat* stats, int stat_stride, RvtGradStatHead* heads, int ring,
+                   long long* verdict, void* ws, size_t ws_bytes, int max_blocks, void* stream);
+int rvt_optim_step_guarded(const RvtOptimChunk* chunks, int n_chunks, const RvtOptimGroup* groups, int n_groups, long long* step,
+                           long long* verdict, int max_blocks, void* stream);
 
 /* Prophesee / COCO mAP evaluation of detections on the device (rvt_amd/csrc/cocoeval.hpp; host mirror rvt_amd/evaluation.py).
  * Replaces utils/evaluation/prophesee/ (filter_boxes, evaluate_list, coco_eval.py) and the COCOeval core it calls (evaluateImg,

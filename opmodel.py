@@ -20,10 +20,11 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
-from rvt_amd._header import LaunchArgs
+from rvt_amd._header import ENUMS, LaunchArgs
 
 HBM_PEAK_GBS = 8000.0                             # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6.3 TB/s achievable
 PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3}      # dense MFMA peaks at 2.4 GHz
+_OPTIM_CHUNK = ENUMS['RVT_OPTIM_CHUNK_ELEMS']
 
 
 def _elt(dtype_code: int) -> int:
@@ -203,6 +204,12 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, frames_unpack_augment_bytes(a.Fout, a.E, a.values_len, a.B), 0.0
     if name == 'rvt_frames_gather':                              # the counts live in the device table: every frame full up to `capacity`
         return 0.0, frames_gather_bytes(a.n, a.E, min(a.capacity, a.n * a.E)), 0.0
+    # the optimizer's chunk table: no element count among the arguments, so a launch is priced at what its table admits (every chunk
+    # full).  grad_stats_bytes / optim_step_bytes take the real element count.
+    if name == 'rvt_grad_stats':
+        return 0.0, grad_stats_bytes(a.n_chunks * _OPTIM_CHUNK, a.n_chunks, a.n_tensors), 0.0
+    if name == 'rvt_optim_step_guarded':                         # the step it is when the verdict is clean; a skipped one reads 8 bytes per workgroup
+        return 0.0, optim_step_bytes(a.n_chunks * _OPTIM_CHUNK, a.n_chunks), 0.0
     return None
 
 
@@ -254,6 +261,19 @@ def frames_gather_bytes(n: int, E: int, nnz: int) -> float:
     seg_offset rows, value_base, values: 8 Gf n + 4 (Sf + 1) n + 8 (n + 1) + nnz) read once and written once, plus the int64 [n][4]
     table.  The reads cross the host link when the stores are pinned host memory; the writes are HBM's."""
     return 2.0 * (n * _frames_meta_bytes(E) + 8 + nnz) + 32.0 * n
+
+
+def grad_stats_bytes(n_elems: int, n_chunks: int, n_tensors: int) -> float:
+    """HBM bytes of one rvt_grad_stats over n_elems fp32 elements in n_chunks chunks of n_tensors tensors: gradient and parameter read
+    once (8 bytes per element), the chunk table read (40 per row), one 32-byte partial row per chunk written and read back, one
+    32-byte row per tensor, the 64-byte head and the verdict written.  (tensor_first, the scalars and the step count: not counted.)"""
+    return 8.0 * n_elems + 40.0 * n_chunks + 2 * 32.0 * n_chunks + 32.0 * n_tensors + 64 + 8
+
+
+def optim_step_bytes(n_elems: int, n_chunks: int) -> float:
+    """HBM bytes of one rvt_optim_step / rvt_optim_step_guarded that steps: 16 bytes read and 12 written per element (csrc/optim.hpp)
+    plus the chunk table."""
+    return 28.0 * n_elems + 40.0 * n_chunks
 
 
 def executed(name: str, args) -> Optional[float]:

@@ -1,5 +1,5 @@
 """Reader of include/rvt_hip.h: the header is the single source of the ctypes binding (prototypes, structs, the rows of the device
-tables and the enumerators).
+tables, the records the device writes back and the enumerators).
 
 A plain regex reader of that header's dialect, not a C parser, and loud: a type it does not know, or text left over after the
 typedef'd structs, the enums and the prototypes are taken out, raises.  The header is read once, when this module is imported."""
@@ -15,7 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__fil
 _SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'size_t': ctypes.c_size_t, 'long long': ctypes.c_longlong}
 _POINTEES = set(_SCALARS) | {'void', 'char', 'unsigned char', 'signed char'}       # what a `T*` may point to besides a struct
-_STRUCT = re.compile(r'typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;')
+_STRUCT = re.compile(r'typedef\s+struct\s*(\w*)\s*\{([^{}]*)\}\s*(\w+)\s*;')     # no tag: a record the device writes (RECORDS)
 _ENUM = re.compile(r'\benum\s*\{([^{}]*)\}\s*;')
 _ENUMERATOR = re.compile(r'([A-Za-z_]\w*)(?:\s*=\s*(-?\d+))?')
 _ARRAY = re.compile(r'\[\s*(\d+)\s*\]\s*\Z')
@@ -76,8 +76,9 @@ def parse(text: str) -> Tuple[Dict[str, type], Dict[str, Proto], Dict[str, int]]
     text = re.sub(r'\bconst\b', ' ', text)
     structs: Dict[str, type] = {}
     for name, body, alias in _STRUCT.findall(text):
-        if name != alias:
+        if name and name != alias:
             raise RuntimeError(f'rvt_hip.h reader: struct {name} is typedef\'d as {alias}')
+        tagged, name = bool(name), alias
         fields = []
         for stmt in filter(str.strip, body.split(';')):
             first, *more = stmt.split(',')               # `int a, b` / `const float *w, *b`: one field per name
@@ -86,7 +87,8 @@ def parse(text: str) -> Tuple[Dict[str, type], Dict[str, Proto], Dict[str, int]]
                 _, stars, field, count = _decl(piece)
                 ty = _ctype(base, stars, structs, f'struct {name}', in_struct=True)
                 fields.append((field, ty if count is None else ty * count))
-        structs[name] = type(name, (ctypes.Structure,), {'_fields_': fields, '__doc__': f'`struct {name}` of include/rvt_hip.h'})
+        structs[name] = type(name, (ctypes.Structure,), {'_fields_': fields, '_tagged_': tagged,
+                                                         '__doc__': f'`struct {name}` of include/rvt_hip.h'})
     enums = _enums(text)
     text = _SCAFFOLD.sub(' ', _ENUM.sub(' ', _STRUCT.sub(' ', text)))
     protos: Dict[str, Proto] = {}
@@ -148,5 +150,9 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     return lib
 
 
-STRUCTS, PROTOS, ENUMS = _read()
+_ALL_STRUCTS, PROTOS, ENUMS = _read()
+# what a host FILLS (host-side records, rows of the device tables: `typedef struct X {...} X;`) and what the device writes and a host
+# only reads back (`typedef struct {...} X;`, no tag): the header's two directions
+STRUCTS = {n: s for n, s in _ALL_STRUCTS.items() if s._tagged_}
+RECORDS = {n: s for n, s in _ALL_STRUCTS.items() if not s._tagged_}
 SIGS = {name: p.argtypes for name, p in PROTOS.items()}      # name -> ctypes types of the arguments, every prototype

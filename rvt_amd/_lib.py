@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._header import ENUMS, SIGS as _SIGS, STRUCTS as _STRUCTS, bind as _bind     # enumerators; name -> argument types; structs; types onto a loaded library
+from ._header import ENUMS, RECORDS as _RECORDS, SIGS as _SIGS, STRUCTS as _STRUCTS, bind as _bind     # enumerators; name -> argument types; structs; types onto a loaded library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RVT_HIP_LIB') or os.path.join(_HERE, 'librvt_hip.so')   # env: another BUILD of the same library
@@ -135,8 +135,8 @@ def workspace(kind: str, like: torch.Tensor, n: int, dtype: torch.dtype, floor: 
 
 
 def row_dtype(struct: str) -> np.dtype:
-    """numpy dtype of one of the header's table rows: the C struct's field names, offsets and size."""
-    return np.dtype(_STRUCTS[struct])
+    """numpy dtype of one of the header's table rows or device-written records: the C struct's field names, offsets and size."""
+    return np.dtype(_STRUCTS[struct] if struct in _STRUCTS else _RECORDS[struct])
 
 
 class DeviceTable:

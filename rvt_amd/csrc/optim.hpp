@@ -90,10 +90,14 @@ __device__ __forceinline__ void optim_update4(const OptimScalars& s, f32x4& p, c
     }
 }
 
-__global__ void __launch_bounds__(OPTIM_THREADS)
-optim_step_kernel(const OptimChunk* __restrict__ chunks, int n_chunks, const OptimGroup* __restrict__ groups, int n_groups,
-                  const long long* __restrict__ step) {
+// The step of every chunk this workgroup owns.  GUARDED (rvt_optim_step_guarded): every workgroup reads verdict[0], the non-finite
+// total of the latest rvt_grad_stats, first and touches nothing when it is not zero; with a zero verdict the two instantiations run
+// the same instructions on the same values.
+template <bool GUARDED>
+__device__ __forceinline__ void optim_step_body(const OptimChunk* __restrict__ chunks, int n_chunks, const OptimGroup* __restrict__ groups,
+                                                int n_groups, const long long* __restrict__ step, const long long* __restrict__ verdict) {
     constexpr int T = OPTIM_THREADS, NV = OPTIM_CHUNK / (4 * OPTIM_THREADS);
+    if (GUARDED && verdict[0] != 0) return;
     const int tid = threadIdx.x;
     const long long k = *step + 1;
     int cur = -1;
@@ -147,6 +151,18 @@ optim_step_kernel(const OptimChunk* __restrict__ chunks, int n_chunks, const Opt
             ch.p[i] = p; ch.m[i] = m; ch.v[i] = v;
         }
     }
+}
+
+__global__ void __launch_bounds__(OPTIM_THREADS)
+optim_step_kernel(const OptimChunk* __restrict__ chunks, int n_chunks, const OptimGroup* __restrict__ groups, int n_groups,
+                  const long long* __restrict__ step) {
+    optim_step_body<false>(chunks, n_chunks, groups, n_groups, step, nullptr);
+}
+
+__global__ void __launch_bounds__(OPTIM_THREADS)
+optim_step_guarded_kernel(const OptimChunk* __restrict__ chunks, int n_chunks, const OptimGroup* __restrict__ groups, int n_groups,
+                          const long long* __restrict__ step, const long long* __restrict__ verdict) {
+    optim_step_body<true>(chunks, n_chunks, groups, n_groups, step, verdict);
 }
 
 // stream-ordered behind optim_step_kernel: the one writer of the step count

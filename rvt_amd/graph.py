@@ -47,10 +47,15 @@ class GraphedStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             fn()
+        # the graph addresses the weight caches the warm-up built (descriptor tables, packed weights, gradient buckets) by raw
+        # pointer: they live as long as the graph does.  __call__ drops the MODELS' references after every replay; without these the
+        # buffers went back to the allocator and the next tensor allocated between two replays landed on a table the graph reads.
+        self._held = [getattr(m, '_mw_cache', None) for m in self.models]
 
     def close(self) -> None:
         """Drop the graph and give the models their gradient hand-off mode back (eager use after a captured phase)."""
         self.graph = None
+        self._held = []
         for m, f in zip(self.models, self._saved_flags):
             m.zero_copy_grads = f
             for p in m.parameters():

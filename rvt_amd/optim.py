@@ -12,6 +12,10 @@ Mirror of the reference's optimisation contract (modules/detection.py:360-392 `c
     final_div_factor (final lr = max lr / final_div_factor), converted to torch's the way detection.py:374 does.
     A group's `lr` is the schedule's maximum, as in the reference (`max_lr=lr`).
   * `from_train_config(params, training_cfg)`: the optimizer the reference's `training` config section describes.
+  * `AdamW.attach_monitor(named_parameters, ring, skip_nonfinite) -> GradMonitor` (opt-in; csrc/gradstats.hpp, rvt_grad_stats):
+    per-tensor gradient statistics into a device ring (the reference's GradFlowLogCallback without a host round trip) and a
+    non-finite verdict that `step()` then obeys on the device (rvt_optim_step_guarded: the GradScaler's step-skip of
+    `precision: 16`).  Without a monitor, or with skip_nonfinite=False, `step()` is `rvt_optim_step` as before.
 
 Differences to the torch pieces a caller can see: the STORED gradients are not clipped (the clamp happens on the way into the
 update; `clip_grad_value_` rewrites them); one counter drives the bias correction and the schedule position of every
@@ -24,6 +28,8 @@ PyTorch fallback: a missing kernel raises.
 """
 from __future__ import annotations
 
+import ctypes
+import math
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -34,6 +40,7 @@ from . import _lib as L
 Tensor = torch.Tensor
 
 CHUNK = L.ENUMS['RVT_OPTIM_CHUNK_ELEMS']              # elements per row of the chunk table (include/rvt_hip.h: RvtOptimChunk)
+MAX_SCALARS = L.ENUMS['RVT_GRADSTAT_MAX_SCALARS']     # scalars per observation (include/rvt_hip.h: RvtGradStatHead)
 SCHEDULE = ('lr_init', 'lr_max', 'lr_final', 'warm_end', 'last')      # the schedule fields of RvtOptimGroup = OneCycle.constants()
 
 
@@ -120,6 +127,7 @@ class AdamW(torch.optim.Optimizer):
         self._chunks: Optional[L.DeviceTable] = None
         self._groups: Optional[L.DeviceTable] = None
         self._sig = self._hyper = None
+        self._monitor: Optional['GradMonitor'] = None     # attach_monitor()
 
     # ---- construction-time checks ---------------------------------------------------------------------------
     def add_param_group(self, param_group: Dict[str, Any]) -> None:
@@ -166,11 +174,8 @@ class AdamW(torch.optim.Optimizer):
         return L.DeviceTable('RvtOptimChunk').upload(self._step.device, np.concatenate(parts))
 
     # ---- the step ---------------------------------------------------------------------------------------------
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _entries(self) -> List[Tuple[Tensor, Tensor, int]]:
+        """(parameter, gradient, group index) of every parameter that has a gradient, in group order."""
         entries = []
         for gi, group in enumerate(self.param_groups):
             for p in group['params']:
@@ -179,12 +184,27 @@ class AdamW(torch.optim.Optimizer):
                     continue
                 _check_grad(p, g)
                 entries.append((p, g, gi))
-        if not entries:
-            return loss
+        return entries
+
+    def _sync_chunks(self, entries) -> None:
+        """The chunk table of these entries: rebuilt when an address or the set of gradients moved, and the monitor's chunk-to-tensor
+        array with it, in the same place, so the two cannot drift apart."""
         sig = tuple((p.data_ptr(), g.data_ptr(), gi) for p, g, gi in entries)
         if sig != self._sig:                              # (with the models' zero_copy_grads: never again after the first step)
             self._chunks = self._build_chunks(entries)
             self._sig = sig
+            if self._monitor is not None:
+                self._monitor._rebuild(entries)
+
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        entries = self._entries()
+        if not entries:
+            return loss
+        self._sync_chunks(entries)
         if len(self._chunks) == 0:                        # (only empty tensors)
             return loss
         rows = self._group_rows()
@@ -195,12 +215,27 @@ class AdamW(torch.optim.Optimizer):
                 self._groups.add(**row)
             self._groups.upload(self._step.device)
             self._hyper = rows
-        L.call('rvt_optim_step', L.ptr(self._chunks.dev), len(self._chunks), L.ptr(self._groups.dev), len(self._groups),
-               L.ptr(self._step), int(self.max_blocks), L.stream_of(self._step))
+        mon = self._monitor
+        if mon is not None and mon.skip_nonfinite:        # the step that obeys the monitor's latest verdict
+            L.call('rvt_optim_step_guarded', L.ptr(self._chunks.dev), len(self._chunks), L.ptr(self._groups.dev), len(self._groups),
+                   L.ptr(self._step), L.ptr(mon._verdict), int(self.max_blocks), L.stream_of(self._step))
+        else:
+            L.call('rvt_optim_step', L.ptr(self._chunks.dev), len(self._chunks), L.ptr(self._groups.dev), len(self._groups),
+                   L.ptr(self._step), int(self.max_blocks), L.stream_of(self._step))
         # the kernel wrote through raw pointers: tell autograd and the models' weight caches (backbone / FPN / head re-pack their
-        # kernel-side copies when a parameter's version moves).  Host-side counters only, no device work.
+        # kernel-side copies when a parameter's version moves).  Host-side counters only, no device work.  (A step the guard dropped
+        # on the device bumps them too: the host does not look.)
         torch.autograd.graph.increment_version([p for p, _, _ in entries])
         return loss
+
+    def attach_monitor(self, named_parameters, ring: int = 64, skip_nonfinite: bool = True) -> 'GradMonitor':
+        """Gradient statistics and the non-finite guard (GradMonitor below).  named_parameters: (name, parameter) pairs, e.g.
+        `model.named_parameters()`; every parameter must be one of this optimizer's.  With skip_nonfinite, step() becomes
+        rvt_optim_step_guarded and obeys the verdict of the latest observe().  A second call replaces the monitor."""
+        mon = GradMonitor(self, named_parameters, ring, skip_nonfinite)
+        self._monitor = mon
+        self._sig = None                                  # both tables are rebuilt together at the next observe() / step()
+        return mon
 
     # ---- what reads the device back ---------------------------------------------------------------------------
     def step_count(self) -> int:
@@ -255,6 +290,163 @@ class AdamW(torch.optim.Optimizer):
                 self.state.pop(p, None)
         self._step.fill_(int(k))
         self._sig = self._hyper = None
+
+
+class GradMonitor:
+    """Per-tensor gradient statistics and the non-finite verdict, computed on the device over the optimizer's own chunk table
+    (csrc/gradstats.hpp, rvt_grad_stats) into a ring the host reads later.  Made by `AdamW.attach_monitor`.
+
+    What it replaces in the reference's loop: `GradFlowLogCallback` (callbacks/gradflow.py; `param.grad.abs().mean()` per named
+    parameter = one host synchronisation each) and the GradScaler of `precision: 16`, which drops a step whose gradients hold an
+    inf or a NaN.  `observe()` is one library call (two launches), allocates nothing, does not synchronise and is capturable; it
+    writes slot `step % ring`, with `step` the optimizer's device counter read on the device, and the verdict that
+    `AdamW.step()` obeys when skip_nonfinite is set.  Call it after the backward and, under data parallelism, after the gradient
+    reduction has finished: every rank then sees the same gradients and reaches the same verdict with no collective added.  Call
+    it before every step: the guarded step obeys the LATEST verdict, however old.
+
+    A skipped step advances neither the bias correction nor the schedule position, because one device counter drives both
+    (Lightning would still step the scheduler); the next observation therefore lands in the same ring slot and replaces the
+    skipped one: `skipped_steps()` is the record that it happened.  `read()`, `grad_flow()` and `skipped_steps()` are the only
+    members that read the device back.  When the set of gradients or an address changes, the optimizer rebuilds its chunk table
+    and this monitor's chunk-to-tensor array with it, and the ring starts empty again (its rows are indexed by table position)."""
+
+    def __init__(self, opt: AdamW, named_parameters, ring: int, skip_nonfinite: bool):
+        if isinstance(ring, bool) or int(ring) != ring or ring < 1:
+            raise ValueError(f'ring must be a positive integer, got {ring}')
+        own = {id(p) for g in opt.param_groups for p in g['params']}
+        self._named: List[Tuple[str, Tensor]] = []
+        for name, p in named_parameters:
+            if id(p) not in own:
+                raise ValueError(f'parameter {name!r} is not one of the optimizer\'s')
+            self._named.append((str(name), p))
+        self._name_of = {id(p): name for name, p in self._named}
+        self.opt, self.ring, self.skip_nonfinite = opt, int(ring), bool(skip_nonfinite)
+        dev = opt._step.device
+        self._cap = max(len(own), 1)                      # rows per slot: one per tensor of the chunk table, at most every parameter
+        self._head_dt, self._stat_dt = L.row_dtype('RvtGradStatHead'), L.row_dtype('RvtGradStat')
+        hb, sb = self.ring * self._head_dt.itemsize, self.ring * self._cap * self._stat_dt.itemsize
+        # one device buffer = one copy per read(): [ring] heads | [ring][cap] rows | verdict[2]
+        self._buf = torch.zeros(hb + sb + 16, dtype=torch.uint8, device=dev)
+        self._heads, self._stats = self._buf[:hb], self._buf[hb:hb + sb]
+        self._verdict = self._buf[hb + sb:].view(torch.int64)
+        self._host: Optional[Tensor] = None
+        self._pending = None                              # (event or None,) of a copy read() has started and not yet parsed
+        self._first: Optional[Tensor] = None              # int32 [n_tensors + 1] first-chunk indices, on the device
+        self._rows: List[Optional[str]] = []              # name (None: not among named_parameters) of each tensor of the table
+        self._numel: List[int] = []
+        self._ws_bytes = 0
+        self._scalars: Tuple[Tensor, ...] = ()
+        self._empty_ring()
+
+    # ---- tables -----------------------------------------------------------------------------------------------
+    def _empty_ring(self) -> None:
+        heads = np.zeros(self.ring, dtype=self._head_dt)
+        heads['step'] = -1                                # no observation in this slot
+        self._heads.copy_(torch.from_numpy(heads.view(np.uint8).reshape(-1)))
+
+    def _rebuild(self, entries) -> None:
+        """Called by the optimizer exactly when it rebuilds its chunk table: the tensors of the table in table order."""
+        tensors = [p for p, _, _ in entries if p.numel() > 0]
+        counts = [(p.numel() + CHUNK - 1) // CHUNK for p in tensors]
+        first = np.zeros(len(tensors) + 1, dtype=np.int32)
+        first[1:] = np.cumsum(counts)
+        self._first = torch.from_numpy(first).to(self._buf.device)
+        self._rows = [self._name_of.get(id(p)) for p in tensors]
+        self._numel = [p.numel() for p in tensors]
+        self._ws_bytes = int(L.get_lib().rvt_grad_stats_ws_bytes(int(first[-1])))
+        self._pending = None
+        self._empty_ring()
+
+    # ---- the observation --------------------------------------------------------------------------------------
+    def observe(self, scalars=()) -> None:
+        """rvt_grad_stats on the current gradients.  scalars: up to RVT_GRADSTAT_MAX_SCALARS one-element float32 tensors on the
+        optimizer's device (the loss terms, ...); the launch reads their values and stores them in the slot's head, which is how a
+        loss reaches the host without an `.item()` per step.  A parameter whose `.grad` is None is left out, as in the reference."""
+        scalars = tuple(scalars)
+        if len(scalars) > MAX_SCALARS:
+            raise ValueError(f'at most {MAX_SCALARS} scalars per observation, got {len(scalars)}')
+        dev = self._buf.device
+        for t in scalars:
+            if not isinstance(t, Tensor) or t.dtype != torch.float32:
+                raise TypeError(f'scalars must be float32 tensors, got {t.dtype if isinstance(t, Tensor) else type(t).__name__}')
+            if t.numel() != 1 or t.device != dev:
+                raise ValueError(f'scalars must be one-element tensors on {dev}')
+        opt = self.opt
+        entries = opt._entries()
+        if not entries:
+            return
+        opt._sync_chunks(entries)
+        if len(opt._chunks) == 0:
+            return
+        st, ws = L.workspace('gradstats', opt._step, self._ws_bytes, torch.uint8)
+        ptrs = (ctypes.c_void_p * len(scalars))(*[L.ptr(t) for t in scalars]) if scalars else None
+        self._scalars = scalars                           # (a captured graph keeps reading these addresses)
+        L.call('rvt_grad_stats', L.ptr(opt._chunks.dev), len(opt._chunks), L.ptr(self._first), len(self._rows), L.ptr(opt._step),
+               ptrs, len(scalars), L.ptr(self._stats), self._cap, L.ptr(self._heads), self.ring, L.ptr(self._verdict), L.ptr(ws),
+               ws.numel(), int(opt.max_blocks), st)
+
+    # ---- what reads the device back ---------------------------------------------------------------------------
+    def read(self, last: int = 1, wait: bool = True) -> Optional[List[Dict[str, Any]]]:
+        """The `last` most recent observations in the ring, oldest first.  ONE non-blocking copy of the ring into a pinned buffer
+        plus an event; wait=False returns None while that copy is still in flight (ask again: the same copy is picked up).
+        Per observation: step (optimizer steps done before it), scalars, global_grad_norm, grad_abs_max, nonfinite, and `params`:
+        name -> grad_abs_mean (abs_sum / numel), grad_norm, grad_abs_max, param_norm, nonfinite, and the raw figures they come from
+        (numel, grad_abs_sum, grad_sq_sum, param_sq_sum; grad_sq_sum of the head too).  The sums run over the finite elements only."""
+        if last < 1:
+            raise ValueError(f'last must be at least 1, got {last}')
+        if self._pending is None:
+            if self._host is None:
+                self._host = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=self._buf.is_cuda)
+            self._host.copy_(self._buf, non_blocking=True)
+            ev = None
+            if self._buf.is_cuda:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self._buf.device))
+            self._pending = (ev,)
+        ev = self._pending[0]
+        if ev is not None:
+            if wait:
+                ev.synchronize()
+            elif not ev.query():
+                return None
+        self._pending = None
+        raw = self._host.numpy()
+        hb, sb = self._heads.numel(), self._stats.numel()
+        heads = raw[:hb].view(self._head_dt)
+        stats = raw[hb:hb + sb].view(self._stat_dt).reshape(self.ring, self._cap)
+        slots = sorted((int(heads['step'][s]), s) for s in range(self.ring) if heads['step'][s] >= 0)[-last:]
+        out = []
+        for k, s in slots:
+            h = heads[s]
+            params = {}
+            for t, (name, n) in enumerate(zip(self._rows, self._numel)):
+                r = stats[s, t]
+                if name is None or r['nonfinite'] < 0:
+                    continue
+                params[name] = dict(grad_abs_mean=float(r['abs_sum']) / n, grad_norm=math.sqrt(float(r['sq_sum'])),
+                                    grad_abs_max=float(r['abs_max']), param_norm=math.sqrt(float(r['param_sq_sum'])),
+                                    nonfinite=int(r['nonfinite']), numel=n, grad_abs_sum=float(r['abs_sum']),
+                                    grad_sq_sum=float(r['sq_sum']), param_sq_sum=float(r['param_sq_sum']))
+            out.append(dict(step=k, scalars=[float(v) for v in h['scalars'][:int(h['n_scalars'])]],
+                            global_grad_norm=math.sqrt(float(h['sq_sum'])), grad_abs_max=float(h['abs_max']),
+                            nonfinite=int(h['nonfinite']), grad_sq_sum=float(h['sq_sum']), params=params))
+        return out
+
+    def skipped_steps(self) -> int:
+        """Steps the guarded step() dropped so far.  Reads the device back."""
+        return int(self._verdict[1].item())
+
+    def grad_flow(self, slot: int = -1) -> Dict[str, List[Any]]:
+        """{'name': [...], 'grad_abs': [...]} of one observation (slot: index into read(last=ring), -1 = the newest), in the order of
+        named_parameters: the `data_dict` the reference's get_grad_flow_figure builds (callbacks/utils/visualization.py: every
+        parameter with requires_grad and a gradient; the mean of |grad|).  Reads the device back."""
+        rec = self.read(last=self.ring)[slot]
+        out: Dict[str, List[Any]] = {'name': [], 'grad_abs': []}
+        for name, p in self._named:
+            if p.requires_grad and name in rec['params']:
+                out['name'].append(name)
+                out['grad_abs'].append(rec['params'][name]['grad_abs_mean'])
+        return out
 
 
 def _key(cfg, name: str, default=None):
