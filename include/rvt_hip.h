@@ -754,6 +754,7 @@ int rvt_event_sequence_mixed(const RvtEventStream* streams, int B, int T, int co
  *     scale:    x1 = min((x + w) * m, capx); y1 likewise; x = x * m; y = y * m; w = x1 - x; h = y1 - y; dropped unless w, h > 0
  *   with, for zoom factor f:  mode 1: hx = min(x0 + W/f, W-1) - 1, m = f, capx = f * (W/f) - 1;  mode 2: m = 1/f,
  *   capx = (1/f) * W - 1 (y likewise). */
+enum { RVT_AUGMENT_PLANES_COLS = 8, RVT_AUGMENT_LABEL_COLS = 12 };    /* entries of one sample's row of the two tables */
 int rvt_augment_planes(const void* in, void* out, const int* table, int F, int B, int C, int H, int W, void* stream);
 int rvt_augment_labels(const float* rows, const int* count, const float* table, int F, int B, int G, float* rows_out, int* count_out,
                        float* yolox_out, void* stream);
@@ -813,6 +814,12 @@ int rvt_augment_labels(const float* rows, const int* count, const float* table, 
  *   walked in fixed-size pieces), no workspace, no allocation, no host synchronisation, no workgroup waits for another; replays in
  *   a hipGraph after the table was rewritten in place.  n = 0 returns 0 and launches nothing.  masks / value_base 8-byte,
  *   seg_offset / status 4-byte aligned; values at any byte address. */
+enum {                               /* the bits of status */
+    RVT_FRAMES_STATUS_CAPACITY = 1,  /* bit 0 */
+    RVT_FRAMES_STATUS_INDEX = 2,     /* bit 1 */
+    RVT_FRAMES_STATUS_COUNT = 4      /* bit 2 */
+};
+enum { RVT_FRAMES_GATHER_COLS = 4 };     /* int64 columns of a row of rvt_frames_gather's table */
 size_t rvt_frames_pack_ws_bytes(long long F, long long E);
 int rvt_frames_pack(const void* frames, long long F, long long E, void* masks, void* seg_offset, void* value_base, void* values,
                     long long capacity, void* status, void* ws, size_t ws_bytes, void* stream);

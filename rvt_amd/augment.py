@@ -47,7 +47,7 @@ NO_LABEL_WARN_MSG = 'No Labels found. This can lead to a crash and should not ha
 filterwarnings('always', message=NO_LABEL_WARN_MSG)
 
 MODE_NONE, MODE_ZOOM_IN, MODE_ZOOM_OUT = 0, 1, 2
-PLANES_TABLE_COLS, LABEL_TABLE_COLS = 8, 12
+PLANES_TABLE_COLS, LABEL_TABLE_COLS = L.ENUMS['RVT_AUGMENT_PLANES_COLS'], L.ENUMS['RVT_AUGMENT_LABEL_COLS']
 
 
 @dataclass

@@ -23,109 +23,47 @@
 // come from the host, computed in double and rounded once, which is what torch does with Python scalars on fp32 tensors.
 #pragma once
 #include "common.hpp"
-#include "augment_map.hpp"                            // constants, aug_pos, aug_nearest: shared with frames_augment.hpp
+#include "augment_map.hpp"                            // geometry and aug_planes_body: shared with frames_augment.hpp
 
 namespace rvt {
+
+// the dense stage of aug_planes_body: the cooperative (row, 16-byte piece) walk over the source rows of the frame `fin`
+struct AugDenseStage {
+    const unsigned char* __restrict__ fin;
+    template <bool VEC>
+    __device__ __forceinline__ void fill(unsigned char* srow, const int* src_rows, int nrows, int LW, int lo, int hi, int W) {
+        constexpr int T = AUG_THREADS, V = VEC ? 16 : 1;
+        const int tid = threadIdx.x, nsrc = hi - lo + 1;
+        int r = tid / nsrc, p = tid - r * nsrc;
+        const int dr = T / nsrc, dp = T - dr * nsrc;
+        while (r < nrows) {
+            const int src = src_rows[r];
+            if (src >= 0) {
+                const int x = (lo + p) * V;
+                const unsigned char* g = fin + (size_t)src * W + x;
+                unsigned char* s = &srow[r * LW + aug_pos(x)];
+                if constexpr (VEC) {
+                    const u32x4 v = *(const u32x4*)g;
+                    unsigned* s4 = (unsigned*)s;      // the skew keeps 4-byte, not 16-byte, alignment
+                    s4[0] = v.x; s4[1] = v.y; s4[2] = v.z; s4[3] = v.w;
+                } else {
+                    *s = *g;
+                }
+            }
+            r += dr; p += dp;
+            if (p >= nsrc) { p -= nsrc; r++; }
+        }
+    }
+};
 
 template <bool VEC>
 __global__ void __launch_bounds__(AUG_THREADS)
 augment_planes_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, const int* __restrict__ table,
                       int B, int C, int H, int W, int chunks) {
-    __shared__ __attribute__((aligned(16))) unsigned short xmap[AUG_MAX_W];
-    __shared__ __attribute__((aligned(16))) unsigned char srow[AUG_ROWS * AUG_LDS_ROW];
-    __shared__ int s_src[AUG_CHUNK];                  // source row inside the frame (plane * H + y), -1 = a zero row
-    constexpr int T = AUG_THREADS, V = VEC ? 16 : 1;
-    const int tid = threadIdx.x;
-    const int f = blockIdx.x / chunks, q0 = (blockIdx.x % chunks) * AUG_CHUNK, NR = C * H;
-    const int* tb = table + (size_t)(f % B) * AUG_PT;
-    const bool flip = tb[0] != 0;
-    const int mode = (tb[1] == 1 || tb[1] == 2) ? tb[1] : 0;
-    const int zh = aug_min(aug_max(tb[4], 1), H), zw = aug_min(aug_max(tb[5], 1), W);
-    const int x0 = aug_min(aug_max(tb[2], 0), W - zw), y0 = aug_min(aug_max(tb[3], 0), H - zh);
-    const int LW = ((aug_pos(W - 1) + 4) & ~3) + 4, ZREL = LW - 4;      // LDS row pitch; its last dword stays zero
-    const unsigned char* fin = in + (size_t)f * NR * W;
-    unsigned char* fout = out + (size_t)f * NR * W;
-
-    for (int x = tid; x < W; x += T) {
-        int sx = x;
-        if (mode == 1) sx = x0 + aug_nearest(x, W, zw);
-        else if (mode == 2) sx = (x >= x0 && x < x0 + zw) ? aug_nearest(x - x0, zw, W) : -1;
-        if (sx >= 0 && flip) sx = W - 1 - sx;
-        xmap[x] = (unsigned short)(sx < 0 ? ZREL : aug_pos(sx));
-    }
-    if (tid < AUG_CHUNK) {
-        const int q = q0 + tid;
-        int src = -1;
-        if (q < NR) {
-            const int c = q / H, y = q - c * H;
-            int sy = y;
-            if (mode == 1) sy = y0 + aug_nearest(y, H, zh);
-            else if (mode == 2) sy = (y >= y0 && y < y0 + zh) ? aug_nearest(y - y0, zh, H) : -1;
-            src = sy < 0 ? -1 : c * H + sy;
-        }
-        s_src[tid] = src;
-    }
-    if (tid < AUG_ROWS) *(unsigned*)&srow[tid * LW + ZREL] = 0u;
-    // source columns a row needs, in units of V bytes
-    const int lo = (mode == 1 ? (flip ? W - x0 - zw : x0) : 0) / V;
-    const int hi = (mode == 1 ? (flip ? W - 1 - x0 : x0 + zw - 1) : W - 1) / V;
-    const int nsrc = hi - lo + 1, ndst = W / V;
-
-    for (int qb = q0; qb < q0 + AUG_CHUNK && qb < NR; qb += AUG_ROWS) {
-        const int nrows = aug_min(AUG_ROWS, NR - qb);
-        __syncthreads();                              // x map and row table written; the previous group's gather is done
-        {
-            int r = tid / nsrc, p = tid - r * nsrc;
-            const int dr = T / nsrc, dp = T - dr * nsrc;
-            while (r < nrows) {
-                const int src = s_src[qb - q0 + r];
-                if (src >= 0) {
-                    const int x = (lo + p) * V;
-                    const unsigned char* g = fin + (size_t)src * W + x;
-                    unsigned char* s = &srow[r * LW + aug_pos(x)];
-                    if constexpr (VEC) {
-                        const u32x4 v = *(const u32x4*)g;
-                        unsigned* s4 = (unsigned*)s;  // the skew keeps 4-byte, not 16-byte, alignment
-                        s4[0] = v.x; s4[1] = v.y; s4[2] = v.z; s4[3] = v.w;
-                    } else {
-                        *s = *g;
-                    }
-                }
-                r += dr; p += dp;
-                if (p >= nsrc) { p -= nsrc; r++; }
-            }
-        }
-        __syncthreads();
-        {
-            int r = tid / ndst, p = tid - r * ndst;
-            const int dr = T / ndst, dp = T - dr * ndst;
-            while (r < nrows) {
-                const bool zero = s_src[qb - q0 + r] < 0;
-                const unsigned char* s = &srow[r * LW];
-                unsigned char* g = fout + (size_t)(qb + r) * W + p * V;
-                if constexpr (VEC) {
-                    u32x4 v = {0u, 0u, 0u, 0u};
-                    if (!zero) {
-                        const u32x4 ma = *(const u32x4*)&xmap[p * 16], mb = *(const u32x4*)&xmap[p * 16 + 8];
-                        const unsigned m[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
-                        unsigned w[4];
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const unsigned a = m[2 * k], b = m[2 * k + 1];
-                            w[k] = (unsigned)s[a & 0xffffu] | ((unsigned)s[a >> 16] << 8) | ((unsigned)s[b & 0xffffu] << 16) |
-                                   ((unsigned)s[b >> 16] << 24);
-                        }
-                        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-                    }
-                    *(u32x4*)g = v;
-                } else {
-                    *g = zero ? (unsigned char)0 : s[xmap[p]];
-                }
-                r += dr; p += dp;
-                if (p >= ndst) { p -= ndst; r++; }
-            }
-        }
-    }
+    const int f = blockIdx.x / chunks, q0 = (blockIdx.x % chunks) * AUG_CHUNK;
+    const size_t frame = (size_t)f * C * H * W;
+    AugDenseStage stage{in + frame};
+    aug_planes_body<VEC>(stage, table + (size_t)(f % B) * AUG_PT, out + frame, q0, C, H, W);
 }
 
 // scale_ of the reference: returns whether the row survives (w > 0 and h > 0)

@@ -19,13 +19,9 @@ int rvt_augment_planes(const void* in, void* out, const int* table, int F, int B
     RVT_CHECK(a + bytes <= b || b + bytes <= a, "augment_planes: in and out overlap (the call is not in-place)");
     const int chunks = (C * H + AUG_CHUNK - 1) / AUG_CHUNK;
     RVT_CHECK((long long)F * chunks <= 0x7fffffffLL, "augment_planes: F=%d frames of %d rows exceed the grid", F, C * H);
-    const dim3 grid((unsigned)(F * chunks));
-    if (W % 16 == 0 && a % 16 == 0 && b % 16 == 0)
-        hipLaunchKernelGGL((augment_planes_kernel<true>), grid, dim3(AUG_THREADS), 0, (hipStream_t)stream, (const unsigned char*)in,
-                           (unsigned char*)out, table, B, C, H, W, chunks);
-    else
-        hipLaunchKernelGGL((augment_planes_kernel<false>), grid, dim3(AUG_THREADS), 0, (hipStream_t)stream, (const unsigned char*)in,
-                           (unsigned char*)out, table, B, C, H, W, chunks);
+    const bool vec = W % 16 == 0 && a % 16 == 0 && b % 16 == 0;
+    hipLaunchKernelGGL(vec ? augment_planes_kernel<true> : augment_planes_kernel<false>, dim3((unsigned)(F * chunks)), dim3(AUG_THREADS), 0,
+                       (hipStream_t)stream, (const unsigned char*)in, (unsigned char*)out, table, B, C, H, W, chunks);
     return check_launch("augment_planes");
 }
 

@@ -24,6 +24,20 @@ static inline bool frames_grid(long long waves, dim3& grid) {
     grid = dim3((unsigned)blocks);
     return true;
 }
+// the argument checks rvt_frames_unpack and rvt_frames_unpack_augment share; who: the entry point's name in the messages, table:
+// rvt_frames_unpack_augment's (has_table), checked like the other arrays
+static int frames_unpack_checks(const char* who, const void* masks, const void* seg_offset, const void* value_base, const void* values,
+                                long long values_len, long long F, long long E, const long long* index, long long Fout, const void* out,
+                                const void* status, bool has_table, const void* table) {
+    RVT_CHECK(masks && seg_offset && value_base && out && status && (table || !has_table), "%s: null argument", who);
+    RVT_CHECK(frames_shape_ok(F, E) && Fout >= 1, "%s: F=%lld, Fout=%lld frames of E=%lld bytes outside the supported range", who, F, Fout, E);
+    RVT_CHECK(values_len >= 0 && (values || values_len == 0), "%s: values_len=%lld without a values array", who, values_len);
+    RVT_CHECK(index || Fout <= F, "%s: without an index Fout=%lld must not exceed F=%lld", who, Fout, F);
+    RVT_CHECK(((uintptr_t)masks & 7) == 0 && ((uintptr_t)value_base & 7) == 0 && ((uintptr_t)index & 7) == 0 &&
+              ((uintptr_t)seg_offset & 3) == 0 && ((uintptr_t)status & 3) == 0 && ((uintptr_t)table & 3) == 0,
+              "%s: masks / value_base / index need 8-byte, seg_offset / status%s 4-byte alignment", who, has_table ? " / table" : "");
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -63,13 +77,7 @@ int rvt_frames_pack(const void* frames, long long F, long long E, void* masks, v
 
 int rvt_frames_unpack(const void* masks, const void* seg_offset, const void* value_base, const void* values, long long values_len,
                       long long F, long long E, const long long* index, long long Fout, void* out, void* status, void* stream) {
-    RVT_CHECK(masks && seg_offset && value_base && out && status, "frames_unpack: null argument");
-    RVT_CHECK(frames_shape_ok(F, E) && Fout >= 1, "frames_unpack: F=%lld, Fout=%lld frames of E=%lld bytes outside the supported range", F, Fout, E);
-    RVT_CHECK(values_len >= 0 && (values || values_len == 0), "frames_unpack: values_len=%lld without a values array", values_len);
-    RVT_CHECK(index || Fout <= F, "frames_unpack: without an index Fout=%lld must not exceed F=%lld", Fout, F);
-    RVT_CHECK(((uintptr_t)masks & 7) == 0 && ((uintptr_t)value_base & 7) == 0 && ((uintptr_t)index & 7) == 0 &&
-              ((uintptr_t)seg_offset & 3) == 0 && ((uintptr_t)status & 3) == 0,
-              "frames_unpack: masks / value_base / index need 8-byte, seg_offset / status 4-byte alignment");
+    RVT_TRY(frames_unpack_checks("frames_unpack", masks, seg_offset, value_base, values, values_len, F, E, index, Fout, out, status, false, nullptr));
     const FrameGeom g = frame_geom(E);
     dim3 grid;
     RVT_CHECK(Fout <= 0x7fffffffLL && frames_grid(Fout * g.Sf, grid), "frames_unpack: Fout=%lld frames of %lld segments exceed the grid", Fout, g.Sf);
@@ -82,31 +90,19 @@ int rvt_frames_unpack(const void* masks, const void* seg_offset, const void* val
 int rvt_frames_unpack_augment(const void* masks, const void* seg_offset, const void* value_base, const void* values, long long values_len,
                               long long F, long long E, const long long* index, long long Fout, const int* table, int B, int C, int H, int W,
                               void* out, void* status, void* stream) {
-    RVT_CHECK(masks && seg_offset && value_base && table && out && status, "frames_unpack_augment: null argument");
-    RVT_CHECK(frames_shape_ok(F, E) && Fout >= 1, "frames_unpack_augment: F=%lld, Fout=%lld frames of E=%lld bytes outside the supported range", F, Fout, E);
+    RVT_TRY(frames_unpack_checks("frames_unpack_augment", masks, seg_offset, value_base, values, values_len, F, E, index, Fout, out, status, true, table));
     RVT_CHECK(B >= 1 && C >= 1 && H >= 1 && W >= 1, "frames_unpack_augment: B=%d C=%d H=%d W=%d must be positive", B, C, H, W);
     RVT_CHECK(W <= AUG_MAX_W, "frames_unpack_augment: W=%d outside the supported range 1..%d", W, AUG_MAX_W);
     RVT_CHECK((long long)C * H <= (1 << 24), "frames_unpack_augment: C*H=%lld rows per frame outside the supported range", (long long)C * H);
     RVT_CHECK((long long)C * H * W == E, "frames_unpack_augment: a frame of E=%lld bytes is not C*H*W = %d*%d*%d", E, C, H, W);
-    RVT_CHECK(values_len >= 0 && (values || values_len == 0), "frames_unpack_augment: values_len=%lld without a values array", values_len);
-    RVT_CHECK(index || Fout <= F, "frames_unpack_augment: without an index Fout=%lld must not exceed F=%lld", Fout, F);
-    RVT_CHECK(((uintptr_t)masks & 7) == 0 && ((uintptr_t)value_base & 7) == 0 && ((uintptr_t)index & 7) == 0 &&
-              ((uintptr_t)seg_offset & 3) == 0 && ((uintptr_t)status & 3) == 0 && ((uintptr_t)table & 3) == 0,
-              "frames_unpack_augment: masks / value_base / index need 8-byte, seg_offset / status / table 4-byte alignment");
     const FrameGeom g = frame_geom(E);
     const int chunks = (C * H + AUG_CHUNK - 1) / AUG_CHUNK;
     RVT_CHECK(Fout * chunks <= 0x7fffffffLL, "frames_unpack_augment: Fout=%lld frames of %d rows exceed the grid", Fout, C * H);
-    const dim3 grid((unsigned)(Fout * chunks));
-    if (W % 16 == 0 && (uintptr_t)out % 16 == 0)
-        hipLaunchKernelGGL((frames_unpack_augment_kernel<true>), grid, dim3(AUG_THREADS), 0, (hipStream_t)stream,
-                           (const unsigned long long*)masks, (const unsigned*)seg_offset, (const long long*)value_base,
-                           (const unsigned char*)values, values_len, F, E, g.Gf, g.Sf, index, table, B, C, H, W, chunks, (unsigned char*)out,
-                           (int*)status);
-    else
-        hipLaunchKernelGGL((frames_unpack_augment_kernel<false>), grid, dim3(AUG_THREADS), 0, (hipStream_t)stream,
-                           (const unsigned long long*)masks, (const unsigned*)seg_offset, (const long long*)value_base,
-                           (const unsigned char*)values, values_len, F, E, g.Gf, g.Sf, index, table, B, C, H, W, chunks, (unsigned char*)out,
-                           (int*)status);
+    const bool vec = W % 16 == 0 && (uintptr_t)out % 16 == 0;
+    hipLaunchKernelGGL(vec ? frames_unpack_augment_kernel<true> : frames_unpack_augment_kernel<false>, dim3((unsigned)(Fout * chunks)),
+                       dim3(AUG_THREADS), 0, (hipStream_t)stream, (const unsigned long long*)masks, (const unsigned*)seg_offset,
+                       (const long long*)value_base, (const unsigned char*)values, values_len, F, E, g.Gf, g.Sf, index, table, B, C, H, W,
+                       chunks, (unsigned char*)out, (int*)status);
     return check_launch("frames_unpack_augment");
 }
 

@@ -56,6 +56,20 @@ template <class T> __device__ __forceinline__ frag_t<T> frag_from_float(const fl
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// wave-level rendezvous for data handed between LANES of one wave through LDS.  The hardware needs nothing (the LDS operations of a
+// wave execute in order), the COMPILER does: with an empty pp_wave_sync() hipcc sank the read-back of line_bounce.hpp's bounce tile into the
+// divergent `if` that guards the writes - lanes outside the branch then stored stale registers (caught by the GPU parity test only:
+// the emulator's rendezvous is a real one).  Wavefront-scope fences + the convergent wave barrier pin the order; no instruction is emitted.
+__device__ __forceinline__ void wave_rendezvous() {
+#ifdef RVT_EMU
+    emu::wave_barrier();
+#else
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
+}
 __device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // ---- MFMA: one 32x32 output block, K = 16 ------------------------------------------------------

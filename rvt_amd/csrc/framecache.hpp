@@ -41,18 +41,8 @@ constexpr int FC_THREADS = 256;
 constexpr int FC_WAVES = FC_THREADS / 64;                      // segments per workgroup
 constexpr int FC_GROUP = 64;                                   // bytes under one mask word
 constexpr int FC_SEG = 64 * FC_GROUP;                          // bytes of one segment
-constexpr int FC_STATUS_CAPACITY = 1, FC_STATUS_INDEX = 2;
-
-// lanes of one wave hand data to each other through LDS (the twin of wave_rendezvous in line_bounce.hpp, without its GEMM includes)
-__device__ __forceinline__ void fc_wave_sync() {
-#ifdef RVT_EMU
-    emu::wave_barrier();
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-}
+constexpr int FC_STATUS_CAPACITY = RVT_FRAMES_STATUS_CAPACITY, FC_STATUS_INDEX = RVT_FRAMES_STATUS_INDEX,
+              FC_STATUS_COUNT = RVT_FRAMES_STATUS_COUNT;     // the bits of status (include/rvt_hip.h)
 
 __device__ __forceinline__ void fc_status_or(int* status, int bits) {
 #ifdef RVT_EMU
@@ -71,7 +61,7 @@ __device__ __forceinline__ int fc_wave_scan(int v, int lane) {
     }
     return v;
 }
-__device__ __forceinline__ long long fc_wave_scan64(long long v, int lane) {
+__device__ __forceinline__ long long fc_wave_scan(long long v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const unsigned lo = (unsigned)__shfl((int)(unsigned)((unsigned long long)v & 0xffffffffULL), (lane - d) & 63);
@@ -94,17 +84,70 @@ __device__ __forceinline__ unsigned fc_byte_of(const u32x4& v, int k) {
     return (w >> (8 * (k & 3))) & 0xffu;
 }
 
-// frame bytes [r, r + 16), r a multiple of 16; zeros behind the frame's end
-__device__ __forceinline__ u32x4 fc_load_line(const unsigned char* __restrict__ frame, bool aligned, long long r, long long E) {
+// The 16-byte line [lo, lo + 16) behind `base` (base + lo is 16-byte aligned) of a run that owns the bytes [b, e) behind `base`: a
+// line inside the run is one 16-byte access, the run's first and last line move byte by byte inside the run, and nothing outside
+// the run is touched (bytes not loaded read as zero; edges are stored by byte stores, never by read-modify-write).  aligned = false:
+// base + lo is not aligned (a frame of a pack's input with E % 16 != 0), and every line moves byte by byte.
+template <typename I>
+__device__ __forceinline__ u32x4 fc_line_load(const unsigned char* __restrict__ base, I lo, I b, I e, bool aligned = true) {
     u32x4 v = {0u, 0u, 0u, 0u};
-    if (aligned && r + 16 <= E) {
-        v = *reinterpret_cast<const u32x4*>(frame + r);
-    } else if (r < E) {
+    if (aligned && lo >= b && lo + 16 <= e) {
+        v = *reinterpret_cast<const u32x4*>(base + lo);
+    } else if (lo + 16 > b && lo < e) {
 #pragma unroll
         for (int k = 0; k < 16; k++)
-            if (r + k < E) v[k >> 2] |= (unsigned)frame[r + k] << (8 * (k & 3));
+            if (lo + k >= b && lo + k < e) v[k >> 2] |= (unsigned)base[lo + k] << (8 * (k & 3));
     }
     return v;
+}
+template <typename I>
+__device__ __forceinline__ void fc_line_store(unsigned char* __restrict__ base, I lo, I b, I e, const u32x4& v) {
+    if (lo >= b && lo + 16 <= e) {
+        *reinterpret_cast<u32x4*>(base + lo) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if (lo + k >= b && lo + k < e) base[lo + k] = (unsigned char)((v[k >> 2] >> (8 * (k & 3))) & 0xffu);
+    }
+}
+
+// Exclusive sum over the workgroup of one tile of a longer sequence (a value per thread, int or long long): returns what lies in
+// front of this thread's value, `run` = the total of the tiles in front, advanced by this tile's.  part: LDS, one row per parity of
+// the tile number (the other parity is free: its readers passed this tile's barrier a tile ago).  Every thread calls it.
+template <typename V>
+__device__ __forceinline__ V fc_block_scan(V v, V& run, V (*part)[FC_WAVES], int par) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const V inc = fc_wave_scan(v, lane);
+    if (lane == 63) part[par][wave] = inc;
+    __syncthreads();
+    V pre = run + inc - v;
+#pragma unroll
+    for (int q = 0; q < FC_WAVES; q++) {
+        const V t = part[par][q];
+        if (q < wave) pre += t;
+        run += t;
+    }
+    return pre;
+}
+
+// Parks segment s of a frame for a wave's decode: the 64 masks (fmask = the frame's Gf masks; the bits behind the frame's end E
+// cleared, groups behind it zero) to mg[0..63] and the count of values in front of each group within the segment to pg[0..63],
+// both in LDS.  Returns the segment's count.  The caller keeps the wave's earlier readers of mg / pg away and calls
+// wave_rendezvous() before the first read.
+__device__ __forceinline__ int fc_park_segment(const unsigned long long* __restrict__ fmask, long long s, long long E, long long Gf,
+                                               unsigned long long* mg, int* pg, int lane) {
+    const long long g = s * 64 + lane;
+    unsigned long long m = 0;
+    if (g < Gf) {
+        m = fmask[g];
+        const long long nb = E - 64 * g;                        // bytes of the group that exist
+        if (nb < 64) m &= (1ULL << nb) - 1;
+    }
+    const int c = __builtin_popcountll(m);
+    const int inc = fc_wave_scan(c, lane);
+    mg[lane] = m;
+    pg[lane] = inc - c;
+    return __shfl(inc, 63);
 }
 
 // -------------------------------------------------------------------------------------------------- pack, launch 1: masks + counts
@@ -120,10 +163,10 @@ frames_mask_kernel(const unsigned char* __restrict__ frames, long long F, long l
     const bool aligned = ((uintptr_t)frame & 15) == 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const u32x4 v = fc_load_line(frame, aligned, s * FC_SEG + j * 1024 + lane * 16, E);
+        const u32x4 v = fc_line_load(frame, (unsigned long long)(s * FC_SEG + j * 1024 + lane * 16), 0ULL, (unsigned long long)E, aligned);
         bits[wave][j * 64 + lane] = (unsigned short)fc_nonzero16(v);
     }
-    fc_wave_sync();
+    wave_rendezvous();
     const unsigned long long m = *reinterpret_cast<const unsigned long long*>(&bits[wave][lane * 4]);
     const long long g = s * 64 + lane;
     if (g < Gf) masks[f * Gf + g] = m;
@@ -139,24 +182,13 @@ __global__ void __launch_bounds__(FC_THREADS)
 frames_seg_scan_kernel(const unsigned* __restrict__ seg_count, long long Sf, unsigned* __restrict__ seg_offset,
                        unsigned* __restrict__ frame_count) {
     __shared__ int part[2][FC_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long f = blockIdx.x;
     const unsigned* __restrict__ src = seg_count + f * Sf;
     unsigned* __restrict__ dst = seg_offset + f * (Sf + 1);
     int run = 0, par = 0;                                       // (a frame holds fewer than 2^31 bytes)
     for (long long base = 0; base < Sf; base += FC_THREADS, par ^= 1) {
         const long long i = base + threadIdx.x;
-        const int v = i < Sf ? (int)src[i] : 0;
-        const int inc = fc_wave_scan(v, lane);
-        if (lane == 63) part[par][wave] = inc;
-        __syncthreads();                                        // (the other parity is free: its readers passed this barrier a tile ago)
-        int pre = run + inc - v;
-#pragma unroll
-        for (int q = 0; q < FC_WAVES; q++) {
-            const int t = part[par][q];
-            if (q < wave) pre += t;
-            run += t;
-        }
+        const int pre = fc_block_scan(i < Sf ? (int)src[i] : 0, run, part, par);
         if (i < Sf) dst[i] = (unsigned)pre;
     }
     if (threadIdx.x == 0) {
@@ -171,22 +203,11 @@ __global__ void __launch_bounds__(FC_THREADS)
 frames_base_scan_kernel(const unsigned* __restrict__ frame_count, long long F, long long capacity, long long* __restrict__ value_base,
                         int* __restrict__ status) {
     __shared__ long long part[2][FC_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long run = 0;
     int par = 0;
     for (long long base = 0; base < F; base += FC_THREADS, par ^= 1) {
         const long long i = base + threadIdx.x;
-        const long long v = i < F ? (long long)frame_count[i] : 0;
-        const long long inc = fc_wave_scan64(v, lane);
-        if (lane == 63) part[par][wave] = inc;
-        __syncthreads();
-        long long pre = run + inc - v;
-#pragma unroll
-        for (int q = 0; q < FC_WAVES; q++) {
-            const long long t = part[par][q];
-            if (q < wave) pre += t;
-            run += t;
-        }
+        const long long pre = fc_block_scan(i < F ? (long long)frame_count[i] : 0LL, run, part, par);
         if (i < F) value_base[i] = pre;
     }
     if (threadIdx.x == 0) {
@@ -217,7 +238,7 @@ frames_compact_kernel(const unsigned char* __restrict__ frames, long long F, lon
     unsigned m[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        v[j] = fc_load_line(frame, aligned, s * FC_SEG + j * 1024 + lane * 16, E);
+        v[j] = fc_line_load(frame, (unsigned long long)(s * FC_SEG + j * 1024 + lane * 16), 0ULL, (unsigned long long)E, aligned);
         m[j] = fc_nonzero16(v[j]);
     }
     // where each line's bytes go: byte order is (j, lane), so four exclusive scans over the lanes, two 16-bit counts per scan
@@ -246,19 +267,10 @@ frames_compact_kernel(const unsigned char* __restrict__ frames, long long F, lon
             img[q++] = (unsigned char)fc_byte_of(v[j], k);
         }
     }
-    fc_wave_sync();
+    wave_rendezvous();
     unsigned char* line0 = dst - a;
     const int end = a + n_fit, nlines = (end + 15) >> 4;
-    for (int L = lane; L < nlines; L += 64) {
-        const int lo = 16 * L;
-        if (lo >= a && lo + 16 <= end) {
-            *reinterpret_cast<u32x4*>(line0 + lo) = *reinterpret_cast<const u32x4*>(img + lo);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                if (lo + k >= a && lo + k < end) line0[lo + k] = img[lo + k];
-        }
-    }
+    for (int L = lane; L < nlines; L += 64) fc_line_store(line0, 16 * L, a, end, *reinterpret_cast<const u32x4*>(img + 16 * L));
 }
 
 // -------------------------------------------------------------------------------------------------------------------------- unpack
@@ -280,17 +292,8 @@ frames_unpack_kernel(const unsigned long long* __restrict__ masks, const unsigne
     const long long left = E - s * FC_SEG;
     const int len = left < FC_SEG ? (int)left : FC_SEG;         // bytes of this segment
 
-    unsigned long long m = 0;
-    const int nb = len - 64 * lane;                             // bytes of group `lane` that exist
-    if (present && nb > 0) {
-        m = masks[idx * Gf + s * 64 + lane];
-        if (nb < 64) m &= (1ULL << nb) - 1;
-    }
-    const int c = __builtin_popcountll(m);
-    const int inc = fc_wave_scan(c, lane);
-    const int total = __shfl(inc, 63);
-    mgrp[wave][1 + lane] = m;
-    pgrp[wave][1 + lane] = inc - c;
+    // (a frame that is not there has no groups: all masks zero)
+    const int total = fc_park_segment(masks + (present ? idx : 0) * Gf, s, E, present ? Gf : 0, &mgrp[wave][1], &pgrp[wave][1], lane);
     if (lane == 0) {
         mgrp[wave][0] = 0; pgrp[wave][0] = 0;
         mgrp[wave][65] = 0; pgrp[wave][65] = total;
@@ -303,20 +306,10 @@ frames_unpack_kernel(const unsigned long long* __restrict__ masks, const unsigne
         av = (int)(((uintptr_t)values + (uintptr_t)start) & 15);
         const long long first = start - av;                     // index into values of the image's byte 0
         const int nl = (av + total + 15) >> 4;
-        for (int L = lane; L < nl; L += 64) {
-            const long long gi = first + 16 * L;
-            u32x4 q = {0u, 0u, 0u, 0u};
-            if (gi >= 0 && gi + 16 <= values_len) {
-                q = *reinterpret_cast<const u32x4*>(values + gi);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 16; k++)
-                    if (gi + k >= 0 && gi + k < values_len) q[k >> 2] |= (unsigned)values[gi + k] << (8 * (k & 3));
-            }
-            *reinterpret_cast<u32x4*>(img + 16 * L) = q;
-        }
+        for (int L = lane; L < nl; L += 64)                     // (lines of the ADDRESS values + first; the array is the run [0, values_len))
+            *reinterpret_cast<u32x4*>(img + 16 * L) = fc_line_load(values, first + 16 * L, 0LL, values_len);
     }
-    fc_wave_sync();
+    wave_rendezvous();
 
     unsigned char* o = out + fo * E + s * FC_SEG;
     const int a = (int)((uintptr_t)o & 15);
@@ -337,13 +330,7 @@ frames_unpack_kernel(const unsigned long long* __restrict__ masks, const unsigne
             q0 |= wd == 0 ? b : 0u; q1 |= wd == 1 ? b : 0u; q2 |= wd == 2 ? b : 0u; q3 |= wd == 3 ? b : 0u;
         }
         const u32x4 q = {q0, q1, q2, q3};
-        if (r0 >= 0 && r0 + 16 <= len) {
-            *reinterpret_cast<u32x4*>(line0 + 16 * L) = q;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                if (r0 + k >= 0 && r0 + k < len) line0[16 * L + k] = (unsigned char)((q[k >> 2] >> (8 * (k & 3))) & 0xffu);
-        }
+        fc_line_store(line0, 16 * L, a, a + len, q);
     }
 }
 

@@ -25,9 +25,8 @@
 
 namespace rvt {
 
-constexpr int FC_STATUS_COUNT = 4;                             // bit 2: gather met a row whose count is outside [0, E]
 constexpr int GA_PIECE = 16384;                                // bytes of one piece of work (a wave: 16 instructions of 1 KiB)
-constexpr int GA_COLS = 4;                                     // int64 columns of a table row
+constexpr int GA_COLS = RVT_FRAMES_GATHER_COLS;                // int64 columns of a table row
 constexpr int GA_DEFAULT_BLOCKS = 64;
 
 // --------------------------------------------------------------------------------------------- launch 1: value_base and status
@@ -46,16 +45,7 @@ frames_gather_scan_kernel(const long long* __restrict__ table, long long n, long
             v = table[i * GA_COLS + 3];
             if (v < 0 || v > E) { v = 0; bad = 1; }
         }
-        const long long inc = fc_wave_scan64(v, lane);
-        if (lane == 63) part[par][wave] = inc;
-        __syncthreads();                                        // (the other parity is free: its readers passed this barrier a tile ago)
-        long long pre = run + inc - v;
-#pragma unroll
-        for (int q = 0; q < FC_WAVES; q++) {
-            const long long t = part[par][q];
-            if (q < wave) pre += t;
-            run += t;
-        }
+        const long long pre = fc_block_scan(v, run, part, par);
         if (i < n) value_base[i] = pre;
     }
 #pragma unroll
@@ -105,21 +95,6 @@ __device__ __forceinline__ u32x4 ga_shift_bytes(const u32x4& lo, const u32x4& hi
     return r;
 }
 
-// aligned source line q of a run: bytes [16 q, 16 q + 16) behind `line0` (16-byte aligned), of which the run owns [b, e); whole
-// lines are one 16-byte load, the run's first and last line are read byte by byte inside the run, any other line is not read
-__device__ __forceinline__ u32x4 ga_load_line(const unsigned char* __restrict__ line0, long long q, long long b, long long e) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    const long long lo = 16 * q;
-    if (lo >= b && lo + 16 <= e) {
-        v = *reinterpret_cast<const u32x4*>(line0 + lo);
-    } else if (lo + 16 > b && lo < e) {
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            if (lo + k >= b && lo + k < e) v[k >> 2] |= (unsigned)line0[lo + k] << (8 * (k & 3));
-    }
-    return v;
-}
-
 // len > 0 bytes from s to d, any alignment on either side, by one wave (every lane calls it with the same arguments)
 __device__ __forceinline__ void ga_copy_bytes(const unsigned char* __restrict__ s, unsigned char* __restrict__ d, long long len, int lane) {
     const int a = (int)((uintptr_t)d & 15), b = (int)((uintptr_t)s & 15);
@@ -129,10 +104,11 @@ __device__ __forceinline__ void ga_copy_bytes(const unsigned char* __restrict__ 
     // destination line k = bytes [sh, sh + 16) of the source lines k + off, k + off + 1
     const int off = b < a ? -1 : 0, sh = b < a ? b - a + 16 : b - a;
     const long long nlines = (dend + 15) >> 4;
-    u32x4 carry = ga_load_line(sline0, off, b, send);           // the line in front of lane 0's (the same load in every lane)
+    // source lines (fc_line_load): whole ones are one 16-byte load, the run's first and last are read byte by byte inside the run
+    u32x4 carry = fc_line_load(sline0, 16LL * off, (long long)b, send);    // the line in front of lane 0's (the same load in every lane)
     for (long long m = 0; m < nlines; m += 64) {                // (the same trip count in every lane: the shuffles below are wave-wide)
         const long long k = m + lane;
-        const u32x4 hi = ga_load_line(sline0, k + off + 1, b, send);
+        const u32x4 hi = fc_line_load(sline0, 16 * (k + off + 1), (long long)b, send);
         u32x4 lo;
 #pragma unroll
         for (int w = 0; w < 4; w++) {
@@ -140,17 +116,7 @@ __device__ __forceinline__ void ga_copy_bytes(const unsigned char* __restrict__ 
             lo[w] = lane == 0 ? carry[w] : up;
             carry[w] = (unsigned)__shfl((int)hi[w], 63);
         }
-        if (k < nlines) {
-            const u32x4 q = ga_shift_bytes(lo, hi, sh);
-            const long long p = 16 * k;
-            if (p >= a && p + 16 <= dend) {
-                *reinterpret_cast<u32x4*>(dline0 + p) = q;
-            } else {
-#pragma unroll
-                for (int t = 0; t < 16; t++)
-                    if (p + t >= a && p + t < dend) dline0[p + t] = (unsigned char)((q[t >> 2] >> (8 * (t & 3))) & 0xffu);
-            }
-        }
+        if (k < nlines) fc_line_store(dline0, 16 * k, (long long)a, dend, ga_shift_bytes(lo, hi, sh));
     }
 }
 

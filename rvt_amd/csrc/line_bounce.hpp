@@ -6,20 +6,6 @@
 
 namespace rvt {
 
-// wave-level rendezvous for data handed between LANES of one wave through LDS.  The hardware needs nothing (the LDS operations of a
-// wave execute in order), the COMPILER does: with an empty pp_wave_sync() hipcc sank the read-back of the bounce tile below into the
-// divergent `if` that guards the writes - lanes outside the branch then stored stale registers (caught by the GPU parity test only:
-// the emulator's rendezvous is a real one).  Wavefront-scope fences + the convergent wave barrier pin the order; no instruction is emitted.
-__device__ __forceinline__ void wave_rendezvous() {
-#ifdef RVT_EMU
-    emu::wave_barrier();
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-}
-
 // Rows leave as FULL 128-byte lines.  In the T-form a lane owns a token, so a store of accumulator pieces writes 32 bytes of 32
 // different lines; with that pattern three different kernels for fc1 + GELU (GEMM engine, streamed weights, weight-stationary) all
 // sat at 2.7 - 2.9 TB/s (a contiguous fill reaches 6.7 TB/s on this part) and the first cut of lnlin_fwd_kernel at 4.6.  The pieces of a

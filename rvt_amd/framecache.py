@@ -35,8 +35,8 @@ from . import _lib as L
 VERSION = 1
 GROUP_BYTES = 64
 SEGMENT_BYTES = 64 * GROUP_BYTES
-STATUS_CAPACITY, STATUS_INDEX, STATUS_COUNT = 1, 2, 4
-GATHER_COLS = 4                                                  # int64 columns of a gather table row: masks, seg_offset, values, count
+STATUS_CAPACITY, STATUS_INDEX, STATUS_COUNT = (L.ENUMS['RVT_FRAMES_STATUS_' + k] for k in ('CAPACITY', 'INDEX', 'COUNT'))
+GATHER_COLS = L.ENUMS['RVT_FRAMES_GATHER_COLS']                  # int64 columns of a gather table row: masks, seg_offset, values, count
 _DTYPES = {'uint8': torch.uint8, 'int8': torch.int8}
 
 
@@ -68,6 +68,19 @@ class PackedFrames:
     value_base: Tensor
     values: Tensor
     status: Tensor
+
+    @staticmethod
+    def empty(frame_shape: Sequence[int], dtype: torch.dtype, num_frames: int, capacity: int, device, pin: bool = False,
+              zero: bool = False) -> 'PackedFrames':
+        """A packed set with rows for num_frames frames and room for `capacity` value bytes; zero: every array zeroed (else only
+        allocated: status too); pin: in pinned host memory."""
+        F, (Gf, Sf) = num_frames, geometry(math.prod(frame_shape))
+
+        def make(*shape, dt):
+            t = (torch.zeros if zero else torch.empty)(*shape, dtype=dt, device=device)
+            return t.pin_memory() if pin else t
+        return PackedFrames(tuple(frame_shape), dtype, make(F, Gf, dt=torch.int64), make(F, Sf + 1, dt=torch.int32),
+                            make(F + 1, dt=torch.int64), make(capacity, dt=torch.uint8), make(1, dt=torch.int32))
 
     @property
     def num_frames(self) -> int:
@@ -254,15 +267,12 @@ def pack_frames(x: Tensor, capacity: Optional[int] = None, out: Optional[PackedF
     E, F = math.prod(frame_shape), math.prod(x.shape[:-3])
     if F < 1 or E < 1:
         raise ValueError(f'no bytes to pack in {tuple(x.shape)}')
-    Gf, Sf = geometry(E)
     dev = x.device
     if out is None:
         cap = F * E if capacity is None else int(capacity)
         if cap < 0:
             raise ValueError(f'capacity {cap} is negative')
-        out = PackedFrames(frame_shape, _DTYPES[name], torch.empty(F, Gf, dtype=torch.int64, device=dev),
-                           torch.empty(F, Sf + 1, dtype=torch.int32, device=dev), torch.empty(F + 1, dtype=torch.int64, device=dev),
-                           torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+        out = PackedFrames.empty(frame_shape, _DTYPES[name], F, cap, dev)
     else:
         if out.frame_shape != frame_shape or out.dtype != x.dtype or out.num_frames != F or out.device != dev:
             raise ValueError(f'out holds {out.num_frames} {out.dtype} frames {out.frame_shape} on {out.device}, x is {F} {x.dtype} frames '
@@ -280,6 +290,21 @@ def pack_frames(x: Tensor, capacity: Optional[int] = None, out: Optional[PackedF
     return out
 
 
+def _check_index(index: Tensor, dev) -> None:
+    if index.dtype != torch.int64 or index.device != dev or not index.is_contiguous():
+        raise ValueError(f'index must be a contiguous int64 tensor on {dev}')
+
+
+def _out_like(packed: PackedFrames, shape: Tuple[int, ...], out: Optional[Tensor]) -> Tensor:
+    """`out` checked against the shape an unpack gives, or a new tensor of it."""
+    dev = packed.device
+    if out is None:
+        return torch.empty(shape, dtype=packed.dtype, device=dev)
+    if tuple(out.shape) != shape or out.dtype != packed.dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f'out must be contiguous {packed.dtype} {shape} on {dev}')
+    return out
+
+
 def unpack_frames(packed: PackedFrames, index: Optional[Tensor] = None, out: Optional[Tensor] = None,
                   leading_shape: Optional[Sequence[int]] = None) -> Tensor:
     """Frames of `packed` by index -> a tensor of packed.dtype shaped leading_shape + frame_shape (leading_shape: index.shape, or
@@ -291,19 +316,14 @@ def unpack_frames(packed: PackedFrames, index: Optional[Tensor] = None, out: Opt
     if index is None:
         Fout = F
     else:
-        if index.dtype != torch.int64 or index.device != dev or not index.is_contiguous():
-            raise ValueError(f'index must be a contiguous int64 tensor on {dev}')
+        _check_index(index, dev)
         Fout = index.numel()
         if Fout < 1:
             raise ValueError('index is empty')
     lead = tuple(leading_shape) if leading_shape is not None else ((F,) if index is None else tuple(index.shape))
     if math.prod(lead) != Fout:
         raise ValueError(f'leading_shape {lead} does not hold the {Fout} frames asked for')
-    shape = lead + tuple(packed.frame_shape)
-    if out is None:
-        out = torch.empty(shape, dtype=packed.dtype, device=dev)
-    elif tuple(out.shape) != shape or out.dtype != packed.dtype or out.device != dev or not out.is_contiguous():
-        raise ValueError(f'out must be contiguous {packed.dtype} {shape} on {dev}')
+    out = _out_like(packed, lead + tuple(packed.frame_shape), out)
     n = packed.values.numel()
     L.call('rvt_frames_unpack', L.ptr(packed.masks), L.ptr(packed.seg_offset), L.ptr(packed.value_base),
            L.ptr(packed.values) if n else None, n, F, E, None if index is None else L.ptr(index), Fout, L.ptr(out), L.ptr(packed.status),
@@ -321,21 +341,17 @@ def unpack_augment(packed: PackedFrames, index: Tensor, planes_table: Tensor, ou
     dev = packed.device
     if len(packed.frame_shape) != 3:
         raise ValueError(f'frames must be (C, H, W) planes, the packed set holds {packed.frame_shape}')
-    if planes_table.dtype != torch.int32 or planes_table.dim() != 2 or planes_table.shape[1] != 8:
-        raise ValueError('planes_table must be int32 [B][8]')
+    cols = L.ENUMS['RVT_AUGMENT_PLANES_COLS']
+    if planes_table.dtype != torch.int32 or planes_table.dim() != 2 or planes_table.shape[1] != cols:
+        raise ValueError(f'planes_table must be int32 [B][{cols}]')
     if planes_table.device != dev or not planes_table.is_contiguous():
         raise ValueError(f'planes_table must be contiguous on {dev}')
     B = planes_table.shape[0]
-    if index.dtype != torch.int64 or index.device != dev or not index.is_contiguous():
-        raise ValueError(f'index must be a contiguous int64 tensor on {dev}')
+    _check_index(index, dev)
     if index.dim() != 2 or index.shape[1] != B or index.shape[0] < 1 or B < 1:
         raise ValueError(f'index must be (T, B={B}) like the rows of planes_table, got {tuple(index.shape)}')
     C, H, W = packed.frame_shape
-    shape = tuple(index.shape) + (C, H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=packed.dtype, device=dev)
-    elif tuple(out.shape) != shape or out.dtype != packed.dtype or out.device != dev or not out.is_contiguous():
-        raise ValueError(f'out must be contiguous {packed.dtype} {shape} on {dev}')
+    out = _out_like(packed, tuple(index.shape) + (C, H, W), out)
     n = packed.values.numel()
     L.call('rvt_frames_unpack_augment', L.ptr(packed.masks), L.ptr(packed.seg_offset), L.ptr(packed.value_base),
            L.ptr(packed.values) if n else None, n, F, E, L.ptr(index), index.numel(), L.ptr(planes_table), B, C, H, W, L.ptr(out),
@@ -448,11 +464,9 @@ class FrameGather:
 
     def empty(self, n: int, capacity: int) -> PackedFrames:
         """An uninitialised packed set on the device with rows for n frames and room for `capacity` value bytes."""
-        Gf, Sf = geometry(self.frame_bytes)
-        dev = self.device
-        return PackedFrames(self.frame_shape, self.dtype, torch.empty(n, Gf, dtype=torch.int64, device=dev),
-                            torch.empty(n, Sf + 1, dtype=torch.int32, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev),
-                            torch.empty(capacity, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        out = PackedFrames.empty(self.frame_shape, self.dtype, n, capacity, self.device)
+        out.status.zero_()
+        return out
 
 
 def gather_frames(stores: Sequence[PackedFrames], global_index, out: Optional[PackedFrames] = None) -> PackedFrames:

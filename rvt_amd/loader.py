@@ -280,24 +280,17 @@ class _Staging:
     """Host residency: a packed set of T * B frames on the device, sized for the densest frames of the stores, and what fills it:
     staging='copy' a pinned twin of the set, staging='gather' a pinned int64 [T * B][4] table and its device twin."""
 
-    def __init__(self, n_frames, E, frame_shape, dtype, cap, dev, pin, gather=False):
-        Gf, Sf = fc.geometry(E)
-
-        def host(*shape, dt):
-            t = torch.zeros(*shape, dtype=dt)
-            return t.pin_memory() if pin else t
-
-        def packed(make):
-            return PackedFrames(tuple(frame_shape), dtype, make(n_frames, Gf, dt=torch.int64), make(n_frames, Sf + 1, dt=torch.int32),
-                                make(n_frames + 1, dt=torch.int64), make(max(cap, 1), dt=torch.uint8), make(1, dt=torch.int32))
-        self.dev = packed(lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev))
+    def __init__(self, n_frames, frame_shape, dtype, cap, dev, pin, gather=False):
+        self.dev = PackedFrames.empty(frame_shape, dtype, n_frames, max(cap, 1), dev, zero=True)
         self.host = self.table_host = self.table_dev = None
         if gather:
-            self.table_host = host(n_frames * fc.GATHER_COLS, dt=torch.int64)
+            self.table_host = torch.zeros(n_frames * fc.GATHER_COLS, dtype=torch.int64)
+            if pin:
+                self.table_host = self.table_host.pin_memory()
             self.table_rows = self.table_host.numpy().reshape(n_frames, fc.GATHER_COLS)        # the same memory, for numpy to fill
             self.table_dev = torch.zeros(n_frames * fc.GATHER_COLS, dtype=torch.int64, device=dev)
         else:
-            self.host = packed(host)
+            self.host = PackedFrames.empty(frame_shape, dtype, n_frames, max(cap, 1), 'cpu', pin=pin, zero=True)
         self.ready = torch.cuda.Event() if dev.type == 'cuda' else None
 
 
@@ -386,7 +379,6 @@ class BatchLoader:
         self.stream_chunks = [streaming_chunks(a, b, self.T) for _, a, b in self.streams]
 
         dev = self.device
-        E = f0.frame_bytes
         self.parts = {}
         for name, b in ((DatasetSamplingMode.RANDOM, self.b_rnd), (DatasetSamplingMode.STREAM, self.b_str)):
             if b:
@@ -411,7 +403,7 @@ class BatchLoader:
             self.gather_blocks = 0                               # 0 = the library's default grid cap
             for p in self.parts.values():
                 n = self.T * p['B']
-                p['staging'] = [_Staging(n, E, self.frame_shape, self.dtype, n * cap, dev, pin, gather) for _ in range(2)]
+                p['staging'] = [_Staging(n, self.frame_shape, self.dtype, n * cap, dev, pin, gather) for _ in range(2)]
 
     # ---- orders ----
     def _generator(self) -> Optional[torch.Generator]:
@@ -489,13 +481,28 @@ class BatchLoader:
                 idx[:, b] = np.where(s.windows >= 0, s.windows + self.base[s.store], -1)
         return idx
 
-    def _stage(self, p: dict, idx: np.ndarray):
-        """Host residency: gather the frames the batch names into the pinned staging set and start its copy on the side stream.
-        Returns (staging set, local index)."""
-        st = p['staging'][p['flip']]
+    def _staging_set(self, p: dict, idx: np.ndarray):
+        """(the staging set this batch fills, the global numbers of the frames it names, the index into them)."""
         need = np.unique(idx[idx >= 0])
         local = np.full_like(idx, -1)
         local[idx >= 0] = np.searchsorted(need, idx[idx >= 0])
+        return p['staging'][p['flip']], need, local
+
+    def _on_side_stream(self, st: '_Staging', fill) -> None:
+        """fill(non_blocking) on the side stream, behind the set's previous reader on the current stream, and st.ready behind it;
+        without a side stream (the CPU emulator) fill runs at once."""
+        if self.side is None:
+            fill(False)
+            return
+        self.side.wait_stream(torch.cuda.current_stream(self.device))            # the set's previous reader is done
+        with torch.cuda.stream(self.side):
+            fill(True)
+            st.ready.record(self.side)
+
+    def _stage(self, p: dict, idx: np.ndarray):
+        """Host residency: gather the frames the batch names into the pinned staging set and start its copy on the side stream.
+        Returns (staging set, local index)."""
+        st, need, local = self._staging_set(p, idx)
         runs, at = [], 0
         while at < len(need):                                    # runs of consecutive frames of one store: one slice each
             k = int(np.searchsorted(self.base, need[at], side='right')) - 1
@@ -512,39 +519,28 @@ class BatchLoader:
             h.seg_offset[:n].copy_(g.seg_offset)
             h.value_base[:n + 1].copy_(g.value_base)
             h.values[:nv].copy_(g.values)
-        if self.side is not None:
-            self.side.wait_stream(torch.cuda.current_stream(self.device))        # the set's previous reader is done
-            with torch.cuda.stream(self.side):
-                for d, s in zip((st.dev.masks, st.dev.seg_offset, st.dev.value_base, st.dev.values), (h.masks, h.seg_offset, h.value_base, h.values)):
-                    d.copy_(s, non_blocking=True)
-                st.ready.record(self.side)
-        else:
+
+        def fill(non_blocking):
             for d, s in zip((st.dev.masks, st.dev.seg_offset, st.dev.value_base, st.dev.values), (h.masks, h.seg_offset, h.value_base, h.values)):
-                d.copy_(s)
+                d.copy_(s, non_blocking=non_blocking)
+        self._on_side_stream(st, fill)
         return st, local
 
     def _stage_gather(self, p: dict, idx: np.ndarray):
         """Host residency, staging='gather': one table row per frame the batch names, and one gather launch on the side stream that
         fetches them from the pinned stores into the device set.  Returns (staging set, local index)."""
-        st = p['staging'][p['flip']]
-        need = np.unique(idx[idx >= 0])
-        local = np.full_like(idx, -1)
-        local[idx >= 0] = np.searchsorted(need, idx[idx >= 0])
+        st, need, local = self._staging_set(p, idx)
         n = len(need)
         if st.ready is not None:
             st.ready.synchronize()                               # the table's previous copy has left the pinned buffer (long done: no wait)
         if n:
             self.gatherer.table(need, out=st.table_rows)
-        if self.side is not None:
-            self.side.wait_stream(torch.cuda.current_stream(self.device))        # the set's previous reader is done
-            with torch.cuda.stream(self.side):
-                if n:
-                    st.table_dev[:n * fc.GATHER_COLS].copy_(st.table_host[:n * fc.GATHER_COLS], non_blocking=True)
-                    self.gatherer.launch(st.table_dev, n, st.dev, self.gather_blocks)
-                st.ready.record(self.side)
-        elif n:
-            st.table_dev[:n * fc.GATHER_COLS].copy_(st.table_host[:n * fc.GATHER_COLS])
-            self.gatherer.launch(st.table_dev, n, st.dev, self.gather_blocks)
+
+        def fill(non_blocking):
+            if n:
+                st.table_dev[:n * fc.GATHER_COLS].copy_(st.table_host[:n * fc.GATHER_COLS], non_blocking=non_blocking)
+                self.gatherer.launch(st.table_dev, n, st.dev, self.gather_blocks)
+        self._on_side_stream(st, fill)
         return st, local
 
     def _plan(self, part: DatasetSamplingMode, samples: List[Sample]) -> dict:

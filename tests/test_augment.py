@@ -164,9 +164,11 @@ def _random_labels(r, T, B, G, H, W):
     return torch.from_numpy(rows), torch.from_numpy(count)
 
 
-# (seed, T, B, C, H, W, G): W % 16 != 0 (byte path), W % 16 == 0 (16-byte path), B = 1, G = 1, W across the 256-column LDS skew
+# (seed, T, B, C, H, W, G): W % 16 != 0 (byte path), W % 16 == 0 (16-byte path), B = 1, G = 1, W across the 256-column LDS skew,
+# the largest supported W on the 16-byte path and the widest row on the byte path
 RANDOM_SHAPES = [(0, 2, 3, 2, 17, 23, 3), (1, 1, 4, 3, 40, 64, 5), (2, 3, 1, 2, 24, 48, 1), (3, 1, 5, 1, 9, 304, 4),
-                 (4, 2, 6, 2, 33, 528, 2), (5, 1, 2, 20, 20, 100, 6), (6, 1, 4, 1, 70, 16, 1)]
+                 (4, 2, 6, 2, 33, 528, 2), (5, 1, 2, 20, 20, 100, 6), (6, 1, 4, 1, 70, 16, 1), (7, 1, 3, 1, 3, 2048, 2),
+                 (8, 2, 2, 1, 5, 2047, 1)]
 
 
 @pytest.mark.parametrize('seed,T,B,C,H,W,G', RANDOM_SHAPES)

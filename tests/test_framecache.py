@@ -133,6 +133,37 @@ def test_round_trip_with_indices(backend, E):
     assert tuple(flat.shape) == (2, 6) + SHAPES[E] and np.array_equal(flat.cpu().numpy().reshape(idx.size, E), want)
 
 
+# ---- 3b. more than one tile of the 256-wide scans ------------------------------------------------------------------------------------
+# (F, frame shape, fill): value_base over three tiles with a ragged last one; one frame past a tile; Sf = 258 (two tiles of the
+# segment scan, and the largest per-frame run at full fill); Sf = 513 (three tiles, ragged by one)
+TILE_CASES = [(600, (2, 3, 5), 0.5), (257, (1, 1, 64), 1.0), (2, (1, 257, 4100), 0.05), (2, (1, 257, 4100), 1.0), (1, (1, 513, 4096), 0.5)]
+
+
+@functools.lru_cache(maxsize=None)
+def _tile_case(F, shape, fill):
+    """(frames uint8 [F][E], their reference encoding); computed once per case, never written to."""
+    E = int(np.prod(shape))
+    rng = np.random.default_rng(17 * F + E)
+    x = rng.integers(1, 256, size=(F, E), dtype=np.uint8)
+    if fill < 1.0:
+        x *= rng.random((F, E)) < fill
+    x.setflags(write=False)
+    return x, ref.encode(x)
+
+
+@pytest.mark.parametrize('F,shape,fill', TILE_CASES, ids=[f'F{F}-{"x".join(map(str, s))}-{int(100 * fl)}' for F, s, fl in TILE_CASES])
+def test_scan_tiles(backend, F, shape, fill):
+    x, want = _tile_case(F, shape, fill)
+    E = x.shape[1]
+    assert fc.geometry(E)[1] > 256 or F > 256                                        # a second tile in one of the scans
+    p = pack_frames(torch.from_numpy(x.copy()).reshape((F,) + shape).to(backend))
+    _assert_same(_arrays(p), want)
+    perm = np.random.default_rng(F).permutation(F)
+    y = unpack_frames(p, torch.from_numpy(perm).to(backend))
+    assert np.array_equal(y.cpu().numpy().reshape(F, E), x[perm])
+    p.check()
+
+
 # ---- 4. the reference-built fixtures; slice / concat -----------------------------------------------------------------------------------
 @pytest.mark.parametrize('name', FIXTURES)
 def test_round_trip_on_fixture(backend, name):

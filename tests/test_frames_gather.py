@@ -13,7 +13,7 @@ from rvt_amd import _header, _lib, framecache as fc
 from rvt_amd.framecache import FrameGather, PackedFrames, gather_frames, unpack_frames
 from tests import framecache_ref as ref
 from tests.backends import backend  # noqa: F401
-from tests.test_framecache import SHAPES, _edge_frames, _packed_from
+from tests.test_framecache import SHAPES, TILE_CASES, _edge_frames, _packed_from, _tile_case
 
 DTYPES = {'uint8': (np.uint8, torch.uint8), 'int8': (np.int8, torch.int8)}
 CANARY = 0x5A
@@ -122,6 +122,22 @@ def test_alignment_sweep(backend):
     assert {int(cnt[i]) for i in idx} >= {0, 1, 15, 16, 17, 31, 33, 4097}
     _assert_set(got, want)
     assert np.array_equal(unpack_frames(got).cpu().numpy().reshape(len(idx), -1), x[idx])
+
+
+# ---- 2b. more rows than one tile of the scan; seg_offset rows of more than one tile ---------------------------------------------------
+@pytest.mark.parametrize('F,shape,fill', TILE_CASES[:1] + TILE_CASES[2:4], ids=['F600', 'Sf258-5', 'Sf258-100'])
+def test_gather_every_frame_reversed(backend, F, shape, fill):
+    x, enc = _tile_case(F, shape, fill)
+    store = _packed_from(enc, shape, torch.uint8, backend)
+    idx = np.arange(F)[::-1].copy()
+    got = gather_frames([store], idx)
+    assert got.num_frames == F
+    got.check()
+    counts = np.diff(enc['value_base'])[idx]
+    assert np.array_equal(got.value_base.cpu().numpy(), np.concatenate(([0], np.cumsum(counts))))
+    assert torch.equal(got.masks.cpu(), store.masks.cpu()[idx]) and torch.equal(got.seg_offset.cpu(), store.seg_offset.cpu()[idx])
+    assert np.array_equal(unpack_frames(got).cpu().numpy().reshape(F, -1), x[idx])
+    got.check()
 
 
 # ---- 3. capacity, bad counts and the write discipline -------------------------------------------------------------------------------

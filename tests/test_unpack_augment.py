@@ -5,7 +5,8 @@ Truth is two restatements that are not under test: the numpy decoder of the form
 plain-torch augmentation (tests/augment_ref.py).  Every comparison is for exact equality.  The shapes are the smallest at which an
 edge can go wrong: less than a segment (2 x 12 x 16), the smallest shape the builders emit (20 x 12 x 16), rows on group boundaries
 (1 x 8 x 640), the Gen1 width whose rows start inside a group and straddle segments on the 16-byte path (2 x 40 x 304), and the
-byte path with rows at every alignment and E no multiple of 64 (3 x 23 x 359)."""
+byte path with rows at every alignment and E no multiple of 64 (3 x 23 x 359), the largest supported W on the 16-byte path
+(1 x 3 x 2048) and the widest row on the byte path (1 x 5 x 2047)."""
 import functools
 import os
 
@@ -22,7 +23,7 @@ from tests.backends import backend  # noqa: F401
 from tests.harness import load_golden
 from tests.test_framecache import _edge_frames
 
-SHAPES = [(2, 12, 16), (20, 12, 16), (1, 8, 640), (2, 40, 304), (3, 23, 359)]
+SHAPES = [(2, 12, 16), (20, 12, 16), (1, 8, 640), (2, 40, 304), (3, 23, 359), (1, 3, 2048), (1, 5, 2047)]
 FILLS = {'empty': 0.0, 'sparse': 0.01, 'half': 0.5, 'full': 1.0}
 F_PACKED = 4
 
