@@ -43,6 +43,31 @@ attn_half - [LN ->] qkv -> softmax(Q K^T) V -> proj * gamma + residual       (at
     `handover_bf16` is the two-launch route the PRE kernel replaces: dx = dxmid + du stored in bf16 (:693), then ln_bwd_kernel
     (rowops.hpp:59-116: fp32 sums of the bf16 rows).
 
+attn_core - softmax(Q K^T) V on a saved qkv tensor: q, k, v, dO are the stored bf16 values, no bias anywhere    (attn_core2.hpp; the
+    helpers of attn.hpp :64-76 and attn_block.hpp :371-380 convert; the transposes by identity MFMA, :26-33, are exact)
+    forward  the UN-normalised exp(scale (s - max)) as the P V operand        :96 (staged :184);   out stored :105 (staged :193)
+    backward P = softmax in fp32 (normalised, :276 / :419) through the LDS tile for dV          :285 (staged :428)
+             dS = P (dP - delta) scale through the LDS tile for dK, from the registers for dQ   :286 :293 (staged :429 :436)
+             dq, dk, dv stored                                                :249 (staged :388)
+    `_softmax_bwd` is this backward and that of attn_half: the two kernels differ in where q, k, v, dO come from, not in the softmax.
+
+lstm - ConvLSTM cell with a 1x1 conv, T steps, and its BPTT.  z = [x | h] W^T + b accumulates in fp32, the gates and c_t stay fp32.
+    h_t rounded where it is stored; the stored value is the next step's operand (`h_bf16`)
+             gemm.hpp:715 (per step)  lstm_scan.hpp:199  lstm_scan2.hpp:203 (s2_pack)  lstm_scan3.hpp:172
+    c_t copy for the backward (`c`, returned before its rounding)    lstm_scan.hpp:200  lstm_scan2.hpp:214  lstm_scan3.hpp:181;  c_last stays fp32
+    activated gates saved for the backward (`gates`, before rounding)  gemm.hpp:718-721  lstm_scan.hpp:202-205 (W_REG)  lstm_scan3.hpp:177-180
+    backward, `saved_gates`: f, i, o, g read back from that save      rowops.hpp:244-247  lstm_scan.hpp:447-450 (GATES)  lstm_scan3.hpp:286-289
+             off: recomputed in fp32 from x_t and the stored h_{t-1}  lstm_scan.hpp:452-455  lstm_scan2.hpp:497-500
+    backward, `c_bf16`: c_{t-1} from the bf16 save, the incoming fp32 c0 converted the same way, tanh(c_t) of f c_{t-1} + i g rebuilt from it
+             lstm_scan.hpp:323-324 :457 :459  lstm_scan2.hpp:449 :460 :503  lstm_scan3.hpp:291 :296 :304
+             off: c_t and c_{t-1} are the forward's fp32 tensors      rowops.hpp:250-251 :254
+    `dz_bf16`: dz, the operand of [dx | dh] = dz W and of dW = dz^T [x | h], and a stored output
+             rowops.hpp:263-266  lstm_scan.hpp:463-466  lstm_scan2.hpp:515-516  lstm_scan3.hpp:306-309
+    `db_bf16`: db from the rounded dz - lstm_scan2.hpp:366 :389 (product against ones), and every test that sums the stored dz itself;
+             off: lstm_scan.hpp:467 sums the fp32 values
+    dx_t stored (lstm_scan.hpp:516, lstm_scan2.hpp:594, lstm_scan3.hpp:348); dh_{t-1} and dc stay in fp32 registers across the steps
+    (lstm_scan.hpp:517, lstm_scan2.hpp:591, lstm_scan3.hpp:349); dh0 stored, dc0 fp32.
+
 dgrad_ln - dx = add + LN'(dy W; x) and, `inside`, dx = LN'(dy W + add; x)     (dgrad_ln.hpp)
     du (+ add) rounded "as the two-launch chain stores it"                    :184 - AFTER the row sums s1 / s2 took the fp32 values (:180-182)
     du * xhat before the column sums (du itself is already bf16)              :244-245;   dx stored :213
@@ -142,6 +167,45 @@ def _from_parts(t, Fr, H, W, ph, pw, window):
     return t.reshape(Fr, H, W, c)
 
 
+def _split_heads(qkv, heads, dh):
+    """(partitions, L, 3C) with the channels of a head as [q | k | v] (maxvit.py:347) -> [3][partitions][heads][L][dh]."""
+    return qkv.reshape(qkv.shape[0], qkv.shape[1], heads, 3, dh).permute(3, 0, 2, 1, 4)
+
+
+def _softmax_bwd(q, k, v, dO, scale, r):
+    """q, k, v, dO [partitions][heads][L][dh] -> dqkv (partitions, L, 3C): P = softmax(scale Q K^T) in fp32 (normalised),
+    dS = P (dP - delta) scale; P and dS are MFMA operands (`r`), the three products accumulate in fp32."""
+    p = torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1)
+    dp = dO @ v.transpose(-1, -2)
+    ds = p * (dp - (p * dp).sum(-1, keepdim=True)) * scale
+    pr, dsr = r(p), r(ds)
+    dq, dk, dv = dsr @ k, dsr.transpose(-1, -2) @ q, pr.transpose(-1, -2) @ dO
+    NP, heads, L, dh = q.shape
+    return torch.stack([dq, dk, dv], 0).permute(1, 3, 2, 0, 4).reshape(NP, L, 3 * heads * dh)
+
+
+def attn_core(qkv, dout, geom, *, rounding=True, dtype=torch.float32):
+    """The attention core on a saved qkv tensor (rvt_attn_fwd / rvt_attn_bwd): qkv (F, H, W, 3C) with the biases already in it, dout
+    (F, H, W, C) or None; geom = (F, H, W, C, dim_head, ph, pw, window) -> dict of out and (dout given) dqkv.  q, k, v and dO are the
+    bf16 tensors as stored: the only conversions are the softmax operands."""
+    Fr, H, W, C, dh, ph, pw, window = geom
+    heads, scale = C // dh, dh ** -0.5
+    qkv, dout = _prep(dtype, qkv, dout)
+    r = lambda t: _r(t, rounding)
+    part = lambda t: _to_parts(t.reshape(Fr, H, W, -1), Fr, H, W, ph, pw, window)
+    back = lambda t: _from_parts(t, Fr, H, W, ph, pw, window)
+    q, k, v = _split_heads(part(qkv), heads, dh)
+    NP, L = q.shape[0], q.shape[2]
+    s = (q @ k.transpose(-1, -2)) * scale
+    e = torch.exp(s - s.max(-1, keepdim=True).values)
+    o = (r(e) @ v) / e.sum(-1, keepdim=True)
+    out = dict(out=back(o.permute(0, 2, 1, 3).reshape(NP, L, C)))
+    if dout is not None:
+        dO = part(dout).reshape(NP, L, heads, dh).permute(0, 2, 1, 3)
+        out['dqkv'] = back(_softmax_bwd(q, k, v, dO, scale, r))
+    return out
+
+
 def attn_half(x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm, geom, eps=1e-5, *, y0=None, rounding=True, dtype=torch.float32,
               handover_bf16=False):
     """geom = (F, H, W, C, dim_head, ph, pw, window).  ln_w None: no norm1.  y0 given (with ln_w = the weight of the norm in FRONT
@@ -165,7 +229,7 @@ def attn_half(x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm, geom, eps=1e
     else:
         ur = xt
     NP, L = xt.shape[0], xt.shape[1]
-    qkv = (ur @ wqkv.t()).reshape(NP, L, heads, 3, dh).permute(3, 0, 2, 1, 4)            # [3][NP][heads][L][dh], no bias yet
+    qkv = _split_heads(ur @ wqkv.t(), heads, dh)                                         # [3][NP][heads][L][dh], no bias yet
     bq, _, bv = bqkv.reshape(heads, 3, dh).permute(1, 0, 2)[:, None, :, None, :]        # [3] x [1][heads][1][dh]; the k bias is dropped
     # ---- forward (attn_block_fwd_kernel)
     q, k, v = r(qkv[0] + bq), r(qkv[1]), r(qkv[2])
@@ -181,13 +245,7 @@ def attn_half(x, ln_w, ln_b, wqkv, bqkv, wp, bp, gamma, wpg_t, dxm, geom, eps=1e
     dt_ = part(dxm)
     wpg = wpg_t.t() if rounding else gamma[:, None] * wp                                 # [c][a]
     dO = r(dt_ @ wpg).reshape(NP, L, heads, dh).permute(0, 2, 1, 3)
-    q, k, v = r(qkv[0] + bq), r(qkv[1]), r(qkv[2] + bv)
-    p = torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1)
-    dp = dO @ v.transpose(-1, -2)
-    ds = p * (dp - (p * dp).sum(-1, keepdim=True)) * scale
-    pr, dsr = r(p), r(ds)
-    dq, dk, dv = dsr @ k, dsr.transpose(-1, -2) @ q, pr.transpose(-1, -2) @ dO
-    dqkv = torch.stack([dq, dk, dv], 0).permute(1, 3, 2, 0, 4).reshape(NP, L, 3 * C)
+    dqkv = _softmax_bwd(r(qkv[0] + bq), r(qkv[1]), r(qkv[2] + bv), dO, scale, r)
     out['dqkv'] = back(dqkv)
     du = r(dqkv) @ wqkv
     if pre or ln_w is not None:
@@ -245,6 +303,64 @@ def dgrad_ln(dy, w, x, add, lw, eps=1e-5, *, inside=False, fused=True, rounding=
     if fused:
         return dict(dx=res + _ln_bwd(dur, xhat, rstd, lw, stats_from=du), dln_w=r(dur * xhat).sum(0), dln_b=dur.sum(0))
     return dict(dx=res + _ln_bwd(dur, xhat, rstd, lw), dln_w=(dur * xhat).sum(0), dln_b=dur.sum(0))
+
+
+# --------------------------------------------------------------------------------------------------------------- ConvLSTM
+def lstm(x, h0, c0, w, b, dH=None, dc_last=None, *, rounding=True, dtype=torch.float32, saved_gates=False, c_bf16=True,
+         dz_bf16=True, h_bf16=True, db_bf16=False):
+    """The 1x1-conv ConvLSTM (rnn.py:52-67) over T steps and its BPTT.  x [T][M][C], h0 [M][C], c0 [M][C] or None (zeros), w [4C][2C]
+    in the natural gate order f, i, o, g and input order [x | h], b [4C]; dH [T][M][C] and dc_last [M][C] (None = zeros).
+    -> dict of h, c [T][M][C], c_last, gates [T][M][4C] and (dH or dc_last given) dz [T][M][4C], dx, dh0, dc0, dW, db.
+    What differs between the kernels:
+      saved_gates  the backward reads the activated gates from the forward's bf16 save instead of recomputing them in fp32
+      c_bf16       the backward reads c_{t-1} as bf16 (Csave; the incoming fp32 c0 is converted the same way) and rebuilds
+                   c_t = f c_{t-1} + i g from it; off: both cell states are the forward's fp32 tensors (per-step kernels)
+      dz_bf16      dz is the bf16 operand of [dx | dh] = dz W and of dW = dz^T [x | h]
+      h_bf16       h_t is rounded where it is stored, and the stored value is the next step's operand
+      db_bf16      db sums the ROUNDED dz (a product against ones, or the test's own sum of the stored dz) instead of the fp32 values"""
+    x, h0, c0, w, b, dH, dc_last = _prep(dtype, x, h0, c0, w, b, dH, dc_last)
+    r = lambda t: _r(t, rounding)
+    T, M, C = x.shape
+    c = torch.zeros(M, C, dtype=dtype) if c0 is None else c0
+    c_in, h = c, h0
+    hs, cs, gs, hin = [], [], [], []
+    for t in range(T):
+        hin.append(h)
+        z = torch.cat([x[t], h], -1) @ w.t() + b
+        f, i, o, g = torch.sigmoid(z[:, :C]), torch.sigmoid(z[:, C:2 * C]), torch.sigmoid(z[:, 2 * C:3 * C]), torch.tanh(z[:, 3 * C:])
+        c = f * c + i * g
+        hn = o * torch.tanh(c)
+        hs.append(hn)
+        cs.append(c)
+        gs.append(torch.cat([f, i, o, g], -1))
+        h = r(hn) if h_bf16 else hn
+    out = dict(h=torch.stack(hs), c=torch.stack(cs), c_last=c, gates=torch.stack(gs))
+    if dH is None and dc_last is None:
+        return out
+    dh_rec = torch.zeros(M, C, dtype=dtype)
+    dc_rec = torch.zeros(M, C, dtype=dtype) if dc_last is None else dc_last
+    dzs, dxs = [None] * T, [None] * T
+    dW, db = torch.zeros_like(w), torch.zeros_like(b)
+    for t in range(T - 1, -1, -1):
+        f, i, o, g = (r(gs[t]) if saved_gates else gs[t]).split(C, -1)
+        cp = cs[t - 1] if t > 0 else c_in
+        if c_bf16:
+            cp = r(cp)
+            cn = f * cp + i * g
+        else:
+            cn = cs[t]
+        dh = dh_rec if dH is None else dH[t] + dh_rec
+        tc = torch.tanh(cn)
+        dc = dc_rec + dh * o * (1.0 - tc * tc)
+        dz = torch.cat([dc * cp * f * (1.0 - f), dc * g * i * (1.0 - i), dh * tc * o * (1.0 - o), dc * i * (1.0 - g * g)], -1)
+        dc_rec = dc * f
+        dzr = r(dz) if dz_bf16 else dz
+        dxh = dzr @ w
+        dxs[t], dh_rec, dzs[t] = dxh[:, :C], dxh[:, C:], dz
+        dW = dW + dzr.t() @ torch.cat([x[t], hin[t]], -1)
+        db = db + (r(dz) if db_bf16 else dz).sum(0)
+    out.update(dz=torch.stack(dzs), dx=torch.stack(dxs), dh0=dh_rec, dc0=dc_rec, dW=dW, db=db)
+    return out
 
 
 def conv_fwd(x, w, stride, pad, *, rounding=True, dtype=torch.float32):

@@ -19,7 +19,8 @@ e_y = max|model - truth|:
         outputs stored in bf16, per element: |ours - truth| <= 2^-8 |truth| + slack          (one bf16 ulp: tests/test_bnact.py)
 factor = 2 (tests/test_optim.py) where the kernel differs from the model only in the order of its operations - the MLP, LayerNorm and
 linear families; 4 (tests/test_bnact.py) for tensors downstream of a hardware exp2 or reciprocal - the attention softmax outputs and
-their gradients.  No measured term anywhere.  A comparison of two kernels gets the SUM of the two sides' ceilings against their common
+their gradients (the fused half and the core of stages 2 - 4), and everything of the ConvLSTM cell and scans (sigmoid / tanh gates).
+No measured term anywhere.  A comparison of two kernels gets the SUM of the two sides' ceilings against their common
 truth (triangle inequality).  The table check runs as well, unchanged; both must hold, so the ceiling never loosens anything, and
 where a check has no entry the ceiling is itself capped by the old 2e-2.
   * Outside record mode a bf16 check with neither a table entry nor a ceiling RAISES: nothing falls back silently.

@@ -374,8 +374,18 @@ ATTN_CASES = [  # F, H, W, C, dh, ph, pw
     (1, 8, 20, 32, 32, 8, 10),     # L=80  (NB=3), Gen1 partition
     (1, 4, 6, 48, 24, 2, 3),       # dim_head 24 (RVT-Small)
     (1, 6, 10, 16, 8, 6, 10),      # dim_head 8, one partition per frame
+    # the widths the stages 2 - 4 run at (dim_head 32: capi_attn.hip groups 4 / 2 / 1 heads per workgroup) and the grid dilations of 1 Mpx
+    (1, 12, 20, 128, 32, 6, 10),   # 4 heads: one workgroup of four
+    (1, 12, 20, 512, 32, 6, 10),   # 16 heads, stage 4 at 1 Mpx
+    (2, 24, 40, 256, 32, 6, 10),   # 8 heads, grid dilation 4 x 4, two frames
+    (1, 48, 80, 128, 32, 6, 10),   # grid dilation 8 x 8
+    (1, 96, 160, 64, 32, 6, 10),   # grid dilation 16 x 16
+    (3, 18, 20, 128, 32, 6, 10),   # 3 x 2 partitions, odd frame count
+    (2, 16, 20, 128, 32, 8, 10),   # Gen1 partitions, L=80 (NB=3): the LDS budget decides the head group
+    (1, 32, 40, 64, 32, 8, 10),    # Gen1 partitions, grid dilation 4 x 4
+    (5, 8, 10, 256, 32, 8, 10),    # one partition per frame
+    (1, 12, 20, 96, 32, 6, 10),    # 3 heads: no grouping
 ]
-
 
 @pytest.mark.parametrize('dt', DTYPES)
 @pytest.mark.parametrize('window', [True, False])
@@ -387,10 +397,12 @@ def test_attention(backend, dt, window, case):
     out = ops.attn_fwd(qkv, Fr, H, W, C, dh, ph, pw, window)
     qr = f64(qkv).requires_grad_(True)
     want = ref_attention(qr, Fr, H, W, C, dh, ph, pw, window)
-    close(out, want, dt, 'attn_fwd')
     want.backward(f64(dout))
+    # the rounding model of the core (attn.hpp / attn_core2.hpp); both outputs are downstream of the hardware exp2 and reciprocal
+    m = modelled(bf16_model.attn_core, dict(out=want, dqkv=qr.grad), dt, qkv, dout, (Fr, H, W, C, dh, ph, pw, window))
+    close(out, want, dt, 'attn_fwd', model=part(m, 'out'), factor=4)
     dq = ops.attn_bwd(qkv, dout, Fr, H, W, C, dh, ph, pw, window)
-    close(dq, qr.grad, dt, 'attn_bwd', f32_mult=2.0)
+    close(dq, qr.grad, dt, 'attn_bwd', f32_mult=2.0, model=part(m, 'dqkv'), factor=4)
     if dt == torch.bfloat16:
         # rows staged through LDS (whole-line requests) against the direct kernels: the same arithmetic on the same values
         with tuning.override(attn_staged=0):
@@ -521,7 +533,7 @@ def test_attn_block_bwd_preln(backend, dt, window, case):
 
 
 @pytest.mark.parametrize('dt', DTYPES)
-@pytest.mark.parametrize('M,C', [(150, 16), (70, 72)])
+@pytest.mark.parametrize('M,C', [(150, 16), (70, 72), (129, 512), (33, 256), (65, 32)])      # C = 512: the width the per-step cell serves
 def test_lstm_cell(backend, dt, M, C):
     x, h = rnd((M, C), backend, dt, 1), rnd((M, C), backend, dt, 2)
     c = rnd((M, C), backend, torch.float32, 3)
@@ -536,34 +548,45 @@ def test_lstm_cell(backend, dt, M, C):
     xr, hr, cr = f64(x).requires_grad_(True), f64(h).requires_grad_(True), f64(c).requires_grad_(True)
     wr, br = f64(w_t).requires_grad_(True), f64(b)
     mix = torch.cat([xr, hr], 1) @ wr.t() + br
+    mix.retain_grad()
     fg, ig, og = torch.sigmoid(mix[:, :C]), torch.sigmoid(mix[:, C:2 * C]), torch.sigmoid(mix[:, 2 * C:3 * C])
     gg = torch.tanh(mix[:, 3 * C:])
     cn = fg * cr + ig * gg
     hn = og * torch.tanh(cn)
-    close(c_out, cn, dt, 'lstm c')
-    close(h_out, hn, dt, 'lstm h')
-    close(gates, torch.cat([fg, ig, og, gg], 1), dt, 'lstm gates')
+    gates_r = torch.cat([fg, ig, og, gg], 1)
     # backward of one step with incoming dh (two parts) and dc
     dh_in, dh_rec = rnd((M, C), backend, dt, 6), rnd((M, C), backend, dt, 7)
     dc_rec = rnd((M, C), backend, torch.float32, 8)
     (hn * (f64(dh_in) + f64(dh_rec))).sum().backward(retain_graph=True)
     (cn * f64(dc_rec)).sum().backward()
+    # the rounding model: one step of tests/bf16_model.py `lstm` as the per-step kernels run it - the gates come back from their bf16
+    # save, both cell states are the fp32 tensors (rowops.hpp lstm_gates_bwd_kernel); factor 4: everything is downstream of the
+    # hardware exp2 / reciprocal of the gate activations (gemm.hpp EpLstm)
+    truth = dict(h=hn[None], c=cn[None], gates=gates_r[None], dz=mix.grad[None], dx=xr.grad[None], dh0=hr.grad, dc0=cr.grad,
+                 dW=wr.grad, db=mix.grad.sum(0))
+    m = modelled(bf16_model.lstm, truth, dt, x[None], h, c, w_t, b, (f64(dh_in) + f64(dh_rec))[None], dc_rec, saved_gates=True, c_bf16=False)
+    close(c_out, cn, dt, 'lstm c', model=part(m, 'c_last'), factor=4)
+    close(h_out, hn, dt, 'lstm h', model=None if m is None else m['h'][0], factor=4)
+    close(gates, gates_r, dt, 'lstm gates', model=None if m is None else m['gates'][0], factor=4)
     dz = torch.empty(M, 4 * C, dtype=dt, device=backend)
     dc_io = dc_rec.clone()
     # the kernel consumes the *saved* (rounded) gates and fp32 cell states
     ops.lstm_gates_bwd(dh_in, dh_rec, dc_io, gates, c_out, c, dz)
-    close(dc_io, cr.grad, dt, 'lstm dc_prev', f32_mult=2.0)
+    close(dc_io, cr.grad, dt, 'lstm dc_prev', f32_mult=2.0, model=part(m, 'dc0'), factor=4)
     dx = torch.empty(M, C, dtype=dt, device=backend)
     dhp = torch.empty(M, C, dtype=dt, device=backend)
     ops.lstm_dgrad(dz, w_t.t().contiguous(), dx, dhp)
-    close(dx, xr.grad, dt, 'lstm dx', f32_mult=2.0)
-    close(dhp, hr.grad, dt, 'lstm dh_prev', f32_mult=2.0)
+    close(dx, xr.grad, dt, 'lstm dx', f32_mult=2.0, model=None if m is None else m['dx'][0], factor=4)
+    close(dhp, hr.grad, dt, 'lstm dh_prev', f32_mult=2.0, model=part(m, 'dh0'), factor=4)
     ops.lstm_dgrad(dz, w_t.t().contiguous(), dx, dhp)
     dw = torch.zeros(4 * C, 2 * C, device=backend)
     dbias = torch.zeros(4 * C, device=backend)
     ops.lstm_wgrad(dz, x, h, dw, dbias)
-    close(dw, wr.grad, dt, 'lstm dw', f32_mult=2.0)
-    close(dbias, f64(dz).sum(0), dt, 'lstm dbias (fused column sum)', f32_mult=1.0)
+    close(dw, wr.grad, dt, 'lstm dw', f32_mult=2.0, model=part(m, 'dW'), factor=4)
+    # the fused column sum against the sum of the kernel's own dz: fp32 accumulation of bf16 values, no rounding point (`wgrad`)
+    colsum = f64(dz).sum(0)
+    mc = modelled(bf16_model.wgrad, dict(colsum=colsum), dt, dz, torch.cat([x, h], 1))
+    close(dbias, colsum, dt, 'lstm dbias (fused column sum)', f32_mult=1.0, model=part(mc, 'colsum'), factor=4)
 
 
 CONV_CASES = [  # F, H, W, Cin, Cout, k, s, p
