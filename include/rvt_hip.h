@@ -94,7 +94,7 @@ typedef struct RvtTuning {
     int conv_wgrad_tn;        /* 1 (round 5): conv weight gradients with Cout % 256 == 0, Cin % 64 == 0 and k*k*Cin >= 256 take ppgemm_tn.hpp (im2col gather by LDS-DMA; the last 256-wide k tile may lie partly beyond K) */
     int attn_staged;          /* 1 (round 5): the partition-attention core of stages 2-4 stages its rows through LDS (whole-line requests) where built */
     int lstm_scan3;           /* round 6: ConvLSTM (bf16, dws_conv False) with the time loop in the kernel, weights streamed from L2 in operand order, gates saved for the reverse scan (lstm_scan3.hpp): bit 0 = at C 256, bit 1 = at C 128 (instead of lstm_scan.hpp's register-resident weights) */
-    int lstm_scan3_rb256;     /* 32-token blocks per workgroup tile of that forward at C = 256: 1 or 2 */
+    int lstm_scan3_rb256;     /* 32-token blocks per workgroup tile of that forward at C = 256: 2 forces 64-token tiles, 1 leaves a stage's choice to rvt_stage_routes (by tokens per step) */
     int lstm_scan3_rb128;     /* ... at C = 128 */
     int route_stage_driver_train; /* 1 (round 6): the training forward / backward of a stage take rvt_stage_seq_train_fwd / rvt_stage_seq_bwd (one call per stage and direction) where covered; 0: the Python host loop */
     int route_attn_preln;     /* 1 (round 6): the backward of a stage's first block also carries the gradient through the down-sampling LayerNorm where no token mask sits between them: rvt_attn_block_bwd_preln on the fused attention half, rvt_linear_dgrad_preln on the op-by-op route (C <= 128); 0: separate rvt_layernorm_bwd */
@@ -333,8 +333,8 @@ int rvt_lstm_scan_bwd(const void* x_all, const void* Hall, const void* Csave, co
  * the loop of modules/detection.py:131-148, and its BPTT).  bf16, dws_conv False, C = 128 / 256 (rvt_lstm_scan3_supported).  The weights do
  * not fit on chip: they are streamed from L2 every step in MFMA-operand order, which rvt_lstm_scan3_pack produces once per
  * optimizer step from the natural [4C][2C] matrix (gate order f,i,o,g, input order [x | h]: rnn.py:52-61):
- *   wp_fwd  [C/64][2C/16][8][64][8]   (wave, k-step, (channel block, gate), lane, element)    = 4C * 2C elements
- *   wtp_bwd [C/64][4C/16][4][64][8]   (wave, k-step, (channel block, x | h part), lane, element) = rows of W^T, same size
+ *   wp_fwd  [C/32][2C/16][4][64][8]   (wave = 32-channel block, k-step, gate, lane, element)        = 4C * 2C elements
+ *   wtp_bwd [C/32][4C/16][2][64][8]   (wave = 32-channel block, k-step, x | h part, lane, element)  = rows of W^T, same size
  * Forward: x_all [T][M][C], Hall [T+1][M][C] (slot 0 = incoming h, filled by the caller; slots 1.. written), c0 fp32 [M][C] or
  * NULL (zeros, rnn.py:43-47), c_last fp32 [M][C].  For BPTT it saves the ACTIVATED gates (gsave) and a bf16 copy of the cell
  * states (Csave) in a private register-dump order; both buffers hold T * rvt_lstm_scan3_rows(C, M) * 4C / * C elements and are
@@ -342,9 +342,11 @@ int rvt_lstm_scan_bwd(const void* x_all, const void* Hall, const void* Csave, co
  * (NULL = zeros), dc_last fp32 [M][C] (NULL = zeros); writes dx_all [T][M][C], dz_all [T][M][4C] (natural gate order: the operand
  * of rvt_lstm_wgrad), dh0 [M][C], dc0 fp32 [M][C]. */
 int rvt_lstm_scan3_supported(int dtype, int C);
-/* rb in {1, 2}: the forward walks tiles of 32 * rb tokens, and the dump order depends on it, so ONE value serves the buffer sizing,
- * the forward and the reverse scan of a step.  rvt_lstm_scan3_rb(C) is the tuned value (RvtTuning.lstm_scan3_rb128 / _rb256); a stage
- * takes it from its route record (RvtStageRoutes.lstm_scan3_rb), never from the tuning record a second time. */
+/* rb in {1, 2}: the forward walks tiles of 32 * rb tokens, and the number of 32-token blocks the dumps hold per step depends on it,
+ * so ONE value serves the buffer sizing, the forward and the reverse scan of a step (the reverse scan's own tile is the launcher's
+ * choice and independent of it).  rvt_lstm_scan3_rb(C) is the tuned value (RvtTuning.lstm_scan3_rb128 / _rb256); a stage takes rb from
+ * its route record (RvtStageRoutes.lstm_scan3_rb: 2 where the tuned value is 2 or the stage has Ms * C >= 2^22 token-channels per
+ * step, else 1), never from the tuning record a second time. */
 int rvt_lstm_scan3_rb(int C);
 int rvt_lstm_scan3_rows(int C, int M, int rb);
 int rvt_lstm_scan3_pack(const void* w, void* wp_fwd, void* wtp_bwd, int C, void* stream);

@@ -141,8 +141,9 @@ int rvt_lstm_scan_bwd(const void* x_all, const void* Hall, const void* Csave, co
 
 
 // ---------------------------------------------------------------- wide stages: streamed weights, saved gates (lstm_scan3.hpp)
-// rb of the forward tile (32 rb tokens per workgroup; it fixes the dump order of gsave / Csave); the reverse scan always walks 32-token
-// blocks.  The tuned value is read HERE only: callers carry it from the sizing of the dumps to the forward to the reverse scan.
+// rb of the forward tile (32 rb tokens per workgroup; it fixes how many 32-token blocks gsave / Csave hold per step); the reverse scan
+// walks tiles of its own size and addresses the dumps by 32-token block.  The tuned value is read HERE only: callers carry it from
+// the sizing of the dumps to the forward to the reverse scan.
 int rvt_lstm_scan3_rb(int C) { return (C == 256 ? tuning().lstm_scan3_rb256 : tuning().lstm_scan3_rb128) == 2 ? 2 : 1; }
 // tuning().lstm_scan3: bit 0 = C 256, bit 1 = C 128
 int rvt_lstm_scan3_supported(int dtype, int C) {
@@ -155,7 +156,7 @@ int rvt_lstm_scan3_rows(int C, int M, int rb) {
 int rvt_lstm_scan3_pack(const void* w, void* wp_fwd, void* wtp_bwd, int C, void* stream) {
     RVT_CHECK(C % 64 == 0 && w != nullptr, "lstm_scan3_pack: C=%d must be a multiple of 64", C);
     hipStream_t st = (hipStream_t)stream;
-    const int pieces = (C / 64) * (2 * C / 16) * 8 * 64;        // (same count in both directions)
+    const int pieces = (C / 32) * (2 * C / 16) * 4 * 64;        // 16-byte pieces (same count in both directions)
     const int grid = imax(1, imin(1024, (pieces + 255) / 256));
     if (wp_fwd != nullptr) hipLaunchKernelGGL(lstm_scan3_pack_kernel<false>, dim3(grid), dim3(256), 0, st, (const bf16*)w, (bf16*)wp_fwd, C);
     if (wtp_bwd != nullptr) hipLaunchKernelGGL(lstm_scan3_pack_kernel<true>, dim3(grid), dim3(256), 0, st, (const bf16*)w, (bf16*)wtp_bwd, C);
@@ -167,7 +168,7 @@ int rvt_lstm_scan3_fwd(const void* x_all, void* Hall, const float* c0, float* c_
     RVT_CHECK(M >= 1 && T_steps >= 1 && (Csave == nullptr) == (gsave == nullptr), "lstm_scan3_fwd: empty problem, or only one of Csave / gsave");
     hipStream_t st = (hipStream_t)stream;
 #define RVT_SCAN3_FWD(CC, RBB) do { auto k = lstm_scan3_fwd_kernel<CC, RBB>;                                                     \
-        hipLaunchKernelGGL(k, dim3(scan_grid(k, CC, M, 32 * RBB)), dim3(CC), 0, st, (const bf16*)x_all, (bf16*)Hall, c0, c_last, \
+        hipLaunchKernelGGL(k, dim3(scan_grid(k, 2 * CC, M, 32 * RBB)), dim3(2 * CC), 0, st, (const bf16*)x_all, (bf16*)Hall, c0, c_last, \
                            (bf16*)Csave, (const bf16*)wp, bias, (bf16*)gsave, M, T_steps); } while (0)
     if (C == 256) { if (rb == 2) RVT_SCAN3_FWD(256, 2); else RVT_SCAN3_FWD(256, 1); }
     else { if (rb == 2) RVT_SCAN3_FWD(128, 2); else RVT_SCAN3_FWD(128, 1); }
@@ -180,10 +181,13 @@ int rvt_lstm_scan3_bwd(const void* gsave, const void* Csave, const float* c0, co
     RVT_CHECK(M >= 1 && T_steps >= 1 && gsave != nullptr && Csave != nullptr && dx_all != nullptr && dz_all != nullptr,
               "lstm_scan3_bwd: empty problem / missing buffers");
     hipStream_t st = (hipStream_t)stream;
-#define RVT_SCAN3_BWD(CC) do { auto k = lstm_scan3_bwd_kernel<CC>;                                                                       \
-        hipLaunchKernelGGL(k, dim3(scan_grid(k, CC, M, 32)), dim3(CC), 0, st, (const bf16*)gsave, (const bf16*)Csave, c0, (const bf16*)dH, \
-                           dc_last, (const bf16*)wtp, (bf16*)dx_all, (bf16*)dz_all, (bf16*)dh0, dc0, M, T_steps, rb); } while (0)
-    if (C == 256) RVT_SCAN3_BWD(256); else RVT_SCAN3_BWD(128);
+    // the reverse scan's own tile (7 [TM][C] tiles of LDS): 32 tokens at both widths, two waves per SIMD (C = 128: 56 KB, two workgroups
+    // per CU; C = 256: 112 KB, one of eight waves).  64 tokens at C = 128 (112 KB, ONE wave per SIMD: nothing runs behind a workgroup's
+    // dump loads and gate math) lost: 2.04 ms against 1.46 for this form and 1.63 for the parent's, 92160 tokens, T = 21.
+#define RVT_SCAN3_BWD(CC, RBB) do { auto k = lstm_scan3_bwd_kernel<CC, RBB>;                                                             \
+        hipLaunchKernelGGL(k, dim3(scan_grid(k, 2 * CC, M, 32 * RBB)), dim3(2 * CC), 0, st, (const bf16*)gsave, (const bf16*)Csave, c0,    \
+                           (const bf16*)dH, dc_last, (const bf16*)wtp, (bf16*)dx_all, (bf16*)dz_all, (bf16*)dh0, dc0, M, T_steps, rb); } while (0)
+    if (C == 256) RVT_SCAN3_BWD(256, 1); else RVT_SCAN3_BWD(128, 1);
 #undef RVT_SCAN3_BWD
     return check_launch("lstm_scan3_bwd");
 }

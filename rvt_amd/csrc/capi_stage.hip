@@ -154,7 +154,13 @@ int rvt_stage_routes(const RvtStageDesc* dp, int T, int B, int save, int has_dws
     const int scan_mode = tn.route_lstm_scan;
     if (!has_dws && rvt_lstm_scan3_supported(dt, C) && !(C == 128 && Ms < 16384 && scan_mode != 0) && (save || T > 1)) {
         r.lstm_route = 3;
-        r.lstm_scan3_rb = rvt_lstm_scan3_rb(C);
+        // Forward tile: 64 tokens (rb = 2) stream half the weight bytes per token, but halve the tile count.  They are the default
+        // where every workgroup the chip holds gets a 64-token tile: Ms / 64 >= 256 CUs x (256 / C) workgroups per CU, i.e.
+        // Ms C >= 2^22 (C = 256: 16384 tokens, C = 128: 32768).  Forward, T = 21, 64- against 32-token tiles (parent: its best):
+        //   C = 256, 23040 tokens (360 tiles): 0.765 against 1.000 ms (0.950);   C = 128, 92160 (1440): 0.948 against 1.220 (1.235);
+        //   C = 256, 640 (stage 4 of RVT-Tiny: 10 tiles on 256 CUs): 0.284 against 0.214 (0.215);   C = 128, 2560: 0.132 against 0.085.
+        // The tuning record still forces 64 (lstm_scan3_rb128 / _rb256 = 2: the tests and the microbenchmark).
+        r.lstm_scan3_rb = rvt_lstm_scan3_rb(C) == 2 || (long long)Ms * C >= (1ll << 22) ? 2 : 1;
     } else if (!has_dws && scan_mode != 0 && rvt_lstm_scan_supported(dt, C) && !(scan_mode == -1 && T == 1 && !save) &&
                (scan_mode == 1 || C <= 64 || rvt_lstm_scan_saves_gates(dt, C))) {
         r.lstm_route = rvt_lstm_scan_saves_gates(dt, C) ? 2 : 1;
