@@ -21,11 +21,11 @@ template <class K> static int scan_grid(K kernel, int threads, int M, int tm) {
     const int per_cu = resident_per_cu(kernel, threads, 1);
     return imax(1, imin(n_tiles, resident_override > 0 ? resident_override : 256 * per_cu));
 }
-template <class T, int C, int NW, int RB, bool W_LDS, bool W_REG = false>
+template <class T, int C, int NW, bool W_LDS, bool W_REG = false>
 static void launch_lstm_scan_fwd(const void* x_all, void* Hall, const float* c0, float* c_last, void* Csave, const void* W,
                                  const float* bias, void* gates_out, int M, int Tn, hipStream_t st) {
-    constexpr int TM = (NW / (C / 32)) * RB * 32;
-    auto k = lstm_scan_fwd_kernel<T, C, NW, RB, W_LDS, W_REG>;
+    constexpr int TM = (NW / (C / 32)) * 32;
+    auto k = lstm_scan_fwd_kernel<T, C, NW, W_LDS, W_REG>;
     hipLaunchKernelGGL(k, dim3(scan_grid(k, 64 * NW, M, TM)), dim3(64 * NW), 0, st, (const T*)x_all, (T*)Hall, c0, c_last,
                        (T*)Csave, (const T*)W, bias, (T*)gates_out, M, Tn);
 }
@@ -75,19 +75,19 @@ int rvt_lstm_scan_fwd(const void* x_all, void* Hall, const float* c0, float* c_l
     RVT_CHECK(M >= 1 && T_steps >= 1, "lstm_scan_fwd: empty problem");
     hipStream_t st = (hipStream_t)stream;
     RVT_CHECK(gates_out == nullptr || scan_regw_built(dtype, C), "lstm_scan_fwd: gates are only saved by the bf16 C = 128 variant");
-#define RVT_SCAN_FWD(TT, CC, NWW, RBB, LDS) launch_lstm_scan_fwd<TT, CC, NWW, RBB, LDS>(x_all, Hall, c0, c_last, Csave, w, bias, nullptr, M, T_steps, st)
+#define RVT_SCAN_FWD(TT, CC, NWW, LDS) launch_lstm_scan_fwd<TT, CC, NWW, LDS>(x_all, Hall, c0, c_last, Csave, w, bias, nullptr, M, T_steps, st)
     if (dtype == RVT_BF16) {
-        if (C == 32) RVT_SCAN_FWD(bf16, 32, 4, 1, true);
+        if (C == 32) RVT_SCAN_FWD(bf16, 32, 4, true);
         else if (C == 64) {                                   // T-form rebuild (lstm_scan2.hpp): one wave = 32 tokens, no barriers
             auto k = lstm_scan2_fwd_kernel<8>;
             hipLaunchKernelGGL(k, dim3(scan_grid(k, 512, M, 256)), dim3(512), 0, st, (const bf16*)x_all, (bf16*)Hall, c0, c_last,
                                (bf16*)Csave, (const bf16*)w, bias, M, T_steps);
         }
-        else launch_lstm_scan_fwd<bf16, 128, 4, 1, false, true>(x_all, Hall, c0, c_last, Csave, w, bias, gates_out, M, T_steps, st);     // (64-token tiles spill: 2.3 ms against 1.65)
+        else launch_lstm_scan_fwd<bf16, 128, 4, false, true>(x_all, Hall, c0, c_last, Csave, w, bias, gates_out, M, T_steps, st);     // (64-token tiles spill: 2.3 ms against 1.65)
     } else {             // (four waves: the f32 variants need more than the 256 registers an 8-wave workgroup leaves)
-        if (C == 32) RVT_SCAN_FWD(float, 32, 4, 1, false);
-        else if (C == 64) RVT_SCAN_FWD(float, 64, 4, 1, false);
-        else RVT_SCAN_FWD(float, 128, 4, 1, false);
+        if (C == 32) RVT_SCAN_FWD(float, 32, 4, false);
+        else if (C == 64) RVT_SCAN_FWD(float, 64, 4, false);
+        else RVT_SCAN_FWD(float, 128, 4, false);
     }
 #undef RVT_SCAN_FWD
     return check_launch("lstm_scan_fwd");

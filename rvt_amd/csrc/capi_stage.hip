@@ -143,9 +143,17 @@ int rvt_stage_routes(const RvtStageDesc* dp, int T, int B, int save, int has_dws
     // ConvLSTM with the time loop inside the kernel instead of one launch per step: only the 1x1-conv cell (dws_conv False — every
     // shipped config).
     //   route 3 (lstm_scan3.hpp; bf16, C = 128 / 256): weights streamed from L2 in operand order, gates saved for the reverse scan:
-    //       instead of 3 launches per step at C = 256 (weights too large for the chip), instead of route 2 at C = 128 — except with few
-    //       tokens per step (stage 3 of RVT-Tiny: 2560), where the register-resident weights of route 2 win: 0.118 + 0.172 ms against
-    //       0.124 + 0.198; at 92160 tokens (stage 2 of RVT-Base) the streamed form does: 1.28 + 1.66 against 1.50 + 2.15.
+    //       instead of 3 launches per step at C = 256 (weights too large for the chip), instead of route 2 at C = 128 — except below
+    //       16384 tokens per step (stage 3 of RVT-Tiny), which stay on the register-resident weights of route 2.  Measured with both
+    //       kernels in one process (profiles/scan_route2/microbench_parent.txt; T = 21, ms, route 3 at rb = 1 against route 2):
+    //         tokens   forward + reverse scan            no-grad forward
+    //            640   0.084 + 0.132 / 0.113 + 0.171     0.081 / 0.086
+    //           2560   0.088 + 0.134 / 0.118 + 0.174     0.082 / 0.087
+    //           7680   0.111 + 0.164 / 0.131 + 0.198     0.096 / 0.092
+    //          92160   1.050 + 1.445 / 1.498 + 2.168     0.793 / 1.076
+    //       Since the one-block-per-wave split route 2 no longer wins a training step anywhere; what it still wins is the no-grad
+    //       forward at 7680 tokens, by 0.004 ms where its own timings spread 0.001.  That kept it from being retired, and the
+    //       exception stands as it was until that point is settled.
     //   routes 1 / 2 (lstm_scan.hpp, lstm_scan2.hpp): by default where the weights stay resident in LDS (C <= 64; gates recomputed by
     //       the reverse scan, which can also accumulate the weight gradients: lstm_scan_wgrad) or in the register file (bf16 C = 128;
     //       gates saved: route 2); tuning.route_lstm_scan = 1: all supported widths (the parity tests); 0 disables.

@@ -74,14 +74,14 @@ template <class T, int C, int NT, int TM> __device__ __forceinline__ void tile_l
 // needs the rows {g C + 32 w + lane} of all four gates, 64 operand pieces = 256 registers, loaded once per launch; streaming
 // them from L2 every step instead (W_LDS = W_REG = false) is what bounded the C = 128 scan (15.5 GB of L2 reads per launch).
 // gates_out (nullable): the activated gates [Tn][M][4C] (natural order f,i,o,g), for the reverse scan that does not recompute them.
-template <class T, int C, int NW, int RB, bool W_LDS, bool W_REG = false>
+template <class T, int C, int NW, bool W_LDS, bool W_REG = false>
 __global__ void __launch_bounds__(64 * NW)
 lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const float* __restrict__ c0, float* __restrict__ c_last,
                      T* __restrict__ Csave, const T* __restrict__ W, const float* __restrict__ bias, T* __restrict__ gates_out,
                      int M, int Tn) {
     typedef LstmScanGeom<T, C, NW> Gm;
     constexpr int NT = Gm::NT, NWC = Gm::NWC, NWM = Gm::NWM, KTC = Gm::KTC;
-    constexpr int TM = NWM * RB * 32;
+    constexpr int TM = NWM * 32;
     constexpr int TILE = KTC * TM * 128;
     constexpr int WPART = KTC * (4 * C) * 128;             // one [4C][C] half of W
     constexpr int NFX = (TM * (C / 8) + NT - 1) / NT;
@@ -121,20 +121,17 @@ lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const fl
                     wreg[W_REG ? part : 0][W_REG ? k16 : 0][W_REG ? g : 0] =
                         frag_load<T>(W + (size_t)(g * C + wn * 32 + (lane & 31)) * 2 * C + part * C + (2 * k16 + (lane >> 5)) * 8);
     }
-    // gate biases folded into the exp2 arguments; LDS byte offsets of this lane's 16 (row, channel) elements per row block
+    // gate biases folded into the exp2 arguments; LDS byte offsets of this lane's 16 (row, channel) elements
     // (fixed for the launch: computing the swizzle per element per step costs more VALU than the gate math itself)
     const float nbf = bias[ch] * -1.4426950408889634f, nbi = bias[C + ch] * -1.4426950408889634f;
     const float nbo = bias[2 * C + ch] * -1.4426950408889634f, tbg = bias[3 * C + ch] * 2.8853900817779268f;
-    int off0[RB];
-#pragma unroll
-    for (int i = 0; i < RB; i++)
-        off0[i] = (int)(reinterpret_cast<char*>(opm_elem_ptr<T>(Ax, TM, (wm * RB + i) * 32 + 4 * half, ch)) - Ax);
+    const int off0 = (int)(reinterpret_cast<char*>(opm_elem_ptr<T>(Ax, TM, wm * 32 + 4 * half, ch)) - Ax);
 
     const int n_tiles = (M + TM - 1) / TM;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int m0 = tile * TM;
         frag_t<T> xr[NFX];
-        float creg[RB][16];
+        float creg[16];
         // prologue of the tile: h_{-1} -> Ah[0], x_0 -> Ax, c_{-1} -> registers (accumulator layout)
         tile_load_regs<T, C, NT, TM>(xr, Hall, m0, M, tid);
         lds_barrier();                                     // previous tile's copy-out / MFMA reads are done
@@ -142,12 +139,10 @@ lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const fl
         tile_load_regs<T, C, NT, TM>(xr, x_all, m0, M, tid);
         lds_tile_from_regs<T, C, NT, TM>(Ax, xr, tid);
 #pragma unroll
-        for (int i = 0; i < RB; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = m0 + (wm * RB + i) * 32 + acc_row(r, lane);
-                creg[i][r] = (c0 != nullptr && row < M) ? c0[(size_t)row * C + ch] : 0.f;
-            }
+        for (int r = 0; r < 16; r++) {
+            const int row = m0 + wm * 32 + acc_row(r, lane);
+            creg[r] = (c0 != nullptr && row < M) ? c0[(size_t)row * C + ch] : 0.f;
+        }
         lds_barrier();
         int cur = 0;
         for (int t = 0; t < Tn; t++) {
@@ -155,11 +150,9 @@ lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const fl
             char* const An = Ah0 + (cur ^ 1) * TILE;
             if (t + 1 < Tn) tile_load_regs<T, C, NT, TM>(xr, x_all + (size_t)(t + 1) * MC, m0, M, tid);
             sched_fence();
-            f32x16 acc[RB][4];
+            f32x16 acc[4];
 #pragma unroll
-            for (int i = 0; i < RB; i++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) acc_zero(acc[i][g]);
+            for (int g = 0; g < 4; g++) acc_zero(acc[g]);
             // (weights streamed from L2: keep the K loop rolled, or every B fragment of the step is hoisted and spilled)
             constexpr int KUNROLL = (W_LDS || W_REG) ? C / 16 : 1;
 #pragma unroll
@@ -169,9 +162,8 @@ lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const fl
 #pragma clang loop unroll_count(KUNROLL)
                 for (int kc = 0; kc < C; kc += 16) {
                     const int fcg = kc / 8 + half;
-                    frag_t<T> a[RB], b[4];
-#pragma unroll
-                    for (int i = 0; i < RB; i++) a[i] = opm_load_frag<T>(A, TM, (wm * RB + i) * 32 + li, fcg);
+                    const frag_t<T> a = opm_load_frag<T>(A, TM, wm * 32 + li, fcg);
+                    frag_t<T> b[4];
 #pragma unroll
                     for (int g = 0; g < 4; g++) {
                         if (W_LDS) b[g] = opm_load_frag<T>(Wl, 4 * C, g * C + ch, fcg);
@@ -179,32 +171,28 @@ lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const fl
                         else b[g] = frag_load<T>(W + (size_t)(g * C + ch) * 2 * C + part * C + fcg * 8);
                     }
 #pragma unroll
-                    for (int i = 0; i < RB; i++)
-#pragma unroll
-                        for (int g = 0; g < 4; g++) mma32(acc[i][g], a[i], b[g]);
+                    for (int g = 0; g < 4; g++) mma32(acc[g], a, b[g]);
                 }
             }
             // gates (rnn.py:57-67), in registers
 #pragma unroll
-            for (int i = 0; i < RB; i++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const float f = sigmoid_zb(acc[i][0][r], nbf);
-                    const float ig = sigmoid_zb(acc[i][1][r], nbi);
-                    const float o = sigmoid_zb(acc[i][2][r], nbo);
-                    const float g = tanh_zb(acc[i][3][r], tbg);
-                    const float cn = f * creg[i][r] + ig * g;
-                    creg[i][r] = cn;
-                    const float hn = o * tanh_f(cn);
-                    *reinterpret_cast<T*>(An + acc_elem_off(off0[i], r)) = (T)hn;
-                    if (Csave != nullptr) *reinterpret_cast<T*>(Cs + acc_elem_off(off0[i], r)) = (T)cn;
-                    if (W_REG && gates_out != nullptr) {
-                        *reinterpret_cast<T*>(Gs + 0 * TILE + acc_elem_off(off0[i], r)) = (T)f;
-                        *reinterpret_cast<T*>(Gs + 1 * TILE + acc_elem_off(off0[i], r)) = (T)ig;
-                        *reinterpret_cast<T*>(Gs + 2 * TILE + acc_elem_off(off0[i], r)) = (T)o;
-                        *reinterpret_cast<T*>(Gs + 3 * TILE + acc_elem_off(off0[i], r)) = (T)g;
-                    }
+            for (int r = 0; r < 16; r++) {
+                const float f = sigmoid_zb(acc[0][r], nbf);
+                const float ig = sigmoid_zb(acc[1][r], nbi);
+                const float o = sigmoid_zb(acc[2][r], nbo);
+                const float g = tanh_zb(acc[3][r], tbg);
+                const float cn = f * creg[r] + ig * g;
+                creg[r] = cn;
+                const float hn = o * tanh_f(cn);
+                *reinterpret_cast<T*>(An + acc_elem_off(off0, r)) = (T)hn;
+                if (Csave != nullptr) *reinterpret_cast<T*>(Cs + acc_elem_off(off0, r)) = (T)cn;
+                if (W_REG && gates_out != nullptr) {
+                    *reinterpret_cast<T*>(Gs + 0 * TILE + acc_elem_off(off0, r)) = (T)f;
+                    *reinterpret_cast<T*>(Gs + 1 * TILE + acc_elem_off(off0, r)) = (T)ig;
+                    *reinterpret_cast<T*>(Gs + 2 * TILE + acc_elem_off(off0, r)) = (T)o;
+                    *reinterpret_cast<T*>(Gs + 3 * TILE + acc_elem_off(off0, r)) = (T)g;
                 }
+            }
             lds_barrier();                                 // h_t / c_t tiles complete; every wave is done with Ax
             {                                              // tile rows -> HBM in 16-byte pieces
                 constexpr int G = C / 8;
@@ -231,12 +219,10 @@ lstm_scan_fwd_kernel(const T* __restrict__ x_all, T* __restrict__ Hall, const fl
             cur ^= 1;
         }
 #pragma unroll
-        for (int i = 0; i < RB; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = m0 + (wm * RB + i) * 32 + acc_row(r, lane);
-                if (row < M) c_last[(size_t)row * C + ch] = creg[i][r];
-            }
+        for (int r = 0; r < 16; r++) {
+            const int row = m0 + wm * 32 + acc_row(r, lane);
+            if (row < M) c_last[(size_t)row * C + ch] = creg[r];
+        }
     }
 }
 

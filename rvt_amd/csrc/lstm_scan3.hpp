@@ -4,7 +4,7 @@
 // lstm_scan.hpp / lstm_scan2.hpp keep the cell's weights on chip (LDS or registers); at C = 256 they are 1 MB and the
 // recurrence ran as one GEMM + gate kernel per step (42 x 3 launches per stage and step of training, each with 23 - 90 tiles on
 // 256 CUs, the activated gates and the fp32 cell state crossing HBM twice per step); at C = 128 (256 KB, register-resident in
-// lstm_scan.hpp) this form wins from 16384 tokens per step.  C = 512 (4 MB) stays on the per-step route.  Here a workgroup owns a
+// lstm_scan.hpp) this form is routed from 16384 tokens per step.  C = 512 (4 MB) stays on the per-step route.  Here a workgroup owns a
 // tile of 32 RB tokens for ALL T steps (a 1x1-conv cell is independent per token) and STREAMS the weights from L2 every step:
 //   * wave w owns ONE block of 32 channels, 32 w .. 32 w + 31 (a workgroup is C / 32 waves = 2 C threads), and computes, for them,
 //     the four gate blocks f, i, o, g as 32x32 MFMA column blocks: the four gates of a (token, channel) land in the same lane and

@@ -53,20 +53,20 @@ attn_core - softmax(Q K^T) V on a saved qkv tensor: q, k, v, dO are the stored b
 
 lstm - ConvLSTM cell with a 1x1 conv, T steps, and its BPTT.  z = [x | h] W^T + b accumulates in fp32, the gates and c_t stay fp32.
     h_t rounded where it is stored; the stored value is the next step's operand (`h_bf16`)
-             gemm.hpp:715 (per step)  lstm_scan.hpp:199  lstm_scan2.hpp:203 (s2_pack)  lstm_scan3.hpp:172
-    c_t copy for the backward (`c`, returned before its rounding)    lstm_scan.hpp:200  lstm_scan2.hpp:214  lstm_scan3.hpp:181;  c_last stays fp32
-    activated gates saved for the backward (`gates`, before rounding)  gemm.hpp:718-721  lstm_scan.hpp:202-205 (W_REG)  lstm_scan3.hpp:177-180
-    backward, `saved_gates`: f, i, o, g read back from that save      rowops.hpp:244-247  lstm_scan.hpp:447-450 (GATES)  lstm_scan3.hpp:286-289
-             off: recomputed in fp32 from x_t and the stored h_{t-1}  lstm_scan.hpp:452-455  lstm_scan2.hpp:497-500
+             gemm.hpp:715 (per step)  lstm_scan.hpp:187  lstm_scan2.hpp:203 (s2_pack)  lstm_scan3.hpp:172
+    c_t copy for the backward (`c`, returned before its rounding)    lstm_scan.hpp:188  lstm_scan2.hpp:214  lstm_scan3.hpp:181;  c_last stays fp32
+    activated gates saved for the backward (`gates`, before rounding)  gemm.hpp:718-721  lstm_scan.hpp:190-193 (W_REG)  lstm_scan3.hpp:177-180
+    backward, `saved_gates`: f, i, o, g read back from that save      rowops.hpp:244-247  lstm_scan.hpp:433-436 (GATES)  lstm_scan3.hpp:286-289
+             off: recomputed in fp32 from x_t and the stored h_{t-1}  lstm_scan.hpp:438-441  lstm_scan2.hpp:497-500
     backward, `c_bf16`: c_{t-1} from the bf16 save, the incoming fp32 c0 converted the same way, tanh(c_t) of f c_{t-1} + i g rebuilt from it
-             lstm_scan.hpp:323-324 :457 :459  lstm_scan2.hpp:449 :460 :503  lstm_scan3.hpp:291 :296 :304
+             lstm_scan.hpp:309-310 :443 :445  lstm_scan2.hpp:449 :460 :503  lstm_scan3.hpp:291 :296 :304
              off: c_t and c_{t-1} are the forward's fp32 tensors      rowops.hpp:250-251 :254
     `dz_bf16`: dz, the operand of [dx | dh] = dz W and of dW = dz^T [x | h], and a stored output
-             rowops.hpp:263-266  lstm_scan.hpp:463-466  lstm_scan2.hpp:515-516  lstm_scan3.hpp:306-309
+             rowops.hpp:263-266  lstm_scan.hpp:449-452  lstm_scan2.hpp:515-516  lstm_scan3.hpp:306-309
     `db_bf16`: db from the rounded dz - lstm_scan2.hpp:366 :389 (product against ones), and every test that sums the stored dz itself;
-             off: lstm_scan.hpp:467 sums the fp32 values
-    dx_t stored (lstm_scan.hpp:516, lstm_scan2.hpp:594, lstm_scan3.hpp:348); dh_{t-1} and dc stay in fp32 registers across the steps
-    (lstm_scan.hpp:517, lstm_scan2.hpp:591, lstm_scan3.hpp:349); dh0 stored, dc0 fp32.
+             off: lstm_scan.hpp:453 sums the fp32 values
+    dx_t stored (lstm_scan.hpp:502, lstm_scan2.hpp:594, lstm_scan3.hpp:348); dh_{t-1} and dc stay in fp32 registers across the steps
+    (lstm_scan.hpp:503, lstm_scan2.hpp:591, lstm_scan3.hpp:349); dh0 stored, dc0 fp32.
 
 dgrad_ln - dx = add + LN'(dy W; x) and, `inside`, dx = LN'(dy W + add; x)     (dgrad_ln.hpp)
     du (+ add) rounded "as the two-launch chain stores it"                    :184 - AFTER the row sums s1 / s2 took the fp32 values (:180-182)

@@ -227,7 +227,7 @@ def _scan_fwd_bwd(backend, dt, C, M, T, zero_state, wx=1.0, kind=None):
             mw = m                       # lstm_scan2.hpp: db = dz^T against a fragment of ones, dz already bf16
         else:
             assert torch.equal(dx2.cpu(), dx.cpu()) and torch.equal(dh02.cpu(), dh0.cpu()) and torch.equal(dc02.cpu(), dc0.cpu())
-            mw = modelled(dt, truth, *margs)     # lstm_scan.hpp:467 sums the fp32 values
+            mw = modelled(dt, truth, *margs)     # lstm_scan.hpp:453 sums the fp32 values
         near(dw - 1.0, wr.grad, dt, 'in-kernel dW', mult=2.0, model=part(mw, 'dW'), cap=cap)
         near(db - 1.0, br.grad, dt, 'in-kernel db', mult=2.0, model=part(mw, 'db'), cap=cap)
     else:
