@@ -74,7 +74,30 @@ dgrad_ln - dx = add + LN'(dy W; x) and, `inside`, dx = LN'(dy W + add; x)     (d
     `fused=False` is the chain it replaces: du stored by the GEMM epilogue, then ln_bwd_kernel on the bf16 rows (rowops.hpp:59-116).
 
 ln_linear - u = LN(x) is the GEMM operand and the saved tensor (ln_linear.hpp:107-115, layernorm_fwd rowops.hpp:50); y stored (:134).
-linear / conv_fwd have no interior rounding point: fp32 accumulation of bf16 products, one storage rounding (gemm.hpp / ppgemm.hpp epilogues).
+
+linear_ep - y = epilogue(x W^T): the linear entry points on BOTH GEMM engines.  fp32 accumulation of bf16 products everywhere.
+    `gelu_in`: GELU(x) is converted to bf16 on its way into the operand tile           gemm.hpp:189 (xf_apply, XfGelu; 128-row engine only)
+    128-row engine (gemm.hpp): the side tensor is combined with the fp32 accumulator, ONE rounding at the store
+             EpStore v + bias + add :418-419   EpScaleRes res + gamma (v + bias) :460-461   EpMul v * mul :514-515
+             EpGeluBwd v * GELU'(pre) :478-479   EpGeluDual g, gp :495-497   EpDgradScatter v + add :669-670
+    256-wide engine (ppgemm.hpp), `side_rounded`: `convert` rounds c1 (acc + c0) into the LDS scratch                      :346-350 :368
+             and `store_rows` adds / multiplies the bf16 side tensor to the ROUNDED value and rounds a second time          :384-385
+             (PP_SCALE_RES: res + bf16(gamma (v + bias));  PP_ADD: bf16(v + bias) + add;  PP_MUL: bf16(v) * mul).  PP_STORE and
+             PP_GELU_DUAL have no side tensor: one rounding (:368).  The conv input gradient by 2 x 2 blocks (rvt_conv_dgrad4) with an
+             added cotangent is PP_ADD and rounds twice as well; the parity-class route (EpDgradScatter) rounds once.
+wgrad - dW = dy^T x, column sums of dy: fp32 throughout (split-K partial tiles and their fold, ppgemm_tn.hpp); `gelu_in` as above (gemm.hpp:189).
+layernorm - rowops.hpp ln_fwd_kernel / ln_bwd_kernel: two-pass statistics in fp32; y stored :50, dx (+ dres) stored :113; dw, db are
+    fp32 sums of fp32 products (:105).  No interior rounding point.
+conv_fwd / conv_dgrad / conv_wgrad - im2col products on the same engines: no interior rounding point but `side_rounded` above.
+    `scale` / `shift` / `act` (rvt_conv_bn_act_fwd): act(fma(acc, scale, shift)) on the fp32 accumulator, one store    gemm.hpp:438-441
+stem - y0 = conv of the uint8 planes (exact in bf16), stored stem.hpp:219; the LayerNorm statistics and output are taken from the
+    STORED y0 (:220 converts it back, "the statistics see what the backward will see"), x stored :247: the test models LN(y0) by
+    `layernorm` on the kernel's own y0.  stem_wgrad: `conv_wgrad`, fp32.
+dwconv - rowops.hpp dwconv_kernel: bias + nine fp32 products, one store :332; dwconv_wgrad_kernel: fp32 sums.
+lin_gelu_ws - fc1 + GELU on the weight-stationary kernel (ln_linear.hpp lin_gelu_ws_kernel): pre = x W^T + b in fp32; Phi and GELU' are
+    READ AT THE NEAREST POINT of the table of gelu_lut.hpp (`snap`): index = round((pre + X) N / 2X) clamped to [0, N]      gelu_lut.hpp:90-94
+             g = pre * Phi(snapped pre) with the UNSNAPPED pre as the factor, gp = GELU'(snapped pre)                     gelu_lut.hpp:123
+             both stored ln_linear.hpp:258-259.  Not a bf16 conversion but a quantisation of the argument, |error| <= 5.8e-4 on GELU'.
 """
 import math
 
@@ -279,10 +302,69 @@ def linear(x, w, b=None, *, rounding=True, dtype=torch.float32):
     return dict(y=x @ w.t() + (b if b is not None else 0.0))
 
 
-def wgrad(dy, x, *, rounding=True, dtype=torch.float32):
-    """dW = dy^T x and the column sums of dy, both kept in fp32 (ppgemm_tn.hpp): as `linear`, no rounding point at all."""
+def linear_ep(x, w, b=None, *, gelu_in=False, gamma=None, res=None, add=None, mul=None, gelu_pre=None, dual=False, side_rounded=False,
+              rounding=True, dtype=torch.float32):
+    """The linear entry points with their epilogues, x [M][K], w [N][K] -> dict of y, or (dual) of g = GELU(x W^T + b), gp = GELU'.
+      gamma, res   y = res + gamma (x W^T + b)          add   y = x W^T + b + add
+      mul          y = (x W^T) * mul                    gelu_pre   y = (x W^T) * GELU'(gelu_pre)
+    gelu_in: the operand is bf16(GELU(x)).  side_rounded: the 256-wide engine - gamma (v + b), v + b or v is rounded to bf16 BEFORE
+    res / add / mul is combined with it (ppgemm.hpp:368 then :384); off: the 128-row engine combines in fp32."""
+    x, w, b, gamma, res, add, mul, gelu_pre = _prep(dtype, x, w, b, gamma, res, add, mul, gelu_pre)
+    assert (res is not None) + (add is not None) + (mul is not None) + (gelu_pre is not None) + bool(dual) <= 1 and (gamma is None) == (res is None)
+    r = lambda t: _r(t, rounding)
+    rs = r if side_rounded else (lambda t: t)
+    if gelu_in:
+        x = r(_gelu_both(x)[0])
+    v = x @ w.t() + (b if b is not None else 0.0)
+    if dual:
+        g, gp = _gelu_both(v)
+        return dict(g=g, gp=gp)
+    if res is not None:
+        return dict(y=res + rs(gamma * v))
+    if add is not None:
+        return dict(y=rs(v) + add)
+    if mul is not None:
+        return dict(y=rs(v) * mul)
+    if gelu_pre is not None:
+        return dict(y=v * _gelu_both(gelu_pre)[1])
+    return dict(y=v)
+
+
+def wgrad(dy, x, *, gelu_in=False, rounding=True, dtype=torch.float32):
+    """dW = dy^T x and the column sums of dy, both kept in fp32 (gemm.hpp split-K, ppgemm_tn.hpp): no rounding point but the GELU'd
+    operand (`gelu_in`: x -> bf16(GELU(x)), gemm.hpp:189).  `+=` into an fp32 buffer: the caller scales the model."""
     dy, x = _prep(dtype, dy, x)
+    if gelu_in:
+        x = _r(_gelu_both(x)[0], rounding)
     return dict(dW=dy.t() @ x, colsum=dy.sum(0))
+
+
+def layernorm(x, w, b, dy=None, dres=None, eps=1e-5, *, rounding=True, dtype=torch.float32):
+    """rowops.hpp ln_fwd_kernel / ln_bwd_kernel: x [rows][C] -> dict of y and (dy given) dx = LN'(dy; x) + dres, dw, db.  Two-pass
+    statistics, everything in fp32, nothing rounded before the stores (`rounding` has nothing to switch)."""
+    x, w, b, dy, dres = _prep(dtype, x, w, b, dy, dres)
+    xhat, rstd = _ln(x, eps)
+    out = dict(y=xhat * w + (b if b is not None else 0.0))
+    if dy is not None:
+        out.update(dx=_ln_bwd(dy, xhat, rstd, w) + (dres if dres is not None else 0.0), dw=(dy * xhat).sum(0), db=dy.sum(0))
+    return out
+
+
+GELU_NLUT_N, GELU_LUT_X = 8192, 6.0        # gelu_lut.hpp: "read at the NEAREST of 8192 points" of [-X, X], X = 6
+
+
+def lin_gelu_ws(x, w, b, *, rounding=True, dtype=torch.float32):
+    """fc1 + GELU on the weight-stationary kernel: pre = x W^T + b -> dict of g, gp.  Phi and GELU' are read at the nearest of the
+    N + 1 = 8193 grid points -X + (2X / N) i, N = 8192, X = 6 (gelu_lut.hpp, comment of the nearest-entry tables); the factor of
+    g = pre * Phi(snapped pre) is the unsnapped pre.  `rounding` switches the snapping (the model's only quantisation) off."""
+    x, w, b = _prep(dtype, x, w, b)
+    pre = x @ w.t() + b
+    xs = pre
+    if rounding:
+        s = GELU_NLUT_N / (2.0 * GELU_LUT_X)
+        xs = torch.round((pre + GELU_LUT_X) * s).clamp(0.0, float(GELU_NLUT_N)) / s - GELU_LUT_X
+    phi = 0.5 * (1.0 + torch.erf(xs * (1.0 / math.sqrt(2.0))))
+    return dict(g=pre * phi, gp=_gelu_both(xs)[1])
 
 
 def dgrad_ln(dy, w, x, add, lw, eps=1e-5, *, inside=False, fused=True, rounding=True, dtype=torch.float32):
@@ -363,7 +445,47 @@ def lstm(x, h0, c0, w, b, dH=None, dc_last=None, *, rounding=True, dtype=torch.f
     return out
 
 
-def conv_fwd(x, w, stride, pad, *, rounding=True, dtype=torch.float32):
-    """x (F, H, W, Cin) channels-last, w (Cout, Cin, k, k) -> y (F, Ho, Wo, Cout); as `linear`, no interior rounding point."""
-    x, w = _prep(dtype, x, w)
-    return dict(y=F.conv2d(x.permute(0, 3, 1, 2), w, None, stride, pad).permute(0, 2, 3, 1))
+def _silu(z):
+    return z * torch.sigmoid(z)
+
+
+def conv_fwd(x, w, stride, pad, scale=None, shift=None, act=0, *, rounding=True, dtype=torch.float32):
+    """x (F, H, W, Cin) channels-last, w (Cout, Cin, k, k) -> y (F, Ho, Wo, Cout); as `linear`, no interior rounding point.
+    scale / shift / act (rvt_conv_bn_act_fwd): the affine on the fp32 accumulator, then SiLU (act = 1), one store."""
+    x, w, scale, shift = _prep(dtype, x, w, scale, shift)
+    y = F.conv2d(x.permute(0, 3, 1, 2), w, None, stride, pad).permute(0, 2, 3, 1)
+    if scale is not None:
+        y = y * scale + shift
+        if act:
+            y = _silu(y)
+    return dict(y=y)
+
+
+def conv_dgrad(dy, w, stride, pad, H, W, add=None, *, side_rounded=False, rounding=True, dtype=torch.float32):
+    """Input gradient of conv_fwd: dy (F, Ho, Wo, Cout), w (Cout, Cin, k, k) -> dx (F, H, W, Cin) (+ add).  side_rounded: the 2 x 2-block
+    route with an added cotangent (ppgemm.hpp PP_ADD) rounds the product before it adds; the parity-class route adds in fp32."""
+    dy, w, add = _prep(dtype, dy, w, add)
+    dx = torch.nn.grad.conv2d_input((dy.shape[0], w.shape[1], H, W), w, dy.permute(0, 3, 1, 2).contiguous(), stride, pad).permute(0, 2, 3, 1)
+    if add is not None:
+        dx = (_r(dx, rounding) if side_rounded else dx) + add
+    return dict(dx=dx)
+
+
+def conv_wgrad(x, dy, k, stride, pad, *, rounding=True, dtype=torch.float32):
+    """dW (Cout, Cin, k, k) = the weight gradient of conv_fwd, kept in fp32 on both engines (split-K im2col, ppgemm_tn.hpp CONV)."""
+    x, dy = _prep(dtype, x, dy)
+    size = (dy.shape[-1], x.shape[-1], k, k)
+    return dict(dW=torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2).contiguous(), size, dy.permute(0, 3, 1, 2).contiguous(), stride, pad))
+
+
+def dwconv(x, w, b, dy=None, *, rounding=True, dtype=torch.float32):
+    """Depth-wise 3 x 3 (rowops.hpp): x, dy (N, H, W, C), w (C, 9), b (C) -> dict of y and (dy given) dx, dw (C, 9), db; fp32, one store."""
+    x, w, b, dy = _prep(dtype, x, w, b, dy)
+    C = x.shape[-1]
+    w4, xc = w.reshape(C, 1, 3, 3), x.permute(0, 3, 1, 2).contiguous()
+    out = dict(y=F.conv2d(xc, w4, b, padding=1, groups=C).permute(0, 2, 3, 1))
+    if dy is not None:
+        dc = dy.permute(0, 3, 1, 2).contiguous()
+        out.update(dx=torch.nn.grad.conv2d_input(xc.shape, w4, dc, 1, 1, 1, C).permute(0, 2, 3, 1),
+                   dw=torch.nn.grad.conv2d_weight(xc, w4.shape, dc, 1, 1, 1, C).reshape(C, 9), db=dy.sum((0, 1, 2)))
+    return out
