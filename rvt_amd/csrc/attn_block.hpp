@@ -26,67 +26,23 @@
 // Token rows are read from HBM directly in MFMA-operand form (lane = row, 16 bytes of the row per k-step), so LayerNorm
 // statistics are an in-lane sum plus one exchange with lane^32, and the epilogue turns accumulator columns back into
 // 16-byte row pieces with v_permlane32_swap (the two halves of a wave hold the two 4-channel halves of every 8-channel
-// piece).  Window / grid partitioning is index arithmetic on the token rows (attn.hpp), weights stay in LDS for the
+// piece).  Window / grid partitioning is index arithmetic on the token rows (attn_pieces.hpp), weights stay in LDS for the
 // whole launch (persistent workgroups), and the waves of a workgroup never synchronise with each other.
 //
 // The backward additionally needs the transposes P, dS (contraction over queries for dV, dK): one trip through a
 // wave-private LDS tile, written as 8-byte row pieces from the accumulators and read back with the transposing LDS read.
+//
+// This file holds the two kernels and what only they use (LDS layout, projections, partition walk).  The column softmax is in
+// attn_pieces.hpp, the weight images and the transposing reads in opm.hpp, the accumulator <-> operand conversions in acc_frags.hpp,
+// row loads and LayerNorm in ln_pieces.hpp.
 #pragma once
 #include "common.hpp"
-#include "attn.hpp"
-#include "mlp.hpp"
+#include "attn_pieces.hpp"
+#include "opm.hpp"
+#include "acc_frags.hpp"
+#include "ln_pieces.hpp"
 
 namespace rvt {
-
-// per-row (= per accumulator register) additive constants of a T-form block: p points at the 32 values of the block
-__device__ __forceinline__ void acc_add_rows(f32x16& c, const float* p, int half) {
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p + 8 * g + 4 * half);
-#pragma unroll
-        for (int w = 0; w < 4; w++) c[4 * g + w] += t[w];
-    }
-}
-
-
-// S^T column softmax for one query block.  In: raw scores s[bj][r] (keys down the registers, this lane's query).  Out:
-// p[bj][r] = exp(scale (s - max)) (UN-normalised) and the column's 1/sum.  Padded keys (j >= L) only exist in the LAST
-// 32-key block: they are selected away by comparing the (compile-time) accumulator row of register r with one per-lane
-// limit; exp2 with scale * log2(e) folded into one multiply.
-template <int NB>
-__device__ __forceinline__ float ab_softmax_cols(const f32x16 (&s)[NB], float (&p)[NB][16], int klim, float scale_log2e) {
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int bj = 0; bj < NB; bj++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const float v = (bj == NB - 1 && ((r & 3) + 8 * (r >> 2)) >= klim) ? -1.0e30f : s[bj][r];
-            p[bj][r] = v;
-            mx = fmaxf(mx, v);
-        }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    float sum = 0.f;
-#pragma unroll
-    for (int bj = 0; bj < NB; bj++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const float e = fast_exp2((p[bj][r] - mx) * scale_log2e);
-            p[bj][r] = e;
-            sum += e;
-        }
-    sum += __shfl_xor(sum, 32);
-    return 1.0f / sum;
-}
-
-// ... and the same constants as the INITIAL value of the accumulator (bias folded into the first MFMA: no zero fill, no adds)
-__device__ __forceinline__ void acc_load_rows(f32x16& c, const float* p, int half) {
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p + 8 * g + 4 * half);
-#pragma unroll
-        for (int w = 0; w < 4; w++) c[4 * g + w] = t[w];
-    }
-}
 
 template <class T, int C> struct AbSmem {
     static constexpr int KT = C / TileGeom<T>::BK;
@@ -96,74 +52,6 @@ template <class T, int C> struct AbSmem {
     static constexpr int K_LNW = 0, K_LNB = C, K_BQKV = 2 * C, K_BP = 5 * C, K_GAM = 6 * C, NCONST = 7 * C;
     static constexpr int OFF_S = OFF_K + NCONST * 4;      // per-wave scratch (backward only) starts here
 };
-
-// stage a row-major [rows][C] weight matrix into an LDS operand matrix; PERM: the 32-column blocks are stored in
-// accumulator order (position 16 q + 8 half + e holds column (e & 3) + 8 (2 q + (e >> 2)) + 4 half)
-template <class T, int C, bool PERM>
-__device__ __forceinline__ void ab_stage_weights(char* dst, const T* __restrict__ src, int rows, int tid, int nthreads) {
-    constexpr int FPR = C / 8;
-    for (int f = tid; f < rows * FPR; f += nthreads) {
-        const int row = f / FPR, fcg = f % FPR;
-        frag_t<T> v;
-        if (!PERM) {
-            v = frag_load<T>(src + (size_t)row * C + fcg * 8);
-        } else {
-            const int blk = fcg >> 2, q = (fcg >> 1) & 1, half = fcg & 1;
-            const T* p = src + (size_t)row * C + blk * 32 + 16 * q + 4 * half;
-#pragma unroll
-            for (int e = 0; e < 4; e++) { v[e] = p[e]; v[4 + e] = p[8 + e]; }
-        }
-        opm_store_frag<T>(dst, rows, row, fcg, v);
-    }
-}
-
-// token rows of this lane (one per 32-token block of the partition) in operand form: piece (ks, half) = 16 bytes
-template <class T, int C, int NB>
-__device__ __forceinline__ void ab_load_rows(frag_t<T> (&f)[NB][C / 16], const T* __restrict__ src, const int (&tok)[NB],
-                                              const bool (&valid)[NB], int half) {
-#pragma unroll
-    for (int b = 0; b < NB; b++)
-#pragma unroll
-        for (int ks = 0; ks < C / 16; ks++) {
-            const frag_t<T> v = frag_load<T>(src + (size_t)tok[b] * C + (2 * ks + half) * 8);     // padded rows read token 0
-            const frag_t<T> z = frag_zero<T>();
-            f[b][ks] = valid[b] ? v : z;
-        }
-}
-
-// LayerNorm (maxvit.py:229) of the rows held in operand form; keeps mean / rstd for the backward
-template <class T, int C, int NB>
-__device__ __forceinline__ void ab_layernorm(const frag_t<T> (&xf)[NB][C / 16], frag_t<T> (&uf)[NB][C / 16], const float* k_lnw,
-                                              const float* k_lnb, const bool (&valid)[NB], int half, float eps,
-                                              float (&mean)[NB], float (&rstd)[NB]) {
-    constexpr int KS = C / 16;
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        float s = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) s += (float)xf[b][ks][e];
-        s += __shfl_xor(s, 32);
-        mean[b] = s / (float)C;
-        float q = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) { const float d = (float)xf[b][ks][e] - mean[b]; q += d * d; }
-        q += __shfl_xor(q, 32);
-        rstd[b] = 1.0f / sqrtf(q / (float)C + eps);
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) {
-            float w[8], bb[8];
-            load_cols<8>(k_lnw, 16 * ks + 8 * half, w);
-            load_cols<8>(k_lnb, 16 * ks + 8 * half, bb);
-#pragma unroll
-            for (int e = 0; e < 8; e++)
-                uf[b][ks][e] = (T)(valid[b] ? ((float)xf[b][ks][e] - mean[b]) * rstd[b] * w[e] + bb[e] : 0.f);
-        }
-    }
-}
 
 // T-form projection block: acc[feature][token] += W[row0 + .][:] . u[token][:]   (A = weight rows, B = token rows)
 template <class T, int C>
@@ -176,11 +64,6 @@ template <class T, int C>
 __device__ __forceinline__ void ab_proj_n(f32x16& acc, const char* Wl, int wrows, int row0, const frag_t<T> (&uf)[C / 16], int li, int half) {
 #pragma unroll
     for (int ks = 0; ks < C / 16; ks++) mma32(acc, uf[ks], opm_load_frag<T>(Wl, wrows, row0 + li, 2 * ks + half));
-}
-
-template <class T> __device__ __forceinline__ void acc_to_frags(const f32x16& a, frag_t<T> (&f)[2]) {
-    f[0] = acc_slot_frag<T>(a, 0);
-    f[1] = acc_slot_frag<T>(a, 1);
 }
 
 template <int NB> struct AbPart {      // which partition, which token rows
@@ -222,8 +105,8 @@ attn_block_fwd_kernel(const T* __restrict__ x, T* __restrict__ xmid, T* __restri
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, half = lane >> 5, wave = tid >> 6;
     char* const stash = smem + S::OFF_S + wave * STASH_B + lane * 16;
 
-    ab_stage_weights<T, C, false>(Wq_l, Wqkv, 3 * C, tid, 64 * WPB);
-    ab_stage_weights<T, C, true>(Wp_l, Wp, C, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(Wq_l, Wqkv, 3 * C, tid, 64 * WPB);
+    opm_stage_weights<T, C, true>(Wp_l, Wp, C, tid, 64 * WPB);
     for (int i = tid; i < C; i += 64 * WPB) {
         kst[S::K_LNW + i] = LN ? ln_w[i] : 1.f;
         kst[S::K_LNB + i] = LN ? ln_b[i] : 0.f;
@@ -349,42 +232,6 @@ attn_block_fwd_kernel(const T* __restrict__ x, T* __restrict__ xmid, T* __restri
 }
 
 // ==================================================================================================== backward
-// Transposed operand piece in ACCUMULATOR order from a row-major LDS tile X[row][col] (opm layout, `rows` rows):
-//   f[e] = X[row0 + (e & 3) + 8 (e >> 2) + 4 (lane >> 5)][col0 + (lane & 31)],  e = 0..7
-// i.e. the operand "row = column col0 + lane&31, contraction over the 16 rows row0..row0+15" whose slot order matches
-// accumulator registers 8 q .. 8 q + 7 of the other operand (row0 = 16 q within a 32-row block).
-template <class T> __device__ __forceinline__ frag_t<T> ab_tr_frag(char* base, int rows, int row0, int col0, int lane) {
-    if constexpr (sizeof(T) == 2) {
-        const int rl = 4 * (lane >> 5) + ((lane & 15) >> 2), cl = col0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-        return frag_from_tr<T>(reinterpret_cast<const bf16*>(opm_elem_ptr<T>(base, rows, row0 + rl, cl)),
-                               reinterpret_cast<const bf16*>(opm_elem_ptr<T>(base, rows, row0 + rl + 8, cl)));
-    } else {
-        frag_t<T> f;
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            f[e] = *opm_elem_ptr<T>(base, rows, row0 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5), col0 + (lane & 31));
-        return f;
-    }
-}
-
-// write a T-form accumulator block (col = lane & 31 = LDS row, registers = 32 columns col0..col0+31) as 4-element row pieces
-template <class T> __device__ __forceinline__ void ab_acc_to_lds(char* base, int rows, int row, int col0, const float (&v)[16], int half) {
-    typedef __attribute__((ext_vector_type(4))) T vec4;
-#pragma unroll
-    for (int gq = 0; gq < 4; gq++) {
-        vec4 t;
-#pragma unroll
-        for (int w = 0; w < 4; w++) t[w] = (T)v[4 * gq + w];
-        *reinterpret_cast<vec4*>(opm_elem_ptr<T>(base, rows, row, col0 + 8 * gq + 4 * half)) = t;
-    }
-}
-
-template <class T, int NB> struct AbBwdScratch {          // per wave: P and dS blocks [32 queries][32 NB keys]
-    static constexpr int KTJ = 32 * NB * (int)sizeof(T) / 128 + ((32 * NB * (int)sizeof(T)) % 128 ? 1 : 0);
-    static constexpr int ONE = KTJ * 32 * 128;
-    static constexpr int BYTES = 2 * ONE;
-};
-
 // dx = dxmid + LN1'( dqkv Wqkv ; x ),  dqkv = attention backward of da = dxmid (gamma Wp)   — dqkv (and u = LN1(x)) go to
 // HBM for the qkv weight-gradient GEMM; LayerNorm parameter gradients leave as one atomic per channel per workgroup.
 // (Measured and dropped in round 2: the qkv weight gradient accumulated inside this kernel — dqkv blocks transposed by
@@ -423,7 +270,7 @@ attn_block_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dxmid, T* _
     // LayerNorm parameter gradients = column sums over tokens of du * xhat and du: the row pieces hold tokens in the LANES; an
     // MFMA against an identity operand turns a piece block into "col = channel, registers = tokens" (exact), where the column
     // sum is an in-lane sum — one running value per 32-channel block instead of per-lane partial sums for every channel
-    frag_t<T> idf[2];
+    frag_t<T> idf[2];              // (make_identity_frags of acc_frags.hpp, written out: through the call hipcc allocates two instantiations differently)
 #pragma unroll
     for (int m = 0; m < 2; m++)
 #pragma unroll
@@ -432,8 +279,8 @@ attn_block_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dxmid, T* _
 #pragma unroll
     for (int cb = 0; cb < NCB; cb++) { aw[cb] = 0.f; ab[cb] = 0.f; }
 
-    ab_stage_weights<T, C, false>(Wq_l, Wqkv, 3 * C, tid, 64 * WPB);
-    ab_stage_weights<T, C, false>(Wp_l, WpgT, C, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(Wq_l, Wqkv, 3 * C, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(Wp_l, WpgT, C, tid, 64 * WPB);
     for (int i = tid; i < C; i += 64 * WPB) {
         kst[S::K_LNW + i] = (LN || PRE) ? ln_w[i] : 1.f;
         kst[S::K_LNB + i] = LN ? ln_b[i] : 0.f;

@@ -1,6 +1,6 @@
 // Partitioned multi-head self-attention core (reference maxvit.py:343-354 minus the two linears, on the partitions of
-// :273-304) for the stages whose attention half is not fused (attn_block.hpp): same contract as the kernels of attn.hpp
-// (qkv [F*H*W][3C] in image token order, per-head [q|k|v]; one wave per (frame, partition, head)), rebuilt on the
+// :273-304) for the stages whose attention half is not fused (attn_block.hpp): the contract of attn_pieces.hpp
+// (qkv [F*H*W][3C] in image token order, per-head [q|k|v]; one wave per (frame, partition, head)), built on the
 // accumulator-to-operand chaining of attn_block.hpp:
 //   * Q, K, V, dO rows come from HBM in operand form = the "row token, contract d" operands of S^T = K Q^T and dP^T = V dO^T;
 //   * the "row d, contract token" operands (V for O^T = V^T P^T; K, Q, dO for dQ^T, dK^T, dV^T) are transposes of those rows:
@@ -10,18 +10,14 @@
 //     come back through the transposing LDS read;
 //   * dQ^T, dK^T, dV^T leave as 16-byte row pieces (v_permlane32_swap) instead of being staged through LDS.
 #pragma once
-#include "attn_block.hpp"
+#include "common.hpp"
+#include "attn_pieces.hpp"      // AttnGeom, load_chunk, ab_softmax_cols, AbBwdScratch
+#include "opm.hpp"              // ab_acc_to_lds, ab_tr_frag: the P / dS trip through LDS
+#include "acc_frags.hpp"        // acc_slot_frag, arr_slot_frag, make_identity_frags, wave_lds_sync
 #include "line_bounce.hpp"
 
 namespace rvt {
 
-// identity operand pieces of a 32-column block: row n = lane & 31, k-step cc: 1 at slot k = 16 cc + 8 half + e == n
-template <class T> __device__ __forceinline__ void make_identity_frags(frag_t<T> (&idf)[2], int li, int half) {
-#pragma unroll
-    for (int cc = 0; cc < 2; cc++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) idf[cc][e] = (T)((16 * cc + 8 * half + e == li) ? 1.0f : 0.0f);
-}
 // rows held in operand form (lane = row, pieces cc = 0, 1) -> the transposed operand "row = column, contract over the 32 rows"
 template <class T> __device__ __forceinline__ void transpose_rows(const frag_t<T> (&rows)[2], const frag_t<T> (&idf)[2], frag_t<T> (&out)[2]) {
     f32x16 acc;

@@ -1,6 +1,8 @@
 // Shared pieces of the partitioned multi-head self-attention kernels (reference maxvit.py:343-354 on the partitions of
-// maxvit.py:273-304): partition geometry / token addressing, operand-chunk loads, the in-lane column softmax.  The kernels
-// themselves are in attn_core2.hpp (attention core on a saved qkv tensor) and attn_block.hpp (fused attention half).
+// maxvit.py:273-304): partition geometry / token addressing (AttnGeom, attn_token), operand-chunk loads (load_chunk), the
+// 4-channel row store (store4), the in-lane column softmax (ab_softmax_cols) and the backward's P / dS scratch layout
+// (AbBwdScratch).  No kernel: those are in attn_core2.hpp (attention core on a saved qkv tensor) and attn_block.hpp
+// (fused attention half); the accumulator <-> operand conversions they chain products with are in acc_frags.hpp.
 //
 // The qkv activations stay in IMAGE token order [F*H*W][3C] (per-head channel layout [q|k|v], dh each — reference
 // maxvit.py:347); window / grid partitioning is pure index arithmetic on the token rows that a partition gathers, so the
@@ -15,16 +17,6 @@
 #include "common.hpp"
 
 namespace rvt {
-
-// LDS hand-off between the lanes of ONE wave (private slice): DS operations of a wave execute in issue order, so draining
-// lgkmcnt (plus a compiler barrier) is all the synchronisation there is to do — no s_barrier across the workgroup.
-__device__ __forceinline__ void wave_lds_sync() {
-#ifdef RVT_EMU
-    emu::wave_barrier();          // emulator: lanes are fibers; the LDS hand-off is between the lanes of this wave only
-#else
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-}
 
 struct AttnGeom {
     int F, H, W, C, dh, heads, ph, pw, L, window;   // L = ph*pw
@@ -61,18 +53,40 @@ template <class T> __device__ __forceinline__ void store4(T* dst, float a, float
     *reinterpret_cast<vec4*>(dst) = v;
 }
 
-template <class T> __device__ __forceinline__ frag_t<T> acc_slot_frag(const f32x16& a, int q) {
-    frag_t<T> f;
+// S^T column softmax for one query block.  In: raw scores s[bj][r] (keys down the registers, this lane's query).  Out:
+// p[bj][r] = exp(scale (s - max)) (UN-normalised) and the column's 1/sum.  Padded keys (j >= L) only exist in the LAST
+// 32-key block: they are selected away by comparing the (compile-time) accumulator row of register r with one per-lane
+// limit; exp2 with scale * log2(e) folded into one multiply.
+template <int NB>
+__device__ __forceinline__ float ab_softmax_cols(const f32x16 (&s)[NB], float (&p)[NB][16], int klim, float scale_log2e) {
+    float mx = -3.0e38f;
 #pragma unroll
-    for (int e = 0; e < 8; e++) f[e] = (T)a[8 * q + e];
-    return f;
+    for (int bj = 0; bj < NB; bj++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float v = (bj == NB - 1 && ((r & 3) + 8 * (r >> 2)) >= klim) ? -1.0e30f : s[bj][r];
+            p[bj][r] = v;
+            mx = fmaxf(mx, v);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float sum = 0.f;
+#pragma unroll
+    for (int bj = 0; bj < NB; bj++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float e = fast_exp2((p[bj][r] - mx) * scale_log2e);
+            p[bj][r] = e;
+            sum += e;
+        }
+    sum += __shfl_xor(sum, 32);
+    return 1.0f / sum;
 }
 
-template <class T> __device__ __forceinline__ frag_t<T> arr_slot_frag(const float (&a)[16], int q) {
-    frag_t<T> f;
-#pragma unroll
-    for (int e = 0; e < 8; e++) f[e] = (T)a[8 * q + e];
-    return f;
-}
+// LDS scratch of the backward kernels (attn_block.hpp, attn_core2.hpp)
+template <class T, int NB> struct AbBwdScratch {          // per wave: P and dS blocks [32 queries][32 NB keys]
+    static constexpr int KTJ = 32 * NB * (int)sizeof(T) / 128 + ((32 * NB * (int)sizeof(T)) % 128 ? 1 : 0);
+    static constexpr int ONE = KTJ * 32 * 128;
+    static constexpr int BYTES = 2 * ONE;
+};
 
 }  // namespace rvt

@@ -1,6 +1,8 @@
-// extern "C" entry points, part 6: partition attention (attn.hpp, attn_core2.hpp) and the fused attention half (attn_block.hpp).
+// extern "C" entry points, part 6: partition attention (attn_pieces.hpp, attn_core2.hpp) and the fused attention half (attn_block.hpp).
 #include "host.hpp"
-#include "attn.hpp"
+#include "fold.hpp"             // launches nothing here: this part has always carried the three static fold kernels (they came in
+                                // behind line_bounce.hpp), and its device code is held byte-identical across the header untangle
+#include "attn_pieces.hpp"
 #include "attn_block.hpp"
 #include "attn_core2.hpp"
 

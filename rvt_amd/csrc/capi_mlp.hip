@@ -1,6 +1,6 @@
 // extern "C" entry points, part 5: fused MLP halves (mlp.hpp, mlp_chain.hpp) and the LayerNorm-backward GEMM (dgrad_ln.hpp).
 #include "host.hpp"
-#include "gemm.hpp"
+#include "fold.hpp"
 #include "dgrad_ln.hpp"
 #include "mlp.hpp"
 #include "mlp_chain.hpp"

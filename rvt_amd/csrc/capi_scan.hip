@@ -1,6 +1,6 @@
 // extern "C" entry points, part 8: ConvLSTM with the time loop inside the kernel (lstm_scan.hpp).
 #include "host.hpp"
-#include "gemm.hpp"
+#include "fold.hpp"
 #include "lstm_scan.hpp"
 #include "lstm_scan2.hpp"
 #include "lstm_scan3.hpp"

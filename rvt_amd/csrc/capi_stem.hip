@@ -1,5 +1,7 @@
 // extern "C" entry points, part 4: the stem on the loader's uint8 planes (stem.hpp).
 #include "host.hpp"
+#include "fold.hpp"             // launches nothing here: this part has always carried the three static fold kernels (they came in
+                                // behind line_bounce.hpp), and its device code is held byte-identical across the header untangle
 #include "stem.hpp"
 
 using namespace rvt;

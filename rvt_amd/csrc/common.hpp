@@ -316,6 +316,12 @@ __device__ __forceinline__ void drain_vmem() {
 #endif
 }
 
+// reduce over groups of G consecutive lanes (G power of two <= 64)
+__device__ __forceinline__ float group_sum(float v, int G) {
+    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
 // sum over the 16 lanes of a DPP row (lanes 16 r .. 16 r + 15), result in all of them: four row rotations
 __device__ __forceinline__ float row16_sum(float v) {
 #ifdef RVT_EMU

@@ -13,7 +13,9 @@
 // mlpc_bwd_dgrad_kernel.  HBM traffic: dy + x + add in, dx out - du never exists.  No VALU-heavy element function anywhere: the
 // kernel is bound by its dy stream.
 #pragma once
-#include "mlp_chain.hpp"
+#include "common.hpp"
+#include "opm.hpp"              // opm_stage_weights, load_cols
+#include "acc_frags.hpp"        // make_identity_frags, wave_lds_sync
 
 namespace rvt {
 
@@ -42,7 +44,7 @@ dgrad_ln_kernel(const T* __restrict__ dy, const T* __restrict__ W, const T* __re
     float* const kst = reinterpret_cast<float*>(smem + S::W_BYTES);
     char* const scr = smem + S::OFF_SCR + (threadIdx.x >> 6) * S::SCR_WAVE;
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, half = lane >> 5, wave = tid >> 6;
-    chain_stage_weights<T, C, false>(W_l, W, K, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(W_l, W, K, tid, 64 * WPB);
     for (int i = tid; i < C; i += 64 * WPB) kst[i] = ln_w[i];
     __syncthreads();
 
@@ -226,7 +228,7 @@ dgrad_ln_kernel(const T* __restrict__ dy, const T* __restrict__ W, const T* __re
         // pass 3: LayerNorm parameter gradients = column sums over the 32 tokens of du xhat and du.  The row pieces hold tokens in
         // the LANES; an MFMA against an identity operand turns a piece into "col = channel, registers = tokens" (exact), where the
         // column sum is an in-lane sum.  (After the stores: with these accumulators alive beside pass 1 the kernel spilled.)
-        frag_t<T> idf[2];
+        frag_t<T> idf[2];          // (make_identity_frags of acc_frags.hpp, written out: through the call hipcc schedules this kernel differently)
 #pragma unroll
         for (int m = 0; m < 2; m++)
 #pragma unroll

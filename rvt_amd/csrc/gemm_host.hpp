@@ -2,6 +2,7 @@
 #pragma once
 #include "host.hpp"
 #include "gemm.hpp"
+#include "fold.hpp"
 #include "ppgemm.hpp"
 #include "ppgemm_tn.hpp"
 

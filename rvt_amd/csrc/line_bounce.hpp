@@ -1,8 +1,8 @@
 // Row hand-over helpers of the chained ("T-form": lane = token) kernels: exact-range buffer resources for a wave's 32-row tile and
-// full-line stores through a per-wave LDS bounce.
+// full-line stores through a per-wave LDS bounce.  No kernel.
 #pragma once
 #include "common.hpp"
-#include "ppgemm.hpp"
+#include "lds_dma.hpp"          // pp_rsrc, pp_make_rsrc, pp_store16
 
 namespace rvt {
 

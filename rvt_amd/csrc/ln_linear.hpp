@@ -11,9 +11,9 @@
 // per lane.  The waves never synchronise after the image has landed; the next tile's rows are in flight while a tile computes.
 #pragma once
 #include "common.hpp"
-#include "mlp_chain.hpp"
-#include "mlp_stream.hpp"
-#include "ppgemm.hpp"
+#include "lds_dma.hpp"          // pp_*: weight image and row accesses; ms_*: reads of the image
+#include "acc_frags.hpp"        // acc_load_rows
+#include "ln_pieces.hpp"        // mc_layernorm
 #include "line_bounce.hpp"
 #include "gelu_lut.hpp"
 

@@ -16,7 +16,7 @@
 // registers in that layout.
 #pragma once
 #include "common.hpp"
-#include "mlp.hpp"
+#include "opm.hpp"
 
 namespace rvt {
 

@@ -16,9 +16,8 @@
 // What bounds these kernels afterwards is the gate math itself: 10 quarter-rate transcendentals per (token, channel) and step.
 #pragma once
 #include "common.hpp"
-#include "mlp.hpp"
-#include "attn_block.hpp"
-#include <utility>
+#include "opm.hpp"
+#include "acc_frags.hpp"        // acc_load_rows, static_for
 
 namespace rvt {
 
@@ -295,10 +294,6 @@ struct Tr2 {
     }
 };
 
-template <int N> struct IntC { static constexpr int v = N; };
-template <int... I, class F> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(IntC<I>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 __global__ void __launch_bounds__(512)
 lstm_scan2_bwd_kernel(const bf16* __restrict__ x_all, const bf16* __restrict__ Hall, const bf16* __restrict__ Csave,
                       const float* __restrict__ c0, const bf16* __restrict__ dH, const float* __restrict__ dc_last,
@@ -376,7 +371,7 @@ lstm_scan2_bwd_kernel(const bf16* __restrict__ x_all, const bf16* __restrict__ H
                 __builtin_amdgcn_s_sleep(SCAN2_HELPER_SLEEP);
 #endif
                 static_for<4>([&](auto kq) __attribute__((always_inline)) {
-                    constexpr int K0 = 16 * decltype(kq)::v;
+                    constexpr int K0 = 16 * decltype(kq)::value;
                     frag_t<T> a[2], b[4];
 #pragma unroll
                     for (int i = 0; i < 2; i++) a[i] = tr_dz[i].load<K0>(Adz);
@@ -558,7 +553,7 @@ lstm_scan2_bwd_kernel(const bf16* __restrict__ x_all, const bf16* __restrict__ H
                 auto p2load = [&](auto pp, int buf) __attribute__((always_inline)) {
 #pragma unroll
                     for (int u = 0; u < 2; u++) { }
-                    constexpr int KC0 = 32 * decltype(pp)::v, KC1 = KC0 + 16;   // (compile-time k-steps: LDS address = per-lane term ^ constant + immediate)
+                    constexpr int KC0 = 32 * decltype(pp)::value, KC1 = KC0 + 16;   // (compile-time k-steps: LDS address = per-lane term ^ constant + immediate)
                     pb[buf][0] = *reinterpret_cast<const frag_t<T>*>(Adz + (KC0 >> 6) * 8192 + ((r_hs ^ (((KC0 >> 3) & 6) << 4)) + r_base));
                     pb[buf][1] = *reinterpret_cast<const frag_t<T>*>(Adz + (KC1 >> 6) * 8192 + ((r_hs ^ (((KC1 >> 3) & 6) << 4)) + r_base));
                     pax[buf][0] = tr_w.load<KC0>(smem + S::OFF_WX);
@@ -566,10 +561,10 @@ lstm_scan2_bwd_kernel(const bf16* __restrict__ x_all, const bf16* __restrict__ H
                     pax[buf][1] = tr_w.load<KC1>(smem + S::OFF_WX);
                     pah[buf][1] = tr_w.load<KC1>(smem + S::OFF_WH);
                 };
-                p2load(IntC<0>{}, 0);
+                p2load(std::integral_constant<int, 0>(), 0);
                 static_for<8>([&](auto pp) __attribute__((always_inline)) {
-                    constexpr int PP = decltype(pp)::v;
-                    if constexpr (PP + 1 < 8) p2load(IntC<PP + 1>{}, (PP + 1) & 1);
+                    constexpr int PP = decltype(pp)::value;
+                    if constexpr (PP + 1 < 8) p2load(std::integral_constant<int, PP + 1>(), (PP + 1) & 1);
                     sched_fence();
 #pragma unroll
                     for (int u = 0; u < 2; u++) {

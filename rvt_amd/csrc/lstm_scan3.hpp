@@ -24,8 +24,8 @@
 // HBM per token-step: forward x + h + c + 4 gates = 7 rows of C; backward dH + c + 4 gates + dz (4) + dx = 11 (per-step route: 16 / 22).
 #pragma once
 #include "common.hpp"
-#include "mlp.hpp"
-#include "ppgemm.hpp"
+#include "opm.hpp"
+#include "lds_dma.hpp"
 
 namespace rvt {
 

@@ -19,51 +19,14 @@
 //   the next A operand, to LDS; second MFMA; final epilogue (LayerScale+residual / LayerNorm backward) in the same
 //   (row, chunk) layout, with the raw input tile still in registers.
 // JC = 128 (bf16) / 64 (f32) so that all operands fit the 160 KiB LDS.
+//
+// Besides the kernels this file keeps what only they use: opm_mma, the fp32 staging passes, the panel prefetch.  The operand-major
+// LDS matrix itself (opm_*, load_cols) is opm.hpp's; group_sum is common.hpp's.
 #pragma once
 #include "common.hpp"
-#include "rowops.hpp"
+#include "opm.hpp"              // the operand-major LDS matrix, load_cols
 
 namespace rvt {
-
-// ---- LDS operand matrix: [rows][K] stored as K/BK sub-tiles of [rows][128 bytes], XOR-swizzled like GEMM tiles ----
-template <class T> __device__ __forceinline__ char* opm_subtile(char* base, int rows, int kt) { return base + (size_t)kt * rows * 128; }
-
-// store an 8-element fragment at (row, kcol0 = 8*fcg)
-template <class T> __device__ __forceinline__ void opm_store_frag(char* base, int rows, int row, int fcg, const frag_t<T>& v) {
-    constexpr int FPR = TileGeom<T>::FPR;
-    tile_store_frag<T>(opm_subtile<T>(base, rows, fcg / FPR), row, fcg % FPR, v);
-}
-
-// address of element (row, kcol) of an LDS operand matrix [rows][K] (K-subtiles of [rows][128 B], swizzled 16-B chunks)
-template <class T> __device__ __forceinline__ T* opm_elem_ptr(char* base, int rows, int row, int kcol) {
-    constexpr int BK = TileGeom<T>::BK;
-    const int kt = kcol / BK, kc = kcol % BK;
-    const int byte = kc * (int)sizeof(T);
-    return reinterpret_cast<T*>(base + (size_t)kt * rows * 128 + lds_chunk_off(row, byte >> 4) + (byte & 15));
-}
-template <class T> __device__ __forceinline__ frag_t<T> opm_load_frag(const char* base, int rows, int row, int fcg) {
-    constexpr int FPR = TileGeom<T>::FPR;
-    return tile_load_frag<T>(base + (size_t)(fcg / FPR) * rows * 128, row, fcg % FPR);
-}
-
-// LDS byte offset of element (R0 + rowc(r), ch) of a swizzled tile, r = accumulator register index of the 32x32 MFMA C/D
-// layout, GIVEN the offset `base` of element (R0, ch) with R0 = 32*w + 4*(lane>>5): rowc(r) = (r&3) + 8*(r>>2) never
-// carries out of the low five row bits, so the two swizzle terms of lds_chunk_off split into a per-lane part (already in
-// `base`) XOR a function of r alone:  ((row>>1)&7) -> ((r>>1)&1) | ((r>>2)&1)<<2,  ((row>>4)&7) -> (r>>3).
-// One v_xor plus an immediate offset per access instead of a dozen integer ops, and ONE register instead of sixteen.
-__device__ __forceinline__ int acc_elem_off(int base, int r) {
-    const int k = (((r >> 1) & 1) | (((r >> 2) & 1) << 2)) ^ ((r >> 3) & 1);
-    return (base ^ (k << 4)) + ((r & 3) + 8 * (r >> 2)) * 128;
-}
-
-// stage a row-major global block [rows][kcols] (leading dimension ld elements) into an operand matrix; all 256 threads
-template <class T> __device__ __forceinline__ void opm_stage(char* base, const T* g, int ld, int rows, int kcols, int tid) {
-    const int fpr_g = kcols / 8;
-    for (int f = tid; f < rows * fpr_g; f += 256) {
-        const int row = f / fpr_g, fcg = f % fpr_g;
-        opm_store_frag<T>(base, rows, row, fcg, frag_load<T>(g + (size_t)row * ld + fcg * 8));
-    }
-}
 
 // acc[i][j] += A[a_row0 + 32 i + .][0..ktot) . B[b_row0 + 32 j + .][0..ktot)
 template <class T, int MI, int NJ>
@@ -183,14 +146,6 @@ template <class T, int C, int TM> struct MlpPanels {       // register image of 
         }
     }
 };
-
-template <int N> __device__ __forceinline__ void load_cols(const float* p, int c0, float (&v)[N]) {
-#pragma unroll
-    for (int q = 0; q < N / 4; q++) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p + c0 + q * 4);
-        v[q * 4 + 0] = t[0]; v[q * 4 + 1] = t[1]; v[q * 4 + 2] = t[2]; v[q * 4 + 3] = t[3];
-    }
-}
 
 // ===================================================================================================== forward
 template <class T, int C, int TM>

@@ -20,29 +20,12 @@
 // (7 GB fetched for 2 GB of input) and two waves per SIMD do not hide the load latency.  Removed)
 #pragma once
 #include "common.hpp"
-#include "attn_block.hpp"
+#include "opm.hpp"              // the weight images: opm_stage_weights, opm_load_frag, ab_tr_frag
+#include "acc_frags.hpp"        // acc_load_rows, arr_slot_frag, make_identity_frags
+#include "ln_pieces.hpp"        // mc_load_row, mc_layernorm
 #include "gelu_lut.hpp"
 
 namespace rvt {
-
-// stage a row-major [rows][K] weight matrix into an LDS operand matrix; PERM: 32-column blocks in accumulator order
-template <class T, int K, bool PERM>
-__device__ __forceinline__ void chain_stage_weights(char* dst, const T* __restrict__ src, int rows, int tid, int nthreads) {
-    constexpr int FPR = K / 8;
-    for (int f = tid; f < rows * FPR; f += nthreads) {
-        const int row = f / FPR, fcg = f % FPR;
-        frag_t<T> v;
-        if (!PERM) {
-            v = frag_load<T>(src + (size_t)row * K + fcg * 8);
-        } else {
-            const int blk = fcg >> 2, q = (fcg >> 1) & 1, half = fcg & 1;
-            const T* p = src + (size_t)row * K + blk * 32 + 16 * q + 4 * half;
-#pragma unroll
-            for (int e = 0; e < 4; e++) { v[e] = p[e]; v[4 + e] = p[8 + e]; }
-        }
-        opm_store_frag<T>(dst, rows, row, fcg, v);
-    }
-}
 
 template <class T, int C> struct McSmem {
     static constexpr int KT = C / TileGeom<T>::BK, HID = 4 * C;
@@ -50,46 +33,6 @@ template <class T, int C> struct McSmem {
     static constexpr int W_2 = (HID / TileGeom<T>::BK) * C * 128;  // [C rows][4C]   (forward: W2, columns in accumulator order)
     static constexpr int K_LNW = 0, K_LNB = C, K_B2 = 2 * C, K_GAM = 3 * C, K_B1 = 4 * C, NCONST = 8 * C;
 };
-
-// one token row per lane (row = tile * 32 + lane & 31) in operand form; LayerNorm in place
-template <class T, int C>
-__device__ __forceinline__ void mc_load_row(frag_t<T> (&f)[C / 16], const T* __restrict__ src, int row, bool valid, int half) {
-#pragma unroll
-    for (int ks = 0; ks < C / 16; ks++) {
-        const frag_t<T> v = frag_load<T>(src + (size_t)(valid ? row : 0) * C + (2 * ks + half) * 8);
-        const frag_t<T> z = frag_zero<T>();
-        f[ks] = valid ? v : z;
-    }
-}
-template <class T, int C>
-__device__ __forceinline__ void mc_layernorm(const frag_t<T> (&xf)[C / 16], frag_t<T> (&uf)[C / 16], const float* k_lnw,
-                                              const float* k_lnb, bool valid, int half, float eps, float& mean, float& rstd) {
-    constexpr int KS = C / 16;
-    float s = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) s += (float)xf[ks][e];
-    s += __shfl_xor(s, 32);
-    mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) { const float d = (float)xf[ks][e] - mean; q += d * d; }
-    q += __shfl_xor(q, 32);
-    rstd = 1.0f / sqrtf(q / (float)C + eps);
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++) {
-        float w[8], bb[8];
-        load_cols<8>(k_lnw, 16 * ks + 8 * half, w);
-        load_cols<8>(k_lnb, 16 * ks + 8 * half, bb);
-        frag_t<T> o;
-#pragma unroll
-        for (int e = 0; e < 8; e++) o[e] = (T)(valid ? ((float)xf[ks][e] - mean) * rstd * w[e] + bb[e] : 0.f);
-        uf[ks] = o;
-    }
-}
 
 // ===================================================================================================== forward
 template <class T, int C, int WPB, int MINW>
@@ -106,8 +49,8 @@ mlpc_fwd_kernel(const T* __restrict__ xmid, T* __restrict__ xout, const float* _
     float* const lut = kst + S::NCONST;
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, half = lane >> 5, wave = tid >> 6;
     GeluTab<T>::template fill<false>(lut, tid, 64 * WPB);
-    chain_stage_weights<T, C, false>(W1_l, W1, HID, tid, 64 * WPB);
-    chain_stage_weights<T, HID, true>(W2_l, W2, C, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(W1_l, W1, HID, tid, 64 * WPB);
+    opm_stage_weights<T, HID, true>(W2_l, W2, C, tid, 64 * WPB);
     for (int i = tid; i < C; i += 64 * WPB) {
         kst[S::K_LNW + i] = ln_w[i]; kst[S::K_LNB + i] = ln_b[i]; kst[S::K_B2 + i] = b2[i]; kst[S::K_GAM + i] = gamma[i];
     }
@@ -203,8 +146,8 @@ mlpc_bwd_dgrad_kernel(const T* __restrict__ dxout, const T* __restrict__ xmid, T
     float* const lut = kst + S::NCONST;
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, half = lane >> 5, wave = tid >> 6;
     GeluTab<T>::template fill<true>(lut, tid, 64 * WPB);
-    chain_stage_weights<T, C, false>(W1_l, W1, HID, tid, 64 * WPB);
-    chain_stage_weights<T, C, false>(W2_l, W2gT, HID, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(W1_l, W1, HID, tid, 64 * WPB);
+    opm_stage_weights<T, C, false>(W2_l, W2gT, HID, tid, 64 * WPB);
     for (int i = tid; i < C; i += 64 * WPB) { kst[S::K_LNW + i] = ln_w[i]; kst[S::K_LNB + i] = ln_b[i]; }
     for (int i = tid; i < HID; i += 64 * WPB) kst[S::K_B1 + i] = b1[i];
     __syncthreads();
@@ -213,10 +156,7 @@ mlpc_bwd_dgrad_kernel(const T* __restrict__ dxout, const T* __restrict__ xmid, T
     // an MFMA against an identity operand turns a piece block into "col = channel, registers = tokens" (exact), where the
     // column sum is an in-lane sum: one accumulator per 32-channel block instead of 2 x 32 per-lane partial sums.
     frag_t<T> idf[2];
-#pragma unroll
-    for (int m = 0; m < 2; m++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) idf[m][e] = (T)((16 * m + 8 * half + e == li) ? 1.0f : 0.0f);
+    make_identity_frags<T>(idf, li, half);
     float aw[NCB], ab[NCB];                                          // dln_w / dln_b of channel 32 cb + (lane & 31), this half's tokens
 #pragma unroll
     for (int cb = 0; cb < NCB; cb++) { aw[cb] = 0.f; ab[cb] = 0.f; }

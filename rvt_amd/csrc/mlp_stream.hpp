@@ -20,8 +20,11 @@
 // GELU' stored 4C wide by the forward, read back by two input-gradient and two weight-gradient GEMMs).
 #pragma once
 #include "common.hpp"
-#include "mlp_chain.hpp"
-#include "ppgemm.hpp"
+#include "lds_dma.hpp"          // pp_*: the weight stream; ms_*: its LDS image
+#include "opm.hpp"
+#include "acc_frags.hpp"
+#include "ln_pieces.hpp"        // mc_load_row, mc_layernorm
+#include "gelu_lut.hpp"
 
 namespace rvt {
 
@@ -36,56 +39,11 @@ template <class T, int C, int HC_ = TileGeom<T>::BK> struct MsGeom {
     static constexpr int K_LNW = 0, K_LNB = C, K_B2 = 2 * C, K_GAM = 3 * C, K_B1 = 4 * C, NCONST = 8 * C;
 };
 
-// LDS image of a streamed chunk: sub-tiles of [rows][128 B] with the 16-byte chunk index XOR (row >> 1) & 7 — the first term of
-// lds_chunk_off only.  (Its second term spreads the WRITES of the transposing loader; an LDS-DMA image has no such writer, and
-// with it the swizzle of row 32 cb + li would depend on cb: one address register per (cb, chunk) instead of one per chunk.)
-// A fragment address is (row * 128 + swz * 16) ^ (chunk * 16): a per-lane base XOR a compile-time constant.
-__device__ __forceinline__ int ms_swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ int ms_rowbase(int row) { return row * 128 + (ms_swz(row) << 4); }
-// ... and the lane's half (k-slots 8 half .. of a k-step = fragment 2 ks + half) folded into the per-lane base as well: every
-// fragment address of a lane is then ONE of a few registers (base ^ compile-time chunk) plus an immediate offset
-template <class T> __device__ __forceinline__ int ms_rowbase_h(int row, int half) { return ms_rowbase(row) ^ ((half * TileGeom<T>::CPF) << 4); }
-template <int I, int N, class F> __device__ __forceinline__ void ms_static_for_impl(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>()); ms_static_for_impl<I + 1, N>(f); }
-}
-template <int N, class F> __device__ __forceinline__ void ms_static_for(F&& f) { ms_static_for_impl<0, N>(f); }
-// fragment fcg (8 elements; the EVEN index 2 ks when `rb` comes from ms_rowbase_h) of the row whose base is `rb`, in a sub-tile
-// array with `rows` rows per sub-tile
-template <class T> __device__ __forceinline__ frag_t<T> ms_load_frag(const char* base, int rows, int rb, int fcg) {
-    constexpr int FPR = TileGeom<T>::FPR, CPF = TileGeom<T>::CPF;
-    const char* const t = base + (fcg / FPR) * rows * 128;
-    frag_t<T> v;
-    u32x4* dst = reinterpret_cast<u32x4*>(&v);
-#pragma unroll
-    for (int c = 0; c < CPF; c++) dst[c] = *reinterpret_cast<const u32x4*>(t + (rb ^ ((((fcg % FPR) * CPF + c)) << 4)));
-    return v;
-}
-template <class T> __device__ __forceinline__ void ms_store_frag(char* base, int rows, int rb, int fcg, const frag_t<T>& v) {
-    constexpr int FPR = TileGeom<T>::FPR, CPF = TileGeom<T>::CPF;
-    char* const t = base + (fcg / FPR) * rows * 128;
-    const u32x4* src = reinterpret_cast<const u32x4*>(&v);
-#pragma unroll
-    for (int c = 0; c < CPF; c++) *reinterpret_cast<u32x4*>(t + (rb ^ ((((fcg % FPR) * CPF + c)) << 4))) = src[c];
-}
 // rows of a 32-row block with bits 2 and 3 of the index exchanged: lane li supplies row ms_rowperm(li) as the A operand of
 // the fc1 product, so that accumulator register 8 q + e (row (e & 3) + 8 (2 q + (e >> 2)) + 4 half) holds hidden unit
 // 16 q + 8 half + e — the k-slot order of a PLAIN 16-byte fragment of W2.  (mlp_chain.hpp permutes the columns of W2 instead
 // when it stages them; an LDS-DMA cannot permute inside its 16-byte pieces.)
 __device__ __forceinline__ int ms_rowperm(int li) { return (li & ~12) | ((li & 4) << 1) | ((li & 8) >> 1); }
-
-// per-lane source offsets (bytes) of this wave's LDS-DMA pieces: piece p = wave + i * WPB of a [rows][ld] matrix chunk whose
-// LDS image is `subtiles` sub-tiles of [rows_per_subtile][128 B] (lane -> row 8 p' + lane / 8, chunk position lane % 8)
-template <class T, int NPW, int WPB>
-__device__ __forceinline__ void ms_piece_offsets(int (&v)[NPW], int wave, int lane, int rows_per_subtile, int ld) {
-    constexpr int EPC = 16 / (int)sizeof(T);              // elements per 16-byte chunk
-    const int rgs = rows_per_subtile / 8;                 // 1-KiB pieces per sub-tile
-#pragma unroll
-    for (int i = 0; i < NPW; i++) {
-        const int p = wave + i * WPB, kt = p / rgs, r = (p % rgs) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ms_swz(r);
-        v[i] = (r * ld + kt * TileGeom<T>::BK + c * EPC) * (int)sizeof(T);
-    }
-}
 
 // ===================================================================================================== forward
 // ABL: ablation bits for profiles/probes/mlps_probe.hip (0 in the library): 1 no weight stream after the first two chunks (no LDS-DMA,
@@ -446,9 +404,9 @@ mlps_bwd_dgrad_kernel(const T* __restrict__ dxout, const T* __restrict__ xmid, T
                 // are dead by then), in flight under the GELU' gathers, waited for in front of the dv2 products
                 sched_fence();
                 frag_t<T> wt[NCB][2];
-                ms_static_for<JPC>([&](auto jj_c) {
+                static_for<JPC>([&](auto jj_c) {
                     if (decltype(jj_c)::value != jj) return;
-                    ms_static_for<NCB * 2>([&](auto i_c) {
+                    static_for<NCB * 2>([&](auto i_c) {
                         constexpr int JJ = decltype(jj_c)::value, CB = decltype(i_c)::value / 2, Q = decltype(i_c)::value % 2;
                         if constexpr (sizeof(T) == 2) wt[CB][Q] = ms_tr_frag<STG * STAGE, G::HC, 32 * JJ + 16 * Q, CB>(smem, ta);
                         else wt[CB][Q] = ms_tr_frag_f32<G::HC>(W1s, 32 * JJ + 16 * Q, CB * 32, lane);
@@ -506,7 +464,7 @@ mlps_bwd_dgrad_kernel(const T* __restrict__ dxout, const T* __restrict__ xmid, T
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) xf[ks] = frag_load<T>(xmid + (size_t)(valid ? row : 0) * C + (2 * ks + half) * 8);
         // LayerNorm backward + residual in operand-piece form (mlp_chain.hpp)
-        frag_t<T> idf[2];
+        frag_t<T> idf[2];          // (make_identity_frags of acc_frags.hpp, written out: the call moves a line of this kernel's assembly)
 #pragma unroll
         for (int m = 0; m < 2; m++)
 #pragma unroll
@@ -756,11 +714,11 @@ mlps_bwd_wgrad_kernel(const bf16* __restrict__ dxout, const bf16* __restrict__ x
         const int vb = (int)(size_t)(__attribute__((address_space(3))) const char*)(v2t);
         const int db_ = (int)(size_t)(__attribute__((address_space(3))) const char*)(dxt);
 #endif
-        ms_static_for<NCB>([&](auto cb_c) {
+        static_for<NCB>([&](auto cb_c) {
             constexpr int CB = decltype(cb_c)::value;
             const int alo = t_lo ^ (CB << 6), ahi = t_hi ^ (CB << 6);
             frag_t<T> vT[2], dT[2];
-            ms_static_for<2>([&](auto q_c) {
+            static_for<2>([&](auto q_c) {
                 constexpr int Q = decltype(q_c)::value;
 #ifdef RVT_EMU
                 vT[Q] = frag_from_tr<T>(reinterpret_cast<const bf16*>(vb + alo + Q * 4096), reinterpret_cast<const bf16*>(vb + ahi + Q * 4096));

@@ -33,9 +33,13 @@
 //           the epilogue's stores / side loads issued since (EPI_OPS per flushed quadrant; step_body's W0..W3);
 //   WAR     n overwrites n - 8, last read in phase <= n - 8 by fragment reads that have returned before that phase's MFMAs,
 //           i.e. two barriers before any wave issues n.
+//
+// The buffer-resource and LDS-DMA primitives the stream is written in (pp_*) are lds_dma.hpp's; this file is the engine: PPMat,
+// PPGeom, PPWork, the epilogues and ppgemm_kernel.  ppgemm_tn.hpp builds the token-contraction kernel on the same pieces.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
-#include "gemm.hpp"
+#include "lds_dma.hpp"        // pp_*: buffer resources, LDS-DMA pieces, counted waits
 
 namespace rvt {
 
@@ -52,44 +56,6 @@ enum { PP_STORE = 0,        // out = v + c0[n]
 struct PPEpArgs {
     bf16* out; bf16* out2; const bf16* side; const float* c0; const float* c1; int ld;
 };
-
-#ifdef RVT_EMU
-struct pp_rsrc { const char* base; unsigned bytes; };
-__device__ __forceinline__ pp_rsrc pp_make_rsrc(const void* base, unsigned bytes) { return pp_rsrc{(const char*)base, bytes}; }
-// one LDS-DMA piece: LDS[lds_off + 16 lane ..) = mem[voff + soff ..), zeros when out of range
-__device__ __forceinline__ void pp_glds16(const pp_rsrc& rs, char* smem, int lds_off, int voff, int soff) {
-    char* d = smem + lds_off + 16 * emu::g.cur->lane;
-    const size_t o = (size_t)(unsigned)voff + (size_t)(unsigned)soff;
-    if (o + 16 <= rs.bytes) memcpy(d, rs.base + o, 16);
-    else memset(d, 0, 16);
-}
-__device__ __forceinline__ u32x4 pp_load16(const pp_rsrc& rs, int voff) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if ((size_t)(unsigned)voff + 16 <= rs.bytes) memcpy(&v, rs.base + (unsigned)voff, 16);
-    return v;
-}
-__device__ __forceinline__ void pp_store16(const pp_rsrc& rs, int voff, const u32x4& v) {
-    if ((size_t)(unsigned)voff + 16 <= rs.bytes) memcpy(const_cast<char*>(rs.base) + (unsigned)voff, &v, 16);
-}
-template <int N> __device__ __forceinline__ void pp_wait_vm() {}
-__device__ __forceinline__ void pp_barrier() { __syncthreads(); }
-__device__ __forceinline__ void pp_wave_sync() { emu::wave_barrier(); }
-__device__ __forceinline__ void pp_setprio(int) {}
-#else
-typedef __amdgpu_buffer_rsrc_t pp_rsrc;
-__device__ __forceinline__ pp_rsrc pp_make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void pp_glds16(const pp_rsrc& rs, char* smem, int lds_off, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(smem + lds_off), 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ u32x4 pp_load16(const pp_rsrc& rs, int voff) { return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0); }
-__device__ __forceinline__ void pp_store16(const pp_rsrc& rs, int voff, const u32x4& v) { __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, 0, 0); }
-template <int N> __device__ __forceinline__ void pp_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void pp_barrier() { __builtin_amdgcn_s_barrier(); }
-__device__ __forceinline__ void pp_wave_sync() {}
-#define pp_setprio(x) __builtin_amdgcn_s_setprio(x)
-#endif
 
 struct PPGeom {
     static constexpr int BM = 256, BN = 256, BK = 64;

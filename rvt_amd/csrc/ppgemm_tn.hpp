@@ -21,7 +21,8 @@
 // Hazard bookkeeping: as ppgemm.hpp (unit order W0..W3 X0..X3 per step, two units per phase, waits 8 / 9 / 10 / 7); there is no
 // epilogue inside the pipeline (one item per workgroup), so the counts are the plain ones.
 #pragma once
-#include "ppgemm.hpp"
+#include "ppgemm.hpp"           // same engine: PPGeom, PPMat, the load stream
+#include "fold.hpp"             // the split-K slices are folded by splitk_reduce_kernel / launch_fold_jobs
 
 namespace rvt {
 

@@ -1,16 +1,11 @@
 // Row-wise / element-wise kernels of the RVT hot path: LayerNorm fwd/bwd, column sums (bias
 // gradients), the event-tensor prepack (uint8/float NCHW -> padded channels-last T), the ConvLSTM
 // gate backward.  All are HBM-bound: every thread moves 16-byte (bf16) / 32-byte (f32) vectors.
+// Kernels only: the lane-group reduction they share with the fused MLP (group_sum) is in common.hpp.
 #pragma once
 #include "common.hpp"
 
 namespace rvt {
-
-// reduce over groups of G consecutive lanes (G power of two <= 64)
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 // ---- LayerNorm forward over the channel axis (reference maxvit.py:172,177,229,241; eps 1e-5) ----
 // G lanes share a row (G = pow2 >= C/8), each lane holds 8 channels; 64/G rows per wave.

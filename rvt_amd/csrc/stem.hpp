@@ -26,7 +26,6 @@
 #pragma once
 #include "common.hpp"
 #include "line_bounce.hpp"
-#include "attn_block.hpp"
 
 namespace rvt {
 

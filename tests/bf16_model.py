@@ -19,81 +19,81 @@ with a rounding backward would be; written out they are just `_r(t)`.
 ROUNDING POINTS (kernel file : line of the conversion)
 
 mlp_half - LN -> fc1 -> GELU -> fc2 * gamma + residual
-    v2 = LN2(x), fc1 operand and saved tensor    mlp.hpp:260  mlp_chain.hpp:89 (forward, dgrad) :423 (wgrad / both)  mlp_stream.hpp:696
-    g = GELU(pre), fc2 operand and saved tensor  mlp.hpp:317  mlp_chain.hpp:153 :454  mlp_stream.hpp:206 :747;  mlp.hpp:791 (recompute)
-    gp = GELU'(pre), saved (`saved_gp`)          mlp.hpp:323 - rvt_mlp_bwd_dgrad multiplies by the STORED value (mlp.hpp:495)
+    v2 = LN2(x), fc1 operand and saved tensor    mlp.hpp:215  ln_pieces.hpp:46 (forward, dgrad)  mlp_chain.hpp:363 (wgrad / both)  mlp_stream.hpp:654
+    g = GELU(pre), fc2 operand and saved tensor  mlp.hpp:272  mlp_chain.hpp:96 :394  mlp_stream.hpp:164 :705;  mlp.hpp:746 (recompute)
+    gp = GELU'(pre), saved (`saved_gp`)          mlp.hpp:278 - rvt_mlp_bwd_dgrad multiplies by the STORED value (mlp.hpp:450)
     (W2 gamma)^T, rounded by the host            rvt_amd/weights.py; the tests build it the same way
-    dh = dg * GELU'(pre), fc1-dgrad / dW1 operand, stored by rvt_mlp_bwd_dgrad      mlp.hpp:498 :792  mlp_chain.hpp:251 :455  mlp_stream.hpp:462 :748
-        (db1 sums the UNROUNDED products: mlp_chain.hpp:452, mlp_stream.hpp:746, mlp.hpp:789)
-    dv2 = dh W1 through a bf16 tile (`dv2_bf16`: rvt_mlp_bwd_recompute_both only)   mlp_chain.hpp:505
-    dv2 * xhat and dv2 before the column sums (`dln_bf16`: the chain / streamed input-gradient kernels)   mlp_chain.hpp:287-288  mlp_stream.hpp:536-537
-        (mlp.hpp:547 :831 and mlp_chain.hpp:525-526 sum in fp32)
-    stored outputs y, pre, dxmid: returned before their rounding (mlp.hpp:353 :325 :555 :839, mlp_chain.hpp:181 :302 :531, mlp_stream.hpp:262 :563)
+    dh = dg * GELU'(pre), fc1-dgrad / dW1 operand, stored by rvt_mlp_bwd_dgrad      mlp.hpp:453 :747  mlp_chain.hpp:191 :395  mlp_stream.hpp:420 :706
+        (db1 sums the UNROUNDED products: mlp_chain.hpp:392, mlp_stream.hpp:704, mlp.hpp:744)
+    dv2 = dh W1 through a bf16 tile (`dv2_bf16`: rvt_mlp_bwd_recompute_both only)   mlp_chain.hpp:445
+    dv2 * xhat and dv2 before the column sums (`dln_bf16`: the chain / streamed input-gradient kernels)   mlp_chain.hpp:227-228  mlp_stream.hpp:494-495
+        (mlp.hpp:502 :786 and mlp_chain.hpp:465-466 sum in fp32)
+    stored outputs y, pre, dxmid: returned before their rounding (mlp.hpp:308 :280 :510 :794, mlp_chain.hpp:124 :242 :471, mlp_stream.hpp:220 :521)
 
 attn_half - [LN ->] qkv -> softmax(Q K^T) V -> proj * gamma + residual       (attn_block.hpp; acc_to_frags / arr_slot_frag convert)
-    u = LN1(x), qkv operand (and the `u` output of the backward)             :163
-    forward  q (+ bias), k (NO bias: softmax is invariant to it), v (NO bias: added to the output, rows of P sum to 1)   :273 :280 :283
-             the UN-normalised exp(scale (s - max)) as the P V operand        :299
-             a = P V / sum + bv, proj operand and saved tensor                :307 :314;   xmid stored :344
-    backward q (+ bias), k (no bias), v (+ bias)                              :554 :562 :534 :540 :537
-             dO = dxmid (Wp gamma), (Wp gamma)^T rounded by the host          :557 :565
-             P = softmax in fp32 (normalised), dS = P (dP - delta) scale, both as MFMA operands   :594-595 :603
-             dq, dk, dv: stored and the operand of du = dqkv Wqkv             :513 :516
-             LN / PRE: du * xhat and du before the column sums                :669-670;   dx stored :685 :693
-    `handover_bf16` is the two-launch route the PRE kernel replaces: dx = dxmid + du stored in bf16 (:693), then ln_bwd_kernel
-    (rowops.hpp:59-116: fp32 sums of the bf16 rows).
+    u = LN1(x), qkv operand (and the `u` output of the backward)ln_pieces.hpp:95
+    forward  q (+ bias), k (NO bias: softmax is invariant to it), v (NO bias: added to the output, rows of P sum to 1)   :156 :163 :166
+             the UN-normalised exp(scale (s - max)) as the P V operand        :182
+             a = P V / sum + bv, proj operand and saved tensor                :190 :197;   xmid stored :227
+    backward q (+ bias), k (no bias), v (+ bias)                              :401 :409 :381 :387 :384
+             dO = dxmid (Wp gamma), (Wp gamma)^T rounded by the host          :404 :412
+             P = softmax in fp32 (normalised), dS = P (dP - delta) scale, both as MFMA operands   :441-442 :450
+             dq, dk, dv: stored and the operand of du = dqkv Wqkv             :360 :363
+             LN / PRE: du * xhat and du before the column sums                :516-517;   dx stored :532 :540
+    `handover_bf16` is the two-launch route the PRE kernel replaces: dx = dxmid + du stored in bf16 (:540), then ln_bwd_kernel
+    (rowops.hpp:54-111: fp32 sums of the bf16 rows).
 
 attn_core - softmax(Q K^T) V on a saved qkv tensor: q, k, v, dO are the stored bf16 values, no bias anywhere    (attn_core2.hpp; the
-    helpers of attn.hpp :64-76 and attn_block.hpp :371-380 convert; the transposes by identity MFMA, :26-33, are exact)
-    forward  the UN-normalised exp(scale (s - max)) as the P V operand        :96 (staged :184);   out stored :105 (staged :193)
-    backward P = softmax in fp32 (normalised, :276 / :419) through the LDS tile for dV          :285 (staged :428)
-             dS = P (dP - delta) scale through the LDS tile for dK, from the registers for dQ   :286 :293 (staged :429 :436)
-             dq, dk, dv stored                                                :249 (staged :388)
+    helpers of acc_frags.hpp :30-42 and opm.hpp :96-105 convert; the transposes by identity MFMA, :22-29, are exact)
+    forward  the UN-normalised exp(scale (s - max)) as the P V operand        :92 (staged :180);   out stored :101 (staged :189)
+    backward P = softmax in fp32 (normalised, :272 / :415) through the LDS tile for dV          :281 (staged :424)
+             dS = P (dP - delta) scale through the LDS tile for dK, from the registers for dQ   :282 :289 (staged :425 :432)
+             dq, dk, dv stored                                                :245 (staged :384)
     `_softmax_bwd` is this backward and that of attn_half: the two kernels differ in where q, k, v, dO come from, not in the softmax.
 
 lstm - ConvLSTM cell with a 1x1 conv, T steps, and its BPTT.  z = [x | h] W^T + b accumulates in fp32, the gates and c_t stay fp32.
     h_t rounded where it is stored; the stored value is the next step's operand (`h_bf16`)
-             gemm.hpp:715 (per step)  lstm_scan.hpp:187  lstm_scan2.hpp:203 (s2_pack)  lstm_scan3.hpp:172
-    c_t copy for the backward (`c`, returned before its rounding)    lstm_scan.hpp:188  lstm_scan2.hpp:214  lstm_scan3.hpp:181;  c_last stays fp32
-    activated gates saved for the backward (`gates`, before rounding)  gemm.hpp:718-721  lstm_scan.hpp:190-193 (W_REG)  lstm_scan3.hpp:177-180
-    backward, `saved_gates`: f, i, o, g read back from that save      rowops.hpp:244-247  lstm_scan.hpp:433-436 (GATES)  lstm_scan3.hpp:286-289
-             off: recomputed in fp32 from x_t and the stored h_{t-1}  lstm_scan.hpp:438-441  lstm_scan2.hpp:497-500
+             gemm.hpp:634 (per step)  lstm_scan.hpp:187  lstm_scan2.hpp:202 (s2_pack)  lstm_scan3.hpp:172
+    c_t copy for the backward (`c`, returned before its rounding)    lstm_scan.hpp:188  lstm_scan2.hpp:213  lstm_scan3.hpp:181;  c_last stays fp32
+    activated gates saved for the backward (`gates`, before rounding)  gemm.hpp:637-640  lstm_scan.hpp:190-193 (W_REG)  lstm_scan3.hpp:177-180
+    backward, `saved_gates`: f, i, o, g read back from that save      rowops.hpp:239-242  lstm_scan.hpp:433-436 (GATES)  lstm_scan3.hpp:286-289
+             off: recomputed in fp32 from x_t and the stored h_{t-1}  lstm_scan.hpp:438-441  lstm_scan2.hpp:492-495
     backward, `c_bf16`: c_{t-1} from the bf16 save, the incoming fp32 c0 converted the same way, tanh(c_t) of f c_{t-1} + i g rebuilt from it
-             lstm_scan.hpp:309-310 :443 :445  lstm_scan2.hpp:449 :460 :503  lstm_scan3.hpp:291 :296 :304
-             off: c_t and c_{t-1} are the forward's fp32 tensors      rowops.hpp:250-251 :254
+             lstm_scan.hpp:309-310 :443 :445  lstm_scan2.hpp:444 :455 :498  lstm_scan3.hpp:291 :296 :304
+             off: c_t and c_{t-1} are the forward's fp32 tensors      rowops.hpp:245-246 :249
     `dz_bf16`: dz, the operand of [dx | dh] = dz W and of dW = dz^T [x | h], and a stored output
-             rowops.hpp:263-266  lstm_scan.hpp:449-452  lstm_scan2.hpp:515-516  lstm_scan3.hpp:306-309
-    `db_bf16`: db from the rounded dz - lstm_scan2.hpp:366 :389 (product against ones), and every test that sums the stored dz itself;
+             rowops.hpp:258-261  lstm_scan.hpp:449-452  lstm_scan2.hpp:510-511  lstm_scan3.hpp:306-309
+    `db_bf16`: db from the rounded dz - lstm_scan2.hpp:361 :384 (product against ones), and every test that sums the stored dz itself;
              off: lstm_scan.hpp:453 sums the fp32 values
-    dx_t stored (lstm_scan.hpp:502, lstm_scan2.hpp:594, lstm_scan3.hpp:348); dh_{t-1} and dc stay in fp32 registers across the steps
-    (lstm_scan.hpp:503, lstm_scan2.hpp:591, lstm_scan3.hpp:349); dh0 stored, dc0 fp32.
+    dx_t stored (lstm_scan.hpp:502, lstm_scan2.hpp:589, lstm_scan3.hpp:348); dh_{t-1} and dc stay in fp32 registers across the steps
+    (lstm_scan.hpp:503, lstm_scan2.hpp:586, lstm_scan3.hpp:349); dh0 stored, dc0 fp32.
 
 dgrad_ln - dx = add + LN'(dy W; x) and, `inside`, dx = LN'(dy W + add; x)     (dgrad_ln.hpp)
-    du (+ add) rounded "as the two-launch chain stores it"                    :184 - AFTER the row sums s1 / s2 took the fp32 values (:180-182)
-    du * xhat before the column sums (du itself is already bf16)              :244-245;   dx stored :213
-    `fused=False` is the chain it replaces: du stored by the GEMM epilogue, then ln_bwd_kernel on the bf16 rows (rowops.hpp:59-116).
+    du (+ add) rounded "as the two-launch chain stores it"                    :186 - AFTER the row sums s1 / s2 took the fp32 values (:182-184)
+    du * xhat before the column sums (du itself is already bf16)              :246-247;   dx stored :215
+    `fused=False` is the chain it replaces: du stored by the GEMM epilogue, then ln_bwd_kernel on the bf16 rows (rowops.hpp:54-111).
 
 ln_linear - u = LN(x) is the GEMM operand and the saved tensor (ln_linear.hpp:107-115, layernorm_fwd rowops.hpp:50); y stored (:134).
 
 linear_ep - y = epilogue(x W^T): the linear entry points on BOTH GEMM engines.  fp32 accumulation of bf16 products everywhere.
-    `gelu_in`: GELU(x) is converted to bf16 on its way into the operand tile           gemm.hpp:189 (xf_apply, XfGelu; 128-row engine only)
+    `gelu_in`: GELU(x) is converted to bf16 on its way into the operand tile           gemm.hpp:190 (xf_apply, XfGelu; 128-row engine only)
     128-row engine (gemm.hpp): the side tensor is combined with the fp32 accumulator, ONE rounding at the store
-             EpStore v + bias + add :418-419   EpScaleRes res + gamma (v + bias) :460-461   EpMul v * mul :514-515
-             EpGeluBwd v * GELU'(pre) :478-479   EpGeluDual g, gp :495-497   EpDgradScatter v + add :669-670
-    256-wide engine (ppgemm.hpp), `side_rounded`: `convert` rounds c1 (acc + c0) into the LDS scratch                      :346-350 :368
-             and `store_rows` adds / multiplies the bf16 side tensor to the ROUNDED value and rounds a second time          :384-385
+             EpStore v + bias + add :419-420   EpScaleRes res + gamma (v + bias) :461-462   EpMul v * mul :515-516
+             EpGeluBwd v * GELU'(pre) :479-480   EpGeluDual g, gp :496-498   EpDgradScatter v + add :588-589
+    256-wide engine (ppgemm.hpp), `side_rounded`: `convert` rounds c1 (acc + c0) into the LDS scratch                      :312-316 :334
+             and `store_rows` adds / multiplies the bf16 side tensor to the ROUNDED value and rounds a second time          :350-351
              (PP_SCALE_RES: res + bf16(gamma (v + bias));  PP_ADD: bf16(v + bias) + add;  PP_MUL: bf16(v) * mul).  PP_STORE and
-             PP_GELU_DUAL have no side tensor: one rounding (:368).  The conv input gradient by 2 x 2 blocks (rvt_conv_dgrad4) with an
+             PP_GELU_DUAL have no side tensor: one rounding (:334).  The conv input gradient by 2 x 2 blocks (rvt_conv_dgrad4) with an
              added cotangent is PP_ADD and rounds twice as well; the parity-class route (EpDgradScatter) rounds once.
-wgrad - dW = dy^T x, column sums of dy: fp32 throughout (split-K partial tiles and their fold, ppgemm_tn.hpp); `gelu_in` as above (gemm.hpp:189).
-layernorm - rowops.hpp ln_fwd_kernel / ln_bwd_kernel: two-pass statistics in fp32; y stored :50, dx (+ dres) stored :113; dw, db are
-    fp32 sums of fp32 products (:105).  No interior rounding point.
+wgrad - dW = dy^T x, column sums of dy: fp32 throughout (split-K partial tiles and their fold, ppgemm_tn.hpp); `gelu_in` as above (gemm.hpp:190).
+layernorm - rowops.hpp ln_fwd_kernel / ln_bwd_kernel: two-pass statistics in fp32; y stored :45, dx (+ dres) stored :108; dw, db are
+    fp32 sums of fp32 products (:100).  No interior rounding point.
 conv_fwd / conv_dgrad / conv_wgrad - im2col products on the same engines: no interior rounding point but `side_rounded` above.
-    `scale` / `shift` / `act` (rvt_conv_bn_act_fwd): act(fma(acc, scale, shift)) on the fp32 accumulator, one store    gemm.hpp:438-441
-stem - y0 = conv of the uint8 planes (exact in bf16), stored stem.hpp:219; the LayerNorm statistics and output are taken from the
-    STORED y0 (:220 converts it back, "the statistics see what the backward will see"), x stored :247: the test models LN(y0) by
+    `scale` / `shift` / `act` (rvt_conv_bn_act_fwd): act(fma(acc, scale, shift)) on the fp32 accumulator, one store    gemm.hpp:439-442
+stem - y0 = conv of the uint8 planes (exact in bf16), stored stem.hpp:218; the LayerNorm statistics and output are taken from the
+    STORED y0 (:219 converts it back, "the statistics see what the backward will see"), x stored :246: the test models LN(y0) by
     `layernorm` on the kernel's own y0.  stem_wgrad: `conv_wgrad`, fp32.
-dwconv - rowops.hpp dwconv_kernel: bias + nine fp32 products, one store :332; dwconv_wgrad_kernel: fp32 sums.
+dwconv - rowops.hpp dwconv_kernel: bias + nine fp32 products, one store :327; dwconv_wgrad_kernel: fp32 sums.
 lin_gelu_ws - fc1 + GELU on the weight-stationary kernel (ln_linear.hpp lin_gelu_ws_kernel): pre = x W^T + b in fp32; Phi and GELU' are
     READ AT THE NEAREST POINT of the table of gelu_lut.hpp (`snap`): index = round((pre + X) N / 2X) clamped to [0, N]      gelu_lut.hpp:90-94
              g = pre * Phi(snapped pre) with the UNSNAPPED pre as the factor, gp = GELU'(snapped pre)                     gelu_lut.hpp:123
@@ -122,7 +122,7 @@ def _ln(x, eps):
 
 
 def _ln_bwd(d, xhat, rstd, w, stats_from=None):
-    """rstd (d w - mean(d w) - xhat mean(d w xhat)); `stats_from`: the tensor the two row means are taken from (dgrad_ln.hpp:180)."""
+    """rstd (d w - mean(d w) - xhat mean(d w xhat)); `stats_from`: the tensor the two row means are taken from (dgrad_ln.hpp:182)."""
     gs = (d if stats_from is None else stats_from) * w
     m1 = gs.mean(-1, keepdim=True)
     m2 = (gs * xhat).mean(-1, keepdim=True)
@@ -308,7 +308,7 @@ def linear_ep(x, w, b=None, *, gelu_in=False, gamma=None, res=None, add=None, mu
       gamma, res   y = res + gamma (x W^T + b)          add   y = x W^T + b + add
       mul          y = (x W^T) * mul                    gelu_pre   y = (x W^T) * GELU'(gelu_pre)
     gelu_in: the operand is bf16(GELU(x)).  side_rounded: the 256-wide engine - gamma (v + b), v + b or v is rounded to bf16 BEFORE
-    res / add / mul is combined with it (ppgemm.hpp:368 then :384); off: the 128-row engine combines in fp32."""
+    res / add / mul is combined with it (ppgemm.hpp:334 then :350); off: the 128-row engine combines in fp32."""
     x, w, b, gamma, res, add, mul, gelu_pre = _prep(dtype, x, w, b, gamma, res, add, mul, gelu_pre)
     assert (res is not None) + (add is not None) + (mul is not None) + (gelu_pre is not None) + bool(dual) <= 1 and (gamma is None) == (res is None)
     r = lambda t: _r(t, rounding)
@@ -332,7 +332,7 @@ def linear_ep(x, w, b=None, *, gelu_in=False, gamma=None, res=None, add=None, mu
 
 def wgrad(dy, x, *, gelu_in=False, rounding=True, dtype=torch.float32):
     """dW = dy^T x and the column sums of dy, both kept in fp32 (gemm.hpp split-K, ppgemm_tn.hpp): no rounding point but the GELU'd
-    operand (`gelu_in`: x -> bf16(GELU(x)), gemm.hpp:189).  `+=` into an fp32 buffer: the caller scales the model."""
+    operand (`gelu_in`: x -> bf16(GELU(x)), gemm.hpp:190).  `+=` into an fp32 buffer: the caller scales the model."""
     dy, x = _prep(dtype, dy, x)
     if gelu_in:
         x = _r(_gelu_both(x)[0], rounding)

@@ -502,7 +502,7 @@ def test_attention(backend, dt, window, case):
     qr = f64(qkv).requires_grad_(True)
     want = ref_attention(qr, Fr, H, W, C, dh, ph, pw, window)
     want.backward(f64(dout))
-    # the rounding model of the core (attn.hpp / attn_core2.hpp); both outputs are downstream of the hardware exp2 and reciprocal
+    # the rounding model of the core (attn_pieces.hpp / attn_core2.hpp); both outputs are downstream of the hardware exp2 and reciprocal
     m = modelled(bf16_model.attn_core, dict(out=want, dqkv=qr.grad), dt, qkv, dout, (Fr, H, W, C, dh, ph, pw, window))
     close(out, want, dt, 'attn_fwd', model=part(m, 'out'), factor=4)
     dq = ops.attn_bwd(qkv, dout, Fr, H, W, C, dh, ph, pw, window)
@@ -796,7 +796,7 @@ def test_stem(backend, case):
     yr = F.conv2d(xin, wr, None, 4, 3)
     xcl = xin.permute(0, 2, 3, 1)                                  # the padded planes, channels-last (integers: exact in any type)
     c_y0 = close(y0, yr.permute(0, 2, 3, 1), dt, 'stem y0', model=modelled(bf16_model.conv_fwd, dict(y=yr.permute(0, 2, 3, 1)), dt, xcl, wt, 4, 3)['y'])
-    # LayerNorm of the STORED (bf16) conv output: what the backward differentiates, and what the kernel normalises (stem.hpp:220 reads
+    # LayerNorm of the STORED (bf16) conv output: what the backward differentiates, and what the kernel normalises (stem.hpp:219 reads
     # the rounded y0 back before the statistics): the model is the fp32 LayerNorm of the kernel's own y0
     xr = F.layer_norm(f64(y0), (64,), f64(lw), f64(lb), 1e-5)
     close(x, xr, dt, 'stem LN(y0)', model=modelled(bf16_model.layernorm, dict(y=xr), dt, y0, lw, lb)['y'])
