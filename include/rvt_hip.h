@@ -388,7 +388,10 @@ typedef struct RvtStageDesc {
 } RvtStageDesc;
 /* inp: [T*B][H_in][W_in][cin_pad] channels-last (dtype), or the uint8 planes when inp_u8;  h0 [B][H][W][C] (dtype) / c0 fp32,
  * both NULL = zero state;  Hall [T+1][B][H][W][C]: slot 0 is scratch for the incoming h, slots 1..T receive h_t (the stage's
- * output features = the next stage's input);  c_last fp32 [B][H][W][C];  ws: rvt_stage_seq_fwd_ws_bytes(desc, T, B) bytes. */
+ * output features = the next stage's input);  c_last fp32 [B][H][W][C];  ws: rvt_stage_seq_fwd_ws_bytes(desc, T, B) bytes.
+ * The size is the driver's own carve run without a base pointer (256-byte pieces, only those the routes use, plus 256 bytes for a base
+ * of any alignment): it depends on the tuning record through the routes, so ask again after rvt_set_tuning.  A smaller ws is refused
+ * before anything is launched. */
 size_t rvt_stage_seq_fwd_ws_bytes(const RvtStageDesc* desc, int T, int B);
 int rvt_stage_seq_fwd(const RvtStageDesc* desc, const void* inp, const void* h0, const float* c0, void* Hall, float* c_last,
                       void* ws, size_t ws_bytes, int T, int B, void* stream);
@@ -463,7 +466,9 @@ int rvt_stage_seq_train_fwd(const RvtStageDesc* desc, const RvtStageTrain* tr, c
 /* dH [T][B][H][W][C] cotangent of Hall[1..] (route 0: must not be NULL), dc_last fp32 (NULL = zeros), prev_cot: cotangent already
  * attached to the stage's input frames (added to the conv input gradient; NULL = none), d_in [T*B][H_in][W_in][Cin] (NULL: no
  * input gradient), dh0 [B][H][W][C], dc0 fp32.  `inp` = the tensor the forward read (planes or channels-last frames).
- * ws: rvt_stage_seq_bwd_ws_bytes bytes.  Parameter gradients are ACCUMULATED (+=) into the pointers of `tr`. */
+ * ws: rvt_stage_seq_bwd_ws_bytes bytes - the backward's own carve run without a base pointer (2-MiB pieces plus 2 MiB for a base of
+ * any alignment; it reads tr->routes, not the tuning record); a smaller ws is refused before anything is launched.
+ * Parameter gradients are ACCUMULATED (+=) into the pointers of `tr`. */
 size_t rvt_stage_seq_bwd_ws_bytes(const RvtStageDesc* desc, const RvtStageTrain* tr, int T, int B);
 int rvt_stage_seq_bwd(const RvtStageDesc* desc, const RvtStageTrain* tr, const void* inp, const void* dH, const float* dc_last,
                       const void* prev_cot, void* d_in, void* dh0, float* dc0, void* ws, size_t ws_bytes, int T, int B, void* stream);

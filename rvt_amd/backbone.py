@@ -229,6 +229,17 @@ class RNNDetector(nn.Module):
             states.append((h if h.requires_grad else h.clone(memory_format=torch.preserve_format), c))
         return feats, states
 
+    def _prepare_input(self, xs: Tensor):
+        """What both forward paths derive from the (T,B,Cin,h,w) input before they part ways: the model resolution (Hm, Wm), the stage
+        geometries at it, and the frames as (T*B,Cin,h,w) in a dtype the prepack / stem kernels read (uint8, int8 or fp32)."""
+        T, B, Cin, h, w = xs.shape
+        Hm, Wm = self.in_res_hw if self.in_res_hw is not None else (h, w)
+        assert h <= Hm and w <= Wm, f'input {h}x{w} larger than model resolution {Hm}x{Wm}'
+        src = xs.reshape(T * B, Cin, h, w)
+        if src.dtype not in (torch.uint8, torch.int8, torch.float32):
+            src = src.float()
+        return Hm, Wm, self.stage_geoms(Hm, Wm), src
+
     def _forward_nograd(self, xs: Tensor, prev_states, token_masks, params):
         """The no-grad forward through the C-side stage driver (include/rvt_hip.h: rvt_stage_seq_fwd): Python allocates, the library
         sequences the kernels.  Returns None when a stage is outside the driver's coverage (token masks, DWS-ConvLSTM): the caller
@@ -236,16 +247,11 @@ class RNNDetector(nn.Module):
         from . import stage_driver as SD
         ns, dt = self.num_stages, self.compute_dtype
         T, B, Cin, h, w = xs.shape
-        Hm, Wm = self.in_res_hw if self.in_res_hw is not None else (h, w)
-        assert h <= Hm and w <= Wm, f'input {h}x{w} larger than model resolution {Hm}x{Wm}'
-        geoms = self.stage_geoms(Hm, Wm)
+        Hm, Wm, geoms, src = self._prepare_input(xs)
         mw = self.model_weights(params, geoms, dt, False)
         if token_masks is not None or any(sw.dws is not None for sw in mw.stages):
             return None
-        src = xs.reshape(T * B, Cin, h, w)
-        if src.dtype not in (torch.uint8, torch.int8, torch.float32):
-            src = src.float()
-        u8 = src.dtype == torch.uint8
+        u8 = src.dtype == torch.uint8                 # the library reads the planes, and prepacks them itself where no stem kernel is built
         if u8:
             inp = src.contiguous()
         else:
@@ -307,13 +313,8 @@ class _BackboneSeqFn(torch.autograd.Function):
         p = dict(zip(names, params))
         dt = mod.compute_dtype
         T, B, Cin, h, w = xs.shape
-        Hm, Wm = mod.in_res_hw if mod.in_res_hw is not None else (h, w)
-        assert h <= Hm and w <= Wm, f'input {h}x{w} larger than model resolution {Hm}x{Wm}'
-        geoms = mod.stage_geoms(Hm, Wm)
+        Hm, Wm, geoms, src = mod._prepare_input(xs)
         need_grad = bool(grad_enabled) and any(ctx.needs_input_grad[4:])
-        src = xs.reshape(T * B, Cin, h, w)
-        if src.dtype not in (torch.uint8, torch.int8, torch.float32):
-            src = src.float()
         g0 = geoms[0]
         if ops.stem_supported(src, dt, g0.C, g0.k, g0.stride, g0.pad):
             inp = src.contiguous()           # the stem kernels read the planes themselves (no channels-last copy)

@@ -11,10 +11,9 @@
 using namespace rvt;
 
 namespace rvt {
-int stage_blocks_fwd(const RvtStageDesc& d, const RvtStageRoutes& r, const void* inp, void* prepack, void* y0, void* x0,
-                     const RvtBlockSaved* blk, int T, int B, void* stream) {
-    const int C = d.C, F = T * B, dt = d.dtype;
-    const int H = conv_out(d.H_in, d.k, d.stride, d.pad), W = conv_out(d.W_in, d.k, d.stride, d.pad), M = F * H * W;
+int stage_blocks_fwd(const RvtStageDesc& d, const RvtStageRoutes& r, const StageShape& s, const void* inp, void* prepack, void* y0, void* x0,
+                     const RvtBlockSaved* blk, void* stream) {
+    const int C = d.C, F = s.F, H = s.H, W = s.W, M = s.M, dt = d.dtype;
     // ---- down-sampling conv + LayerNorm (maxvit.py:174-178) ----
     if (d.inp_u8 && rvt_stem_supported(dt, 1, d.Cin, C, d.k, d.stride, d.pad, d.w_raw)) {
         RVT_TRY(rvt_stem_fwd(inp, d.conv_w, d.ln_w, d.ln_b, y0, x0, dt, F, d.Cin, d.cin_pad, d.h_raw, d.w_raw, d.H_in, d.W_in, d.eps, stream));
@@ -63,29 +62,47 @@ int stage_blocks_fwd(const RvtStageDesc& d, const RvtStageRoutes& r, const void*
     return 0;
 }
 
-int stage_lstm_scan_fwd(const RvtStageDesc& d, const RvtStageRoutes& r, const void* x, void* Hall, const float* c0, float* c_last,
-                        void* Csave, void* gates, const void* wp3, int T, int B, void* stream) {
-    const int Ms = B * conv_out(d.H_in, d.k, d.stride, d.pad) * conv_out(d.W_in, d.k, d.stride, d.pad);
+int stage_lstm_fwd(const RvtStageDesc& d, const RvtStageRoutes& r, const StageShape& s, const void* x, void* Hall, const float* c0,
+                   float* c_last, void* Csave, void* gates, const void* wp3, const LstmStep* steps, int T, void* stream) {
     if (r.lstm_route == 3) {
         RVT_CHECK(wp3 != nullptr, "stage forward: lstm_scan3 weights missing");
-        return rvt_lstm_scan3_fwd(x, Hall, c0, c_last, Csave, wp3, d.lstm_bn, gates, d.dtype, Ms, d.C, T, r.lstm_scan3_rb, stream);
+        return rvt_lstm_scan3_fwd(x, Hall, c0, c_last, Csave, wp3, d.lstm_bn, gates, d.dtype, s.Ms, d.C, T, r.lstm_scan3_rb, stream);
     }
-    return rvt_lstm_scan_fwd(x, Hall, c0, c_last, Csave, d.lstm_wn, d.lstm_bn, r.lstm_route == 2 ? gates : nullptr, d.dtype, Ms, d.C, T, stream);
+    if (r.lstm_route != 0)
+        return rvt_lstm_scan_fwd(x, Hall, c0, c_last, Csave, d.lstm_wn, d.lstm_bn, r.lstm_route == 2 ? gates : nullptr, d.dtype, s.Ms, d.C, T, stream);
+    for (int t = 0; t < T; t++) {
+        const LstmStep& k = steps[t];
+        RVT_TRY(rvt_lstm_fwd((const char*)x + (size_t)t * s.state * s.e, k.h_in, k.c_in, d.lstm_w, d.lstm_b, k.h_out, k.c_out, k.gates, d.dtype, s.Ms, d.C, stream));
+    }
+    return 0;
 }
 }  // namespace rvt
 
 namespace {
-static size_t stage_ws_bytes(const RvtStageDesc& d, const RvtStageRoutes& r, int T, int B) {
-    const int H = conv_out(d.H_in, d.k, d.stride, d.pad), W = conv_out(d.W_in, d.k, d.stride, d.pad);
-    const size_t tok = (size_t)T * B * H * W, e = elt_bytes(d.dtype), pad = 256;
-    size_t n = 3 * (tok * d.C * e + pad);                                   // activation ping-pong (y0 / x / xmid / xout)
-    if (!r.attn_block) n += tok * d.C * e * 5 + 3 * pad;                    // u, qkv (3C), a
-    if (r.mlp_route == 0) n += tok * d.C * e * 5 + 2 * pad;                 // v2, GELU(h) (4C)
-    if (!d.inp_u8 || !rvt_stem_supported(d.dtype, 1, d.Cin, d.C, d.k, d.stride, d.pad, d.w_raw))
-        n += d.inp_u8 ? (size_t)T * B * d.H_in * d.W_in * d.cin_pad * e + pad : 0;      // prepacked input
-    n += 2 * ((size_t)B * H * W * d.C * 4 + pad);                           // cell-state ping-pong of the per-step route
-    n += (size_t)8 * d.C * d.C * e + pad;                                   // ConvLSTM weights in operand order (lstm_scan3 route)
-    return n + 4096;
+// Every piece the no-grad driver takes from its workspace, in the order it takes them.  On a counting Carver this is
+// rvt_stage_seq_fwd_ws_bytes: a piece the routes do not use is neither carved nor counted.
+struct FwdCarve {
+    void* bufs[3];                // activation ring: y0 / x / xmid / xout
+    void* pk;                     // loader planes without a stem kernel for this shape are prepacked here
+    RvtBlockSaved scratch;        // op-by-op halves: u, qkv, a / v2, GELU(h) - one set shared by all blocks
+    float* cbuf[2];               // per-step ConvLSTM: cell-state ping-pong
+    void* wp;                     // lstm_scan3: the weights in operand order
+};
+static FwdCarve carve_fwd(Carver& cv, const RvtStageDesc& d, const RvtStageRoutes& r, const StageShape& s) {
+    FwdCarve c;
+    memset(&c, 0, sizeof(c));
+    for (void*& b : c.bufs) b = cv.take(s.act);
+    if (d.inp_u8 && !rvt_stem_supported(d.dtype, 1, d.Cin, d.C, d.k, d.stride, d.pad, d.w_raw)) c.pk = cv.take((size_t)s.F * d.H_in * d.W_in * d.cin_pad * s.e);
+    if (!r.attn_block) { c.scratch.u = r.ln_linear ? nullptr : cv.take(s.act); c.scratch.qkv = cv.take(3 * s.act); c.scratch.a = cv.take(s.act); }
+    if (r.mlp_route == 0) { c.scratch.v2 = cv.take(s.act); c.scratch.hg = cv.take(4 * s.act); }
+    if (r.lstm_route == 3) c.wp = cv.take((size_t)8 * d.C * d.C * s.e);
+    else if (r.lstm_route == 0) for (float*& b : c.cbuf) b = (float*)cv.take(s.state * 4);
+    return c;
+}
+static size_t fwd_ws_bytes(const RvtStageDesc& d, const RvtStageRoutes& r, const StageShape& s) {
+    Carver cv = Carver::counting(256);
+    carve_fwd(cv, d, r, s);
+    return cv.bytes();
 }
 }  // namespace
 
@@ -98,7 +115,9 @@ int rvt_stage_routes(const RvtStageDesc* dp, int T, int B, int save, int has_dws
     const RvtStageDesc& d = *dp;
     const RvtTuning& tn = tuning();
     const int dt = d.dtype, C = d.C, n_tok = d.ph * d.pw;
-    const int Ms = B * conv_out(d.H_in, d.k, d.stride, d.pad) * conv_out(d.W_in, d.k, d.stride, d.pad);     // tokens per time step
+    StageShape s;
+    stage_shape(d, T, B, nullptr, &s);
+    const int Ms = s.Ms;                                   // tokens per time step
     RvtStageRoutes r;
     memset(&r, 0, sizeof(r));
 
@@ -183,8 +202,9 @@ int rvt_stage_routes(const RvtStageDesc* dp, int T, int B, int save, int has_dws
 
 size_t rvt_stage_seq_fwd_ws_bytes(const RvtStageDesc* d, int T, int B) {
     RvtStageRoutes r;
-    if (rvt_stage_routes(d, T, B, 0, 0, 0, &r) != 0) return 0;
-    return stage_ws_bytes(*d, r, T, B);
+    StageShape s;
+    if (rvt_stage_routes(d, T, B, 0, 0, 0, &r) != 0 || stage_shape(*d, T, B, nullptr, &s) != 0) return 0;
+    return fwd_ws_bytes(*d, r, s);
 }
 
 int rvt_stage_seq_fwd(const RvtStageDesc* dp, const void* inp, const void* h0, const float* c0, void* Hall, float* c_last,
@@ -194,65 +214,43 @@ int rvt_stage_seq_fwd(const RvtStageDesc* dp, const void* inp, const void* h0, c
     const RvtStageDesc& d = *dp;
     RVT_CHECK(d.num_blocks >= 0 && d.blocks != nullptr && inp != nullptr && Hall != nullptr && c_last != nullptr, "stage_seq_fwd: bad arguments");
     RVT_CHECK((h0 == nullptr) == (c0 == nullptr), "stage_seq_fwd: h0 and c0 go together");
-    RVT_CHECK(ws != nullptr && ws_bytes >= stage_ws_bytes(d, r, T, B), "stage_seq_fwd: workspace of %zu bytes < rvt_stage_seq_fwd_ws_bytes = %zu",
-              ws_bytes, stage_ws_bytes(d, r, T, B));
-    const int C = d.C, F = T * B, dt = d.dtype;
-    const int H = conv_out(d.H_in, d.k, d.stride, d.pad), W = conv_out(d.W_in, d.k, d.stride, d.pad);
-    RVT_CHECK(H % d.ph == 0 && W % d.pw == 0, "stage_seq_fwd: %dx%d not divisible by the partition %dx%d", H, W, d.ph, d.pw);
-    const size_t e = elt_bytes(dt), tok = (size_t)F * H * W, act = tok * C * e;
-    RVT_CHECK(tok * 4 * C < ((size_t)1 << 31), "stage_seq_fwd: %zu token rows exceed the operators' 32-bit sizes", tok);
+    StageShape s;
+    RVT_TRY(stage_shape(d, T, B, "stage_seq_fwd", &s));
+    const size_t need = fwd_ws_bytes(d, r, s);
+    RVT_CHECK(ws != nullptr && ws_bytes >= need, "stage_seq_fwd: workspace of %zu bytes < rvt_stage_seq_fwd_ws_bytes = %zu", ws_bytes, need);
     Carver cv{(char*)ws, ws_bytes, 256};
-    void* bufs[3] = {cv.take(act), cv.take(act), cv.take(act)};
+    const FwdCarve c = carve_fwd(cv, d, r, s);
+    RVT_CHECK(cv.ok, "stage_seq_fwd: workspace carving overflow");
     hipStream_t st = (hipStream_t)stream;
-    void* pk = nullptr;                                   // loader planes without a stem kernel for this shape are prepacked here
-    if (d.inp_u8 && !rvt_stem_supported(dt, 1, d.Cin, C, d.k, d.stride, d.pad, d.w_raw)) pk = cv.take((size_t)F * d.H_in * d.W_in * d.cin_pad * e);
 
     // the block table of a forward that keeps nothing: three ping-pong activations, one scratch set shared by all blocks
-    RvtBlockSaved scratch;
-    memset(&scratch, 0, sizeof(scratch));
-    if (!r.attn_block) { scratch.u = r.ln_linear ? nullptr : cv.take(act); scratch.qkv = cv.take(3 * act); scratch.a = cv.take(act); }
-    if (r.mlp_route == 0) { scratch.v2 = cv.take(act); scratch.hg = cv.take(4 * act); }
-    RVT_CHECK(cv.ok, "stage_seq_fwd: workspace carving overflow");
-    std::vector<RvtBlockSaved> blk(2 * d.num_blocks, scratch);
+    std::vector<RvtBlockSaved> blk(2 * d.num_blocks, c.scratch);
     int xi = 1;                                           // bufs[xi] = the running activation
     for (RvtBlockSaved& b : blk) {
         const int mi = (xi + 1) % 3, oi = 3 - xi - mi;
-        b.xin = bufs[xi]; b.xmid = bufs[mi]; b.xout = bufs[oi];
+        b.xin = c.bufs[xi]; b.xmid = c.bufs[mi]; b.xout = c.bufs[oi];
         xi = oi;
     }
-    RVT_TRY(stage_blocks_fwd(d, r, inp, pk, bufs[0], bufs[1], blk.data(), T, B, stream));
-    const void* x = bufs[xi];
+    RVT_TRY(stage_blocks_fwd(d, r, s, inp, c.pk, c.bufs[0], c.bufs[1], blk.data(), stream));
 
     // ---- ConvLSTM over the T steps (rnn.py:43-67); Hall slot 0 = incoming h, slots 1..T = the stage's output features ----
-    const size_t sN = (size_t)B * H * W * C;             // elements of one state
-    const int Ms = B * H * W;
     char* const HallB = (char*)Hall;
-    if (r.lstm_route != 0) {
-        void* wp = r.lstm_route == 3 ? cv.take((size_t)8 * C * C * e) : nullptr;
-        RVT_CHECK(cv.ok, "stage_seq_fwd: workspace carving overflow");
-        if (h0 != nullptr) { if (hipMemcpyAsync(HallB, h0, sN * e, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_last_error("stage_seq_fwd: state copy failed"); return 1; } }
-        else if (hipMemsetAsync(HallB, 0, sN * e, st) != hipSuccess) { set_last_error("stage_seq_fwd: memset failed"); return 1; }
-        if (wp != nullptr) RVT_TRY(rvt_lstm_scan3_pack(d.lstm_wn, wp, nullptr, C, stream));
-        RVT_TRY(stage_lstm_scan_fwd(d, r, x, Hall, c0, c_last, nullptr, nullptr, wp, T, B, stream));
-    } else {
-        float* cbuf[2] = {(float*)cv.take(sN * 4), (float*)cv.take(sN * 4)};
-        RVT_CHECK(cv.ok, "stage_seq_fwd: workspace carving overflow");
-        const void* h_prev = h0;
+    const size_t hB = s.state * s.e;                      // bytes of one h slot
+    // None state -> zeros (rnn.py:43-47); the scan kernels want the incoming h in slot 0, the per-step route reads it where it is
+    if (h0 == nullptr) RVT_HIP(hipMemsetAsync(HallB, 0, hB, st), "stage_seq_fwd: memset");
+    else if (r.lstm_route != 0) RVT_HIP(hipMemcpyAsync(HallB, h0, hB, hipMemcpyDeviceToDevice, st), "stage_seq_fwd: state copy");
+    if (c.wp != nullptr) RVT_TRY(rvt_lstm_scan3_pack(d.lstm_wn, c.wp, nullptr, d.C, stream));
+    std::vector<LstmStep> steps;
+    if (r.lstm_route == 0) {                              // c ping-pongs between two buffers; the last step writes c_last
+        const void* h_prev = h0 != nullptr ? h0 : HallB;
         const float* c_prev = c0;
-        if (h0 == nullptr) {                              // None state -> zeros (rnn.py:43-47)
-            if (hipMemsetAsync(HallB, 0, sN * e, st) != hipSuccess || hipMemsetAsync(cbuf[1], 0, sN * 4, st) != hipSuccess) {
-                set_last_error("stage_seq_fwd: memset failed"); return 1;
-            }
-            h_prev = HallB; c_prev = cbuf[1];
-        }
+        if (c0 == nullptr) { RVT_HIP(hipMemsetAsync(c.cbuf[1], 0, s.state * 4, st), "stage_seq_fwd: memset"); c_prev = c.cbuf[1]; }
         for (int t = 0; t < T; t++) {
-            float* c_out = t + 1 == T ? c_last : cbuf[t & 1];
-            RVT_TRY(rvt_lstm_fwd((const char*)x + (size_t)t * sN * e, h_prev, c_prev, d.lstm_w, d.lstm_b, HallB + (size_t)(t + 1) * sN * e, c_out,
-                                 nullptr, dt, Ms, C, stream));
-            h_prev = HallB + (size_t)(t + 1) * sN * e;
-            c_prev = c_out;
+            steps.push_back(LstmStep{h_prev, c_prev, HallB + (size_t)(t + 1) * hB, t + 1 == T ? c_last : c.cbuf[t & 1], nullptr});
+            h_prev = steps[t].h_out; c_prev = steps[t].c_out;
         }
     }
+    RVT_TRY(stage_lstm_fwd(d, r, s, c.bufs[xi], Hall, c0, c_last, nullptr, nullptr, c.wp, steps.data(), T, stream));
     return check_launch("stage_seq_fwd");
 }
 

@@ -5,8 +5,9 @@
 // (tests/test_stage_driver.py).  The routes come from rvt_stage_routes (capi_stage.hip), copied by the host into RvtStageTrain when
 // the forward is planned and read back unchanged by the backward; the host owns everything that outlives a call (saved activations,
 // gradient buckets); this file owns the order of launches and the backward's temporaries.  The forward's block loop and scan tail are
-// the ones of the no-grad driver (host.hpp: stage_blocks_fwd, stage_lstm_scan_fwd).  Nothing is launched that the operator entry
+// the ones of the no-grad driver (host.hpp: stage_blocks_fwd, stage_lstm_fwd).  Nothing is launched that the operator entry
 // points do not launch.
+#include <vector>
 #include "host.hpp"
 
 using namespace rvt;
@@ -14,16 +15,9 @@ using namespace rvt;
 namespace {
 static inline size_t zmax(size_t a, size_t b) { return a > b ? a : b; }
 
-struct TrainSizes {
-    int H, W, M; size_t e, act, state;
-    size_t wgrad_floats, mlp_floats, scan_floats, stem_floats;
-};
-static TrainSizes train_sizes(const RvtStageDesc& d, const RvtStageRoutes& t, int T, int B) {
-    TrainSizes s;
-    s.H = conv_out(d.H_in, d.k, d.stride, d.pad); s.W = conv_out(d.W_in, d.k, d.stride, d.pad);
-    s.e = elt_bytes(d.dtype);
-    const size_t tok = (size_t)T * B * s.H * s.W;
-    s.M = (int)tok; s.act = tok * d.C * s.e; s.state = (size_t)B * s.H * s.W * d.C;
+// what the backward's operators ask for as fp32 workspace on these routes (0 = that operator does not run)
+struct BwdFloats { size_t wgrad, mlp, scan, stem; };
+static BwdFloats bwd_floats(const RvtStageDesc& d, const RvtStageRoutes& r, const StageShape& s) {
     const int C = d.C, M = s.M;
     size_t w = rvt_wgrad_workspace_floats(d.dtype, 4 * C, 2 * C, M, 1);
     w = zmax(w, rvt_wgrad_workspace_floats(d.dtype, C, 4 * C, M, 1));
@@ -31,22 +25,31 @@ static TrainSizes train_sizes(const RvtStageDesc& d, const RvtStageRoutes& t, in
     w = zmax(w, rvt_wgrad_workspace_floats(d.dtype, C, C, M, 1));
     w = zmax(w, rvt_wgrad_workspace_floats(d.dtype, 3 * C, C, M, 1));
     w = zmax(w, rvt_wgrad_workspace_floats(d.dtype, C, d.k * d.k * d.cin_pad, M, 0));
-    s.wgrad_floats = zmax(w, (size_t)1 << 20);
-    s.mlp_floats = t.mlp_route == 1 ? rvt_mlp_bwd_fused_ws_floats(d.dtype, C, M) : 0;
-    s.scan_floats = (t.lstm_route == 1 && t.lstm_scan_wgrad) ? rvt_lstm_scan_bwd_ws_floats(d.dtype, C, B * s.H * s.W) : 0;
-    s.stem_floats = d.inp_u8 ? rvt_stem_wgrad_ws_floats(d.Cin, T * B, d.H_in, d.W_in) : 0;
-    return s;
+    BwdFloats f;
+    f.wgrad = zmax(w, (size_t)1 << 20);
+    f.mlp = r.mlp_route == 1 ? rvt_mlp_bwd_fused_ws_floats(d.dtype, C, M) : 0;
+    f.scan = (r.lstm_route == 1 && r.lstm_scan_wgrad) ? rvt_lstm_scan_bwd_ws_floats(d.dtype, C, s.Ms) : 0;
+    f.stem = d.inp_u8 ? rvt_stem_wgrad_ws_floats(d.Cin, s.F, d.H_in, d.W_in) : 0;
+    return f;
 }
-static size_t train_bwd_ws_bytes(const RvtStageDesc& d, const RvtStageRoutes& t, int T, int B) {
-    const TrainSizes s = train_sizes(d, t, T, B);
-    const size_t pad = (size_t)2 << 21;            // (2-MiB aligned pieces: up to one alignment skip + one round-up each)
-    size_t n = 3 * (s.act + pad);                  // dx ring (block cotangents)
-    n += 4 * s.act + pad;                          // dz of the ConvLSTM, then dh of the op-by-op MLP
-    n += 3 * s.act + pad;                          // dqkv
-    n += 2 * (s.act + pad);                        // da / du / dv2, dy0
-    n += s.state * s.e + pad;                      // per-step route: second dh buffer
-    n += (s.wgrad_floats + s.mlp_floats + s.scan_floats + s.stem_floats) * 4 + 4 * pad;
-    return n + pad;
+// Every piece the backward takes from its workspace, in the order it takes them (a braced list is evaluated left to right).  On a
+// counting Carver this is rvt_stage_seq_bwd_ws_bytes.
+struct BwdCarve {
+    void* ring[3];                // dx ring (block cotangents), [M][C] each
+    void* big4;                   // [M][4C]: dz of the ConvLSTM, then dh of the op-by-op MLP
+    void *dqkv, *t1, *dy0;        // [M][3C]; [M][C]: da / du / dv2; [M][C]
+    void* dh_b;                   // one h state - per-step route: second dh buffer
+    float *ws_wgrad, *ws_mlp, *ws_scan, *ws_stem;      // BwdFloats; NULL where 0
+};
+static BwdCarve carve_bwd(Carver& cv, const StageShape& s, const BwdFloats& f) {
+    auto floats = [&cv](size_t n) { return n ? (float*)cv.take(n * 4) : nullptr; };
+    return BwdCarve{{cv.take(s.act), cv.take(s.act), cv.take(s.act)}, cv.take(4 * s.act), cv.take(3 * s.act), cv.take(s.act), cv.take(s.act),
+                    cv.take(s.state * s.e), floats(f.wgrad), floats(f.mlp), floats(f.scan), floats(f.stem)};
+}
+static size_t bwd_ws_bytes(const StageShape& s, const BwdFloats& f) {
+    Carver cv = Carver::counting((size_t)1 << 21);
+    carve_bwd(cv, s, f);
+    return cv.bytes();
 }
 static bool desc_ok(const RvtStageDesc* d, const RvtStageTrain* t) {
     return d != nullptr && t != nullptr && d->struct_bytes == (int)sizeof(RvtStageDesc) && t->struct_bytes == (int)sizeof(RvtStageTrain) &&
@@ -61,41 +64,36 @@ int rvt_stage_seq_train_fwd(const RvtStageDesc* dp, const RvtStageTrain* tp, con
     const RvtStageDesc& d = *dp; const RvtStageTrain& t = *tp;
     RVT_CHECK(T >= 1 && B >= 1 && inp != nullptr && t.Hall != nullptr && t.c_last != nullptr && t.y0 != nullptr && t.x0 != nullptr,
               "stage_seq_train_fwd: bad arguments");
-    const int C = d.C, dt = d.dtype;
-    const TrainSizes s = train_sizes(d, t.routes, T, B);
-    const int H = s.H, W = s.W, M = s.M;
-    RVT_CHECK(H % d.ph == 0 && W % d.pw == 0, "stage_seq_train_fwd: %dx%d not divisible by the partition %dx%d", H, W, d.ph, d.pw);
-    RVT_CHECK((size_t)M * 4 * C < ((size_t)1 << 31), "stage_seq_train_fwd: %d token rows exceed the operators' 32-bit sizes", M);
-    hipStream_t st = (hipStream_t)stream;
+    StageShape s;
+    RVT_TRY(stage_shape(d, T, B, "stage_seq_train_fwd", &s));
     const RvtStageRoutes& r = t.routes;
     const int nb = 2 * d.num_blocks;
     RVT_CHECK(r.driver_covers && (nb == 0 || t.saved[0].xin == t.x0), "stage_seq_train_fwd: routes the driver does not cover, or saved[0].xin != x0");
     for (int bi = 0; bi < nb; bi++)       // what the backward reads beyond what the forward itself needs
         RVT_CHECK(t.saved[bi].a != nullptr && (r.mlp_route != 0 || t.saved[bi].hgp != nullptr), "stage_seq_train_fwd: block %d misses a / hgp", bi);
-    RVT_TRY(stage_blocks_fwd(d, r, inp, nullptr, t.y0, t.x0, t.saved, T, B, stream));
+    RVT_TRY(stage_blocks_fwd(d, r, s, inp, nullptr, t.y0, t.x0, t.saved, stream));
     const void* x = nb > 0 ? t.saved[nb - 1].xout : t.x0;
-    // ---- ConvLSTM over the T steps (rnn.py:43-67); Hall slot 0 = incoming h (host) ----
-    const int Ms = B * H * W;
-    char* const HallB = (char*)t.Hall;
+    // ---- ConvLSTM over the T steps (rnn.py:43-67); Hall slot 0 = incoming h, Call slot 0 = incoming c (host) ----
+    std::vector<LstmStep> steps;
     if (r.lstm_route != 0) {
         RVT_CHECK(t.Csave != nullptr && (r.lstm_route == 1 || t.gates != nullptr), "stage_seq_train_fwd: scan buffers missing");
-        RVT_TRY(stage_lstm_scan_fwd(d, r, x, t.Hall, c0, t.c_last, t.Csave, t.gates, t.lstm_wp3, T, B, stream));
     } else {
         RVT_CHECK(t.Call != nullptr && t.gates != nullptr, "stage_seq_train_fwd: per-step ConvLSTM buffers missing");
-        for (int ts = 0; ts < T; ts++)
-            RVT_TRY(rvt_lstm_fwd((const char*)x + (size_t)ts * s.state * s.e, HallB + (size_t)ts * s.state * s.e, t.Call + (size_t)ts * s.state,
-                                 d.lstm_w, d.lstm_b, HallB + (size_t)(ts + 1) * s.state * s.e, t.Call + (size_t)(ts + 1) * s.state,
-                                 (char*)t.gates + (size_t)ts * s.state * 4 * s.e, dt, Ms, C, stream));
-        if (hipMemcpyAsync(t.c_last, t.Call + (size_t)T * s.state, s.state * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            set_last_error("stage_seq_train_fwd: state copy failed"); return 1;
-        }
+        char* const HallB = (char*)t.Hall;
+        const size_t hB = s.state * s.e;                  // bytes of one h slot
+        for (int ts = 0; ts < T; ts++)                    // step ts: slot ts -> slot ts + 1 of Hall / Call, gates kept for BPTT
+            steps.push_back(LstmStep{HallB + ts * hB, t.Call + ts * s.state, HallB + (ts + 1) * hB, t.Call + (ts + 1) * s.state, (char*)t.gates + ts * 4 * hB});
     }
+    RVT_TRY(stage_lstm_fwd(d, r, s, x, t.Hall, c0, t.c_last, t.Csave, t.gates, t.lstm_wp3, steps.data(), T, stream));
+    if (r.lstm_route == 0)
+        RVT_HIP(hipMemcpyAsync(t.c_last, t.Call + (size_t)T * s.state, s.state * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream), "stage_seq_train_fwd: state copy");
     return check_launch("stage_seq_train_fwd");
 }
 
 size_t rvt_stage_seq_bwd_ws_bytes(const RvtStageDesc* d, const RvtStageTrain* t, int T, int B) {
-    if (!desc_ok(d, t) || T < 1 || B < 1) return 0;
-    return train_bwd_ws_bytes(*d, t->routes, T, B);
+    StageShape s;
+    if (!desc_ok(d, t) || T < 1 || B < 1 || stage_shape(*d, T, B, nullptr, &s) != 0) return 0;
+    return bwd_ws_bytes(s, bwd_floats(*d, t->routes, s));
 }
 
 int rvt_stage_seq_bwd(const RvtStageDesc* dp, const RvtStageTrain* tp, const void* inp, const void* dH, const float* dc_last,
@@ -103,24 +101,16 @@ int rvt_stage_seq_bwd(const RvtStageDesc* dp, const RvtStageTrain* tp, const voi
     RVT_CHECK(desc_ok(dp, tp) && tp->tb != nullptr, "stage_seq_bwd: bad descriptors");
     const RvtStageDesc& d = *dp; const RvtStageTrain& t = *tp;
     RVT_CHECK(T >= 1 && B >= 1 && inp != nullptr && dh0 != nullptr && dc0 != nullptr, "stage_seq_bwd: bad arguments");
-    RVT_CHECK(ws != nullptr && ws_bytes >= train_bwd_ws_bytes(d, t.routes, T, B), "stage_seq_bwd: workspace of %zu bytes < rvt_stage_seq_bwd_ws_bytes = %zu",
-              ws_bytes, train_bwd_ws_bytes(d, t.routes, T, B));
-    const int C = d.C, F = T * B, dt = d.dtype;
-    const TrainSizes s = train_sizes(d, t.routes, T, B);
-    const int H = s.H, W = s.W, M = s.M, Ms = B * H * W;
-    hipStream_t st = (hipStream_t)stream;
     const RvtStageRoutes& r = t.routes;
+    StageShape s;
+    RVT_TRY(stage_shape(d, T, B, "stage_seq_bwd", &s));
+    const BwdFloats f = bwd_floats(d, r, s);
+    const size_t need = bwd_ws_bytes(s, f);
+    RVT_CHECK(ws != nullptr && ws_bytes >= need, "stage_seq_bwd: workspace of %zu bytes < rvt_stage_seq_bwd_ws_bytes = %zu", ws_bytes, need);
+    const int C = d.C, F = s.F, dt = d.dtype, H = s.H, W = s.W, M = s.M, Ms = s.Ms;
+    hipStream_t st = (hipStream_t)stream;
     Carver cv{(char*)ws, ws_bytes, (size_t)1 << 21};
-    void* ring[3] = {cv.take(s.act), cv.take(s.act), cv.take(s.act)};
-    void* big4 = cv.take(4 * s.act);
-    void* dqkv = cv.take(3 * s.act);
-    void* t1 = cv.take(s.act);
-    void* dy0 = cv.take(s.act);
-    void* dh_b = cv.take(s.state * s.e);
-    float* ws_wgrad = (float*)cv.take(s.wgrad_floats * 4);
-    float* ws_mlp = s.mlp_floats ? (float*)cv.take(s.mlp_floats * 4) : nullptr;
-    float* ws_scan = s.scan_floats ? (float*)cv.take(s.scan_floats * 4) : nullptr;
-    float* ws_stem = s.stem_floats ? (float*)cv.take(s.stem_floats * 4) : nullptr;
+    const auto [ring, big4, dqkv, t1, dy0, dh_b, ws_wgrad, ws_mlp, ws_scan, ws_stem] = carve_bwd(cv, s, f);
     RVT_CHECK(cv.ok, "stage_seq_bwd: workspace carving overflow");
     const int nb = 2 * d.num_blocks;
     const void* x_last = nb > 0 ? t.saved[nb - 1].xout : t.x0;       // the ConvLSTM's input frames
@@ -139,8 +129,8 @@ int rvt_stage_seq_bwd(const RvtStageDesc* dp, const RvtStageTrain* tp, const voi
                                   r.lstm_route == 2 ? t.gates : nullptr, dt, Ms, C, T, stream));
     } else {
         RVT_CHECK(dH != nullptr, "stage_seq_bwd: the per-step route needs dH (zeros, not NULL)");
-        if (dc_last != nullptr) { if (hipMemcpyAsync(dc0, dc_last, s.state * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_last_error("stage_seq_bwd: copy failed"); return 1; } }
-        else if (hipMemsetAsync(dc0, 0, s.state * 4, st) != hipSuccess) { set_last_error("stage_seq_bwd: memset failed"); return 1; }
+        if (dc_last != nullptr) RVT_HIP(hipMemcpyAsync(dc0, dc_last, s.state * 4, hipMemcpyDeviceToDevice, st), "stage_seq_bwd: copy");
+        else RVT_HIP(hipMemsetAsync(dc0, 0, s.state * 4, st), "stage_seq_bwd: memset");
         void* dh_buf[2] = {dh0, dh_b};                   // step t writes dh_buf[t & 1]: the last one (t = 0) lands in dh0
         const void* dh_rec = nullptr;
         for (int ts = T - 1; ts >= 0; ts--) {

@@ -128,48 +128,27 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
                 sv.blocks.append(dict(xin=x, qkv=qkv, a=a, xmid=xmid, hg=hg, hgp=hgp, u=u, v2=v2))
             x = xout
 
-    Hall = torch.empty((T + 1, B, H, W, C), dtype=dt, device=dev)
     dws = sw.dws
     # a no-grad forward on the per-step route reads the incoming states where they are (streaming inference, T = 1: the two
     # state copies per stage were 5 % of the step); BPTT and the scan kernel want them in slot 0
     direct0 = (not save) and h0 is not None and r.lstm_route == 0 and h0.dtype == dt and h0.is_contiguous() \
         and c0 is not None and c0.dtype == torch.float32 and c0.is_contiguous()
-    if h0 is None:
-        Hall[0].zero_()                                                           # rnn.py:43-47
-    elif not direct0:
-        Hall[0].copy_(h0)
-    if r.lstm_route == 3:
-        # wide stage: all T steps in ONE launch, weights streamed in operand order, gates + cell states saved in dump order
-        c_last = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-        rows = ops.lstm_scan3_rows(C, B * H * W, r.lstm_scan3_rb)
-        Csave = torch.empty((T, rows, C), dtype=dt, device=dev) if save else None
-        gsave = torch.empty((T, rows, 4 * C), dtype=dt, device=dev) if save else None
-        ops.lstm_scan3_fwd(x.view(T, B, H, W, C), Hall, c0, c_last, Csave, sw.scan3_packed(bwd=False), sw.lstm_bn, gsave, r.lstm_scan3_rb)
-        if save:
-            sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, None, gsave
-            sv.xin_lstm, sv.hconv, sv.Csave, sv.c0 = x, None, Csave, (None if c0 is None else c0.clone())
-        return Hall, c_last, sv
+    lb = stage_driver.LstmBuffers(r, g, dt, dev, T, B, h0, c0, save, direct0)
+    Hall, Call, c_last = lb.Hall, lb.Call, lb.c_last
     if r.lstm_route != 0:
-        # all T steps in ONE launch: h / c stay on chip, BPTT keeps only a T-typed copy of the cell states
-        c_last = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-        Csave = torch.empty((T, B, H, W, C), dtype=dt, device=dev) if save else None
-        # C = 128 (bf16): weights in the register file; the gates are stored for a reverse scan that keeps W^T in registers
-        gsave = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev) if save and r.lstm_route == 2 else None
-        ops.lstm_scan_fwd(x.view(T, B, H, W, C), Hall, c0, c_last, Csave, sw.lstm_wn, sw.lstm_bn, gates_out=gsave)
+        # all T steps in ONE launch: h / c stay on chip, BPTT keeps only a T-typed copy of the cell states (+ the gates where the
+        # reverse scan reads them: route 2, weights in the register file; route 3, a wide stage, weights streamed in operand order,
+        # gates + cell states saved in dump order)
+        xs = x.view(T, B, H, W, C)
+        if r.lstm_route == 3:
+            ops.lstm_scan3_fwd(xs, Hall, c0, c_last, lb.Csave, sw.scan3_packed(bwd=False), sw.lstm_bn, lb.gates, r.lstm_scan3_rb)
+        else:
+            ops.lstm_scan_fwd(xs, Hall, c0, c_last, lb.Csave, sw.lstm_wn, sw.lstm_bn, gates_out=lb.gates)
         if save:
-            sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, None, gsave
-            # the incoming cell state may alias the caller's tensor (RNNStates resets states in place, modules/utils/detection.py:96-113):
-            # BPTT needs the value the forward saw, so it keeps a copy (B*H*W*C fp32 per stage)
-            sv.xin_lstm, sv.hconv, sv.Csave, sv.c0 = x, None, Csave, (None if c0 is None else c0.clone())
+            lb.fill_saved(sv, x)
         return Hall, c_last, sv
     # cell states: all T+1 slots are kept for BPTT; a no-grad forward ping-pongs between two
-    nc = T + 1 if save else 2
-    Call = torch.empty((nc, B, H, W, C), dtype=torch.float32, device=dev)
-    if h0 is None:
-        Call[0].zero_()
-    elif not direct0:
-        Call[0].copy_(c0)
-    gates = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev) if save else None
+    nc = Call.shape[0]
     # DWS-ConvLSTM (rnn.py:50-54): depth-wise 3x3 on h_{t-1} only, or on cat(x, h_{t-1}) (the x half batched over T)
     x_lstm = x
     hconv = None
@@ -187,13 +166,12 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
             bh = dws['b'] if dws['only_hidden'] else dws['b'][C:]
             h_in = ops.dwconv(h_prev, wh, bh, dws['k'], out=hconv[t if save else 0])
         ops.lstm_fwd(xt[t], h_in, c_prev, sw.lstm_w, sw.lstm_b, Hall[t + 1], Call[(t + 1) % nc],
-                     gates[t] if save else None)
-    # the final cell state is handed to the caller (RNNStates keeps it across steps): a buffer of its own when the
-    # T+1-slot array is what BPTT holds on to
-    c_last = Call[T % nc].clone() if save else Call[T % nc]
+                     lb.gates[t] if save else None)
     if save:
-        sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, Call, gates
-        sv.xin_lstm, sv.hconv, sv.Csave, sv.c0 = x_lstm, hconv, None, None
+        # the final cell state is handed to the caller (RNNStates keeps it across steps): a buffer of its own, since the
+        # T+1-slot array is what BPTT holds on to
+        c_last.copy_(Call[T])
+        lb.fill_saved(sv, x, x_lstm, hconv)
     return Hall, c_last, sv
 
 

@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib as L
+from . import _lib as L, tuning
 from ._header import STRUCTS, fields
 
 RvtBlockWeights, RvtStageDesc, RvtStageRoutes, RvtBlockSaved, RvtBlockTrain, RvtStageTrain = (
@@ -46,13 +46,15 @@ class StageCall:
         d.blocks = ctypes.cast(self.blocks, ctypes.POINTER(RvtBlockWeights))
         d.lstm_w, d.lstm_b, d.lstm_wn, d.lstm_bn = p(sw.lstm_w), p(sw.lstm_b), p(sw.lstm_wn), p(sw.lstm_bn)
         self.desc, self.sw, self.g, self.dtype = d, sw, g, dtype
-        self._ws_bytes = {}
+        self._ws_bytes, self._ws_gen = {}, tuning.generation
 
     def ws_bytes(self, T: int, B: int) -> int:
+        """rvt_stage_seq_fwd_ws_bytes, cached by what it depends on: (T, B) and the tuning record (this object outlives a tuning change)."""
+        if self._ws_gen != tuning.generation:
+            self._ws_bytes, self._ws_gen = {}, tuning.generation
         n = self._ws_bytes.get((T, B))
         if n is None:
-            n = int(L.get_lib().rvt_stage_seq_fwd_ws_bytes(ctypes.byref(self.desc), T, B))
-            self._ws_bytes[(T, B)] = n
+            n = self._ws_bytes[(T, B)] = int(L.get_lib().rvt_stage_seq_fwd_ws_bytes(ctypes.byref(self.desc), T, B))
         return n
 
 
@@ -83,6 +85,40 @@ def stage_seq_fwd(call: StageCall, inp: torch.Tensor, h0: Optional[torch.Tensor]
     return Hall, c_last
 
 
+class LstmBuffers:
+    """The ConvLSTM-side buffers of one stage forward, allocated by route for the host loop (rvt_amd/stage.py) and train_forward alike:
+    Hall (T+1,B,H,W,C), slot 0 = incoming h (zeros for None); c_last fp32, handed to the caller; scan routes when save: Csave, gates
+    (routes 2 / 3; route 3 in the kernel's dump order) and c0_saved - the incoming cell state may alias the caller's tensor (RNNStates
+    resets states in place, modules/utils/detection.py:96-113) and BPTT needs the value the forward saw; per-step route: Call, all T+1
+    cell states for BPTT or the two a no-grad forward ping-pongs between (c_last = the slot its last step writes), gates when save.
+    direct0: the no-grad host loop reads the incoming states where they are at step 0, slot 0 stays unwritten."""
+
+    def __init__(self, r: RvtStageRoutes, g, dt: torch.dtype, dev, T: int, B: int, h0, c0, save: bool, direct0: bool = False):
+        from . import ops
+        E = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)
+        st, lr = (B, g.H, g.W), r.lstm_route
+        self.Hall = E(T + 1, *st, g.C)
+        self.Csave = self.gates = self.Call = self.c0_saved = None
+        if lr == 0:
+            self.Call = E(T + 1 if save else 2, *st, g.C, dtype=torch.float32)
+            self.gates = E(T, *st, 4 * g.C) if save else None
+        elif save:
+            rows = (ops.lstm_scan3_rows(g.C, B * g.H * g.W, r.lstm_scan3_rb),) if lr == 3 else st
+            self.Csave, self.gates = E(T, *rows, g.C), (E(T, *rows, 4 * g.C) if lr != 1 else None)
+            self.c0_saved = None if c0 is None else c0.clone()
+        for buf, s0 in ((self.Hall, h0), (self.Call, c0)):
+            if buf is not None and h0 is None:
+                buf[0].zero_()                                                    # rnn.py:43-47
+            elif buf is not None and not direct0:
+                buf[0].copy_(s0)
+        self.c_last = self.Call[T % 2] if (lr == 0 and not save) else E(*st, g.C, dtype=torch.float32)
+
+    def fill_saved(self, sv, x: torch.Tensor, x_lstm: Optional[torch.Tensor] = None, hconv: Optional[torch.Tensor] = None) -> None:
+        """x: the stage's last block output; x_lstm / hconv: what the DWS-ConvLSTM of the host loop fed the cell instead."""
+        sv.x_last, sv.Hall, sv.Call, sv.gates = x, self.Hall, self.Call, self.gates
+        sv.xin_lstm, sv.hconv, sv.Csave, sv.c0 = (x if x_lstm is None else x_lstm), hconv, self.Csave, self.c0_saved
+
+
 # ---- training-side driver (round 6; include/rvt_hip.h: rvt_stage_seq_train_fwd / rvt_stage_seq_bwd, csrc/capi_train.hip) ----------------
 # plan() decides the routes; the host owns every tensor that outlives a call; the library sequences the launches.  `StageSaved` is filled
 # exactly as the Python host loop fills it, so either backward can consume it.
@@ -93,7 +129,6 @@ class TrainCall:
 
 def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0, c0, T: int, B: int):
     """Training forward of one stage in ONE library call.  Returns (Hall, c_last, StageSaved) like stage.stage_seq_forward."""
-    from . import ops
     from .stage import StageSaved
     sw, g = call.sw, call.g
     dt, dev = sw.conv_w.dtype, inp.device
@@ -127,41 +162,21 @@ def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0
             sv.blocks.append(s)
             x = xout
             i += 1
-    Hall = E(T + 1, B, H, W, C)
-    if h0 is None:
-        Hall[0].zero_()
-    else:
-        Hall[0].copy_(h0)
-    c_last = E(B, H, W, C, dtype=torch.float32)
+    lb = LstmBuffers(routes, g, dt, dev, T, B, h0, c0, save=True)
     lr = routes.lstm_route
-    Csave = gates = Call = None
     if lr == 3:
-        rows = ops.lstm_scan3_rows(C, B * H * W, routes.lstm_scan3_rb)
-        Csave, gates = E(T, rows, C), E(T, rows, 4 * C)
         tr.lstm_wp3 = L.ptr(sw.scan3_packed(bwd=False))
-    elif lr in (1, 2):
-        Csave = E(T, B, H, W, C)
-        gates = E(T, B, H, W, 4 * C) if lr == 2 else None
-    else:
-        Call = E(T + 1, B, H, W, C, dtype=torch.float32)
-        if h0 is None:
-            Call[0].zero_()
-        else:
-            Call[0].copy_(c0)
-        gates = E(T, B, H, W, 4 * C)
     tr.saved = ctypes.cast(saved_arr, ctypes.POINTER(RvtBlockSaved))
-    tr.y0, tr.x0, tr.Hall, tr.c_last = L.ptr(y0), L.ptr(x0), L.ptr(Hall), L.ptr(c_last)
-    tr.Csave, tr.gates, tr.Call = L.ptr(Csave), L.ptr(gates), L.ptr(Call)
+    tr.y0, tr.x0, tr.Hall, tr.c_last = L.ptr(y0), L.ptr(x0), L.ptr(lb.Hall), L.ptr(lb.c_last)
+    tr.Csave, tr.gates, tr.Call = L.ptr(lb.Csave), L.ptr(lb.gates), L.ptr(lb.Call)
     lib = L.get_lib()
     rc = lib.rvt_stage_seq_train_fwd(ctypes.byref(call.desc), ctypes.byref(tr), L.ptr(inp), L.ptr(c0) if lr != 0 else None, T, B, L.stream_of(inp))
     L.check('rvt_stage_seq_train_fwd', rc, lib)
-    sv.x_last, sv.Hall, sv.Call, sv.gates = x, Hall, Call, gates
-    sv.xin_lstm, sv.hconv, sv.Csave = x, None, Csave
-    sv.c0 = None if (c0 is None or lr == 0) else c0.clone()      # (scan routes: the state the forward saw; RNNStates resets states in place)
+    lb.fill_saved(sv, x)
     tc = TrainCall()
     tc.call, tc.tr, tc.saved_arr, tc.tb_arr, tc.inp, tc.keep = call, tr, saved_arr, None, inp, (y0, x0)
     sv.train = tc
-    return Hall, c_last, sv       # (per-step route: c_last was copied out of Call[T] by the library, BPTT keeps the T+1-slot array)
+    return lb.Hall, lb.c_last, sv  # (per-step route: c_last was copied out of Call[T] by the library, BPTT keeps the T+1-slot array)
 
 
 def train_backward(sw, g, sv, dH, dc_last, T: int, B: int, need_input_grad: bool, prev_cot, sg, pre: str):

@@ -33,6 +33,7 @@ TEST_GEOMETRY: Dict[str, int] = dict(gemm_resident=8, wgrad_slice_tokens=128, ro
 _overrides: Dict[str, int] = {}          # what the caller asked for on top of the library defaults
 _pushed_to = None                        # the library object that currently holds `_overrides`
 _cache: Dict[str, int] = {}
+generation = 0                           # bumped by every push(): a key for whatever is cached from the record (stage_driver.StageCall.ws_bytes)
 
 
 def _defaults(lib) -> RvtTuning:
@@ -43,7 +44,8 @@ def _defaults(lib) -> RvtTuning:
 
 def push(lib) -> None:
     """Install the current overrides into `lib` (called by rvt_amd._lib whenever the active library changes)."""
-    global _pushed_to, _cache
+    global _pushed_to, _cache, generation
+    generation += 1
     t = _defaults(lib)
     for k, v in _overrides.items():
         setattr(t, k, int(v))
