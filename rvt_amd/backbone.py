@@ -256,19 +256,14 @@ class RNNDetector(nn.Module):
             inp = src.contiguous()
         else:
             inp = ops.prepack_input(src, Hm, Wm, round8(Cin), dt)
-        key = (dt, u8, h, w, Hm, Wm)
-        calls = getattr(mw, '_stage_calls', None)
-        if calls is None or calls[0] != key:
-            calls = (key, [SD.StageCall(mw.stages[si], geoms[si], dt, u8 and si == 0, h, w) for si in range(ns)])
-            mw._stage_calls = calls
         feats, states = {}, []
         for si in range(ns):
             st = prev_states[si]
             h0 = c0 = None
             if st is not None:
                 h0, c0 = _to_cl(st[0], dt), _to_cl(st[1], torch.float32)
-            Hall, c_last = SD.stage_seq_fwd(calls[1][si], inp, h0, c0, T, B)
             g = geoms[si]
+            Hall, c_last = SD.stage_seq_fwd(mw.stage_call(si, g, inp), inp, h0, c0, T, B)
             inp = Hall[1:].reshape(T * B, g.H, g.W, g.C)
             feats[si + 1] = Hall[1:].permute(0, 1, 4, 2, 3)
             states.append((feats[si + 1][-1].clone(memory_format=torch.preserve_format), c_last.permute(0, 3, 1, 2)))
@@ -325,7 +320,6 @@ class _BackboneSeqFn(torch.autograd.Function):
         for si in range(ns):
             g = geoms[si]
             pre = f'stages.{si}.'
-            sw = mw.stages[si]
             h0, c0 = states_in[2 * si], states_in[2 * si + 1]
             if h0 is not None:
                 h0, c0 = _to_cl(h0, dt), _to_cl(c0, torch.float32)
@@ -333,7 +327,7 @@ class _BackboneSeqFn(torch.autograd.Function):
             if si == 0 and token_masks is not None:
                 assert mod.stages[0].mask_token is not None, 'No mask token present in this stage'
                 tm, mt = token_masks.to(xs.device), p[pre + 'mask_token'].detach()
-            Hall, c_last, sv = stage_seq_forward(sw, g, inp, h0, c0, T, B, need_grad, tm, mt)
+            Hall, c_last, sv = stage_seq_forward(mw.stage_call(si, g, inp), inp, h0, c0, T, B, need_grad, tm, mt)
             svs.append(sv)
             inp = Hall[1:].reshape(T * B, g.H, g.W, g.C)
             outs += [Hall[1:].permute(0, 1, 4, 2, 3), c_last.permute(0, 3, 1, 2)]
@@ -390,8 +384,7 @@ class _BackboneSeqFn(torch.autograd.Function):
                 gp = geoms[si - 1]
                 prev_cot = _to_cl(gout[2 * (si - 1)], dt).view(T * B, gp.H, gp.W, gp.C)
             d_in, dh0, dc0 = stage_seq_backward(mw.stages[si], g, ctx.svs[si], dH, dc_last, T, B, si > 0, prev_cot,
-                                                mw.grads[si], f'stages.{si}.',
-                                                finalize=lambda si=si: mw.finalize_stage_grads(si))
+                                                mw.grads[si], finalize=lambda si=si: mw.finalize_stage_grads(si))
             d_from_above = d_in
             call_hook(si)                 # every parameter gradient of the stage is final
             if ctx.needs_input_grad[4 + 2 * si]:

@@ -226,21 +226,11 @@ class ConvPack:
                 Cout, Cin, k, s, pad = c.out_channels, c.in_channels, c.ksize, c.stride, c.pad
                 w = c.conv.weight.detach()
                 wp = arT.take(Cout, k * k * Cin)
-                parts, total = [], 0
-                for py in range(s):
-                    for px in range(s):
-                        ky, kx = weights.conv_dgrad_taps(k, s, pad, py), weights.conv_dgrad_taps(k, s, pad, px)
-                        parts.append((ky, kx, Cin * len(ky) * len(kx) * Cout))
-                        total += parts[-1][2]
-                wd = arT.take(total)
-                dwp = ar32.take(Cout, k * k * Cin)
                 if second:
                     weights._pack_entry(tab, w, wp, weights.PACK_CONV_FWD, (Cout, Cin, k, Cin))
-                    off = 0
-                    for ky, kx, cnt in parts:
-                        if cnt:
-                            weights._pack_entry(tab, w, wd[off:off + cnt], weights.PACK_CONV_DGRAD, (Cout, Cin, k, len(ky), len(kx)), None, ky, kx, n=cnt)
-                        off += cnt
+                wd = weights.take_conv_dgrad(tab if second else None, arT, w, Cout, Cin, k, s, pad)
+                dwp = ar32.take(Cout, k * k * Cin)
+                if second:
                     c._pk.wp, c._pk.wd, c._pk.dwp = wp, wd, dwp
         self.bufT, self.buf32 = arT.buf, ar32.buf
         self.stats_all = ar32.buf[:n_stats]

@@ -56,16 +56,17 @@ class StageSaved:
         self.train = None           # set by the C-side training driver (rvt_amd/stage_driver.py: train_forward)
 
 
-def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[Tensor], c0: Optional[Tensor],
+def stage_seq_forward(call: stage_driver.StageCall, inp: Tensor, h0: Optional[Tensor], c0: Optional[Tensor],
                       T: int, B: int, save: bool, token_mask: Optional[Tensor] = None,
                       mask_token: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[StageSaved]]:
-    """inp: (T*B, H_in, W_in, cin_pad), or the uint8 planes (T*B, Cin, h, w) where ops.stem_supported.  Returns Hall (T+1,B,H,W,C), the final cell state (B,H,W,C) fp32, saved."""
+    """call: the stage's descriptor for this input flavour (weights.ModelWeights.stage_call).  inp: (T*B, H_in, W_in, cin_pad), or the uint8 planes
+    (T*B, Cin, h, w) where ops.stem_supported.  Returns Hall (T+1,B,H,W,C), the final cell state (B,H,W,C) fp32, saved."""
+    sw, g = call.sw, call.g
     F_ = T * B
     H, W, C = g.H, g.W, g.C
     dt, dev = sw.conv_w.dtype, inp.device
     u8 = inp.dtype == torch.uint8
-    call = stage_driver.StageCall(sw, g, dt, u8, inp.shape[-2] if u8 else 0, inp.shape[-1] if u8 else 0)
-    r = stage_driver.plan(sw, g, dt, T, B, save, token_mask, call)
+    r = stage_driver.plan(call, T, B, save, token_mask)
     if save and r.driver_covers and tuning.get('route_stage_driver_train') != 0:
         # the whole training forward of the stage as ONE library call (include/rvt_hip.h: rvt_stage_seq_train_fwd) where covered
         return stage_driver.train_forward(call, r, inp, h0, c0, T, B)
@@ -177,21 +178,22 @@ def stage_seq_forward(sw: StageWeights, g: StageGeom, inp: Tensor, h0: Optional[
 
 def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optional[Tensor], dc_last: Optional[Tensor],
                        T: int, B: int, need_input_grad: bool, prev_cot: Optional[Tensor],
-                       sg: StageGrads, pre: str, finalize=None) -> Tuple[Optional[Tensor], Tensor, Tensor]:
+                       sg: StageGrads, finalize=None) -> Tuple[Optional[Tensor], Tensor, Tensor]:
     """dH: (T,B,H,W,C) cotangent of Hall[1:] (None = zeros); dc_last: (B,H,W,C) fp32 cotangent of Call[T].
     prev_cot: cotangent already attached to this stage's INPUT frames (T*B,H_in,W_in,Cin) (added to the conv dgrad).
-    Parameter gradients are ACCUMULATED into the views of the stage's fp32 bucket `sg` (rvt_amd/weights.py); `finalize`
+    Parameter gradients are ACCUMULATED into the views of the stage's fp32 bucket, read from its records `sg.stage` / `sg.blocks` under
+    the header's slot names (rvt_amd/weights.py: BLOCK_GRADS, STAGE_GRADS, HOST_LOOP_GRADS); `finalize`
     (LayerScale fold + conv unpack, two table launches) runs behind the last weight-gradient GEMM of the stage.
     Returns (d_input or None, dh0, dc0)."""
     F_ = T * B
     H, W, C = g.H, g.W, g.C
     dt, dev = sv.y0.dtype, sv.y0.device
     f32 = torch.float32
-    G = sg.g
+    gs = sg.stage
     r = sv.routes                # what the forward was planned with: the tuning record is not consulted again
     if sv.train is not None:
         # BPTT + block / conv backward of the stage as ONE library call (rvt_stage_seq_bwd); the LayerScale fold / conv unpack follow
-        out = stage_driver.train_backward(sw, g, sv, dH, dc_last, T, B, need_input_grad, prev_cot, sg, pre)
+        out = stage_driver.train_backward(sv, dH, dc_last, T, B, need_input_grad, prev_cot)
         if finalize is not None:
             finalize()
         return out
@@ -220,8 +222,7 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
         ops.lstm_scan_bwd(sv.xin_lstm.view(T, B, H, W, C), sv.Hall, sv.Csave, sv.c0, dH,
                           None if dc_last is None else dc_last.to(f32).contiguous(), sw.lstm_wn, sw.lstm_wt, sw.lstm_bn,
                           dx, dz, dh_rec, dc_rec,
-                          dw=G(pre + 'lstm.conv1x1.weight').view(4 * C, 2 * C) if lstm_wgrad_done else None,
-                          db=G(pre + 'lstm.conv1x1.bias') if lstm_wgrad_done else None, gates=sv.gates)
+                          dw=gs.d_lstm_w if lstm_wgrad_done else None, db=gs.d_lstm_b if lstm_wgrad_done else None, gates=sv.gates)
     else:
         dz = torch.empty((T, B, H, W, 4 * C), dtype=dt, device=dev)
         if dH is None:
@@ -243,14 +244,13 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
             dh_rec = nxt
     if not lstm_wgrad_done:
         h_seg = sv.Hall[:T].reshape(F_, H, W, C) if dws is None else sv.hconv.view(F_, H, W, C)
-        ops.lstm_wgrad(dz.view(F_, H, W, 4 * C), sv.xin_lstm, h_seg, G(pre + 'lstm.conv1x1.weight').view(4 * C, 2 * C),
-                       G(pre + 'lstm.conv1x1.bias'))
+        ops.lstm_wgrad(dz.view(F_, H, W, 4 * C), sv.xin_lstm, h_seg, gs.d_lstm_w, gs.d_lstm_b)
     dh0, dc0 = dh_rec, dc_rec
     dx = dx.view(F_, H, W, C)
     if dws is not None:
         kk = dws['k']
         cg = dws['w'].shape[0]
-        dwd, dbd = G(pre + 'lstm.conv3x3_dws.weight').view(cg, kk * kk), G(pre + 'lstm.conv3x3_dws.bias')
+        dwd, dbd = gs.d_dws_w.view(cg, kk * kk), gs.d_dws_b
         hprev = sv.Hall[:T].reshape(F_, H, W, C)
         if dws['only_hidden']:
             ops.dwconv_wgrad(hprev, dhc.view(F_, H, W, C), dwd, dbd, kk)
@@ -269,10 +269,10 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
             window = which == 0
             bi_flat -= 1
             s = sv.blocks[bi_flat]
-            bp = f'{pre}att_blocks.{pi}.{"att_window" if window else "att_grid"}.'
+            gb = sg.blocks[bi_flat]
             # MLP branch: xout = xmid + g2 * (gelu(hd) W2^T + b2).  The weight-gradient GEMM delivers the raw products
             # S2 = dxout^T g and cs2 = colsum(dxout); LayerScale is folded in by the finalize table launch.
-            dn2w, dn2b = G(bp + 'norm2.weight'), G(bp + 'norm2.bias')
+            dn2w, dn2b = gb.d_n2_w, gb.d_n2_b
             assert (s['hg'] is None) == (r.mlp_route == 1) and (s['qkv'] is None) == bool(r.attn_block)
             if r.mlp_route == 1:
                 # everything on chip: recompute, both input-gradient products, LayerNorm backward and the fc1 / fc2 weight
@@ -281,16 +281,14 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                 # otherwise two: the weight-gradient half (which needs all 2 x 64 x 256 accumulators), then the input-gradient half
                 if r.mlp_bwd_both:
                     dxmid = ops.mlp_bwd_recompute_both(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'], bw['fc2_wt'],
-                                                       bw['fc1_wt'], dn2w, dn2b, G(bp + 'mlp.net.0.0.weight'),
-                                                       G(bp + 'mlp.net.0.0.bias'), G(bp + 'S2'), G(bp + 'cs2'), g.eps)
+                                                       bw['fc1_wt'], dn2w, dn2b, gb.d_fc1_w, gb.d_fc1_b, gb.d_S2, gb.d_cs2, g.eps)
                 else:
                     ops.mlp_bwd_recompute_wgrad(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'],
-                                                bw['fc2_wt'], G(bp + 'mlp.net.0.0.weight'), G(bp + 'mlp.net.0.0.bias'),
-                                                G(bp + 'S2'), G(bp + 'cs2'), g.eps)
+                                                bw['fc2_wt'], gb.d_fc1_w, gb.d_fc1_b, gb.d_S2, gb.d_cs2, g.eps)
                     dxmid = ops.mlp_bwd_recompute_dgrad(dx, s['xmid'], bw['n2_w'], bw['n2_b'], bw['fc1_w'], bw['fc1_b'],
                                                         bw['fc2_wt'], bw['fc1_wt'], dn2w, dn2b, g.eps)
             else:
-                ops.linear_wgrad(dx, s['hg'], G(bp + 'S2'), gelu_in=bool(r.mlp_store_pre), colsum_out=G(bp + 'cs2'))
+                ops.linear_wgrad(dx, s['hg'], gb.d_S2, gelu_in=bool(r.mlp_store_pre), colsum_out=gb.d_cs2)
                 fused = bool(r.mlp_bwd_dgrad)
                 if fused:       # fc2 dgrad * gp, fc1 dgrad and LayerNorm-2 backward (+ residual) in one kernel
                     dhd, dxmid = ops.mlp_bwd_dgrad(dx, s['hgp'], s['xmid'], bw['n2_w'], bw['fc2_wt'], bw['fc1_wt'], dn2w,
@@ -300,7 +298,7 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                 else:
                     dhd = ops.linear_dgrad(dx, bw['fc2_wt'], mul=s['hgp'])
                 v2 = s['v2'] if s['v2'] is not None else ops.layernorm_fwd(s['xmid'], bw['n2_w'], bw['n2_b'], g.eps)
-                ops.linear_wgrad(dhd, v2, G(bp + 'mlp.net.0.0.weight'), colsum_out=G(bp + 'mlp.net.0.0.bias'))
+                ops.linear_wgrad(dhd, v2, gb.d_fc1_w, colsum_out=gb.d_fc1_b)
                 del v2
                 if not fused:
                     if r.dgrad_ln_fc1:     # fc1 input gradient + norm2 backward + residual: one launch
@@ -311,60 +309,53 @@ def stage_seq_backward(sw: StageWeights, g: StageGeom, sv: StageSaved, dH: Optio
                         del dv2
                 del dhd
             # attention branch: xmid = xin + g1 * (a Wp^T + bp)
-            ops.linear_wgrad(dxmid, s['a'], G(bp + 'S1'), colsum_out=G(bp + 'cs1'))
+            ops.linear_wgrad(dxmid, s['a'], gb.d_S1, colsum_out=gb.d_cs1)
             if r.attn_block:
-                # fused: proj / attention / qkv input gradients and the norm1 backward in one launch (from the block input)
-                has_n1 = bw['n1_w'] is not None
+                # fused: proj / attention / qkv input gradients and the norm1 backward in one launch (from the block input; a block
+                # without norm1 has no d_n1_* either)
                 if bi_flat == 0 and r.attn_preln:
                     # the stage's first block: its input is the down-sampling norm's output, and nothing sits between them -
                     # the same launch carries the gradient through that norm (dy0 instead of dx)
                     dy0_fused, dqkv = ops.attn_block_bwd_preln(s['xin'], sv.y0, dxmid, sw.ln_w, bw['qkv_w'], bw['qkv_b'], bw['proj_wt'],
-                                                               G(pre + 'downsample_cf2cl.norm.weight'),
-                                                               G(pre + 'downsample_cf2cl.norm.bias'), F_, H, W, C, g.dim_head,
-                                                               g.ph, g.pw, window, g.eps)
+                                                               gs.d_ln_w, gs.d_ln_b, F_, H, W, C, g.dim_head, g.ph, g.pw, window, g.eps)
                     dx, u = None, None
                 else:
                     dy0_fused = None
                     dx, dqkv, u = ops.attn_block_bwd(s['xin'], dxmid, bw['n1_w'], bw['n1_b'], bw['qkv_w'], bw['qkv_b'], bw['proj_wt'],
-                                                     G(bp + 'norm1.weight') if has_n1 else None,
-                                                     G(bp + 'norm1.bias') if has_n1 else None, F_, H, W, C, g.dim_head, g.ph, g.pw,
-                                                     window, g.eps)
+                                                     gb.d_n1_w, gb.d_n1_b, F_, H, W, C, g.dim_head, g.ph, g.pw, window, g.eps)
                 u = s['xin'] if u is None else u
-                ops.linear_wgrad(dqkv, u, G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
+                ops.linear_wgrad(dqkv, u, gb.d_qkv_w, colsum_out=gb.d_qkv_b)
                 del dqkv, dxmid, u
                 continue
             da = ops.linear_dgrad(dxmid, bw['proj_wt'])
             dqkv = ops.attn_bwd(s['qkv'], da, F_, H, W, C, g.dim_head, g.ph, g.pw, window)
             del da
-            ops.linear_wgrad(dqkv, s['u'], G(bp + 'self_attn.qkv.weight'), colsum_out=G(bp + 'self_attn.qkv.bias'))
+            ops.linear_wgrad(dqkv, s['u'], gb.d_qkv_w, colsum_out=gb.d_qkv_b)
             if bi_flat == 0 and r.attn_preln:
                 # the stage's first block: qkv input gradient + residual cotangent carried through the down-sampling norm (one launch)
-                dy0_fused = ops.linear_dgrad_preln(dqkv, bw['qkv_w'], sv.y0, dxmid, sw.ln_w, G(pre + 'downsample_cf2cl.norm.weight'),
-                                                   G(pre + 'downsample_cf2cl.norm.bias'), g.eps)
+                dy0_fused = ops.linear_dgrad_preln(dqkv, bw['qkv_w'], sv.y0, dxmid, sw.ln_w, gs.d_ln_w, gs.d_ln_b, g.eps)
                 dx = None
             elif bw['n1_w'] is None:
                 dx = ops.linear_dgrad(dqkv, bw['qkv_wt'], add=dxmid)
             elif r.dgrad_ln_qkv:           # qkv input gradient + norm1 backward + residual: one launch
-                dx = ops.linear_dgrad_ln(dqkv, bw['qkv_w'], s['xin'], dxmid, bw['n1_w'], G(bp + 'norm1.weight'),
-                                         G(bp + 'norm1.bias'), g.eps)
+                dx = ops.linear_dgrad_ln(dqkv, bw['qkv_w'], s['xin'], dxmid, bw['n1_w'], gb.d_n1_w, gb.d_n1_b, g.eps)
             else:
                 du = ops.linear_dgrad(dqkv, bw['qkv_wt'])
-                dx = ops.layernorm_bwd(s['xin'], bw['n1_w'], du, dxmid, G(bp + 'norm1.weight'), G(bp + 'norm1.bias'), g.eps)
+                dx = ops.layernorm_bwd(s['xin'], bw['n1_w'], du, dxmid, gb.d_n1_w, gb.d_n1_b, g.eps)
                 del du
             del dqkv, dxmid
 
     # ---- token mask, down-sampling LayerNorm + conv ---------------------------------------------------------
     if sv.mask is not None:
-        ops.token_mask_bwd(dx, sv.mask, G(pre + 'mask_token').view(C))            # also zeroes dx on masked tokens
+        ops.token_mask_bwd(dx, sv.mask, gs.d_mask_token.view(C))            # also zeroes dx on masked tokens
     if dy0_fused is not None:
         dy0 = dy0_fused                                                           # (rvt_attn_block_bwd_preln of the first block)
     else:
-        dy0 = ops.layernorm_bwd(sv.y0, sw.ln_w, dx, None, G(pre + 'downsample_cf2cl.norm.weight'),
-                                G(pre + 'downsample_cf2cl.norm.bias'), g.eps)
+        dy0 = ops.layernorm_bwd(sv.y0, sw.ln_w, dx, None, gs.d_ln_w, gs.d_ln_b, g.eps)
     if sv.inp.dtype == torch.uint8:
-        ops.stem_wgrad(sv.inp, dy0, G('raw/conv'), g.H_in, g.W_in)
+        ops.stem_wgrad(sv.inp, dy0, gs.d_raw_conv, g.H_in, g.W_in)
     else:
-        ops.conv_wgrad(sv.inp, dy0, G('raw/conv'), g.k, g.stride, g.pad)
+        ops.conv_wgrad(sv.inp, dy0, gs.d_raw_conv, g.k, g.stride, g.pad)
     if finalize is not None:
         finalize()               # in stream order behind every weight-gradient GEMM of this stage
     d_in = None

@@ -23,9 +23,10 @@ RvtBlockWeights, RvtStageDesc, RvtStageRoutes, RvtBlockSaved, RvtBlockTrain, Rvt
 
 
 class StageCall:
-    """Descriptor of one stage for one input flavour; keeps the host-side block array (and through `sw` the device tensors) alive."""
+    """Descriptor of one stage for one input flavour; keeps the host-side block array (and through `sw` the device tensors) alive.
+    Built and kept by weights.ModelWeights.stage_call; `train`: the stage's TrainTables where the weight set has gradient buckets."""
 
-    def __init__(self, sw, g, dtype: torch.dtype, inp_u8: bool, h_raw: int, w_raw: int):
+    def __init__(self, sw, g, dtype: torch.dtype, inp_u8: bool, h_raw: int, w_raw: int, train: Optional['TrainTables'] = None):
         p = L.ptr
         nb = 2 * g.num_blocks
         self.blocks = (RvtBlockWeights * max(nb, 1))()
@@ -45,7 +46,7 @@ class StageCall:
         d.conv_w, d.ln_w, d.ln_b = p(sw.conv_w), p(sw.ln_w), p(sw.ln_b)
         d.blocks = ctypes.cast(self.blocks, ctypes.POINTER(RvtBlockWeights))
         d.lstm_w, d.lstm_b, d.lstm_wn, d.lstm_bn = p(sw.lstm_w), p(sw.lstm_b), p(sw.lstm_wn), p(sw.lstm_bn)
-        self.desc, self.sw, self.g, self.dtype = d, sw, g, dtype
+        self.desc, self.sw, self.g, self.dtype, self.train = d, sw, g, dtype, train
         self._ws_bytes, self._ws_gen = {}, tuning.generation
 
     def ws_bytes(self, T: int, B: int) -> int:
@@ -58,9 +59,9 @@ class StageCall:
         return n
 
 
-def plan(sw, g, dt, T: int, B: int, save: bool, token_mask, call: Optional[StageCall] = None) -> RvtStageRoutes:
-    """The routes of one stage forward (and of its backward when save).  `call`: the stage's descriptor where the caller has one."""
-    call = call or StageCall(sw, g, dt, False, 0, 0)
+def plan(call: StageCall, T: int, B: int, save: bool, token_mask) -> RvtStageRoutes:
+    """The routes of one stage forward (and of its backward when save)."""
+    sw = call.sw
     r = RvtStageRoutes()
     lib = L.get_lib()
     L.check('rvt_stage_routes', lib.rvt_stage_routes(ctypes.byref(call.desc), T, B, int(save), int(sw.dws is not None), int(token_mask is not None),
@@ -122,9 +123,30 @@ class LstmBuffers:
 # ---- training-side driver (round 6; include/rvt_hip.h: rvt_stage_seq_train_fwd / rvt_stage_seq_bwd, csrc/capi_train.hip) ----------------
 # plan() decides the routes; the host owns every tensor that outlives a call; the library sequences the launches.  `StageSaved` is filled
 # exactly as the Python host loop fills it, so either backward can consume it.
+class TrainTables:
+    """What the training driver's records hold for as long as a weight set lives, filled once by header field name
+    (weights.ModelWeights._build_grads): the RvtBlockTrain host array - the W^T arena views of `sw.blocks` and the accumulators of the
+    gradient records `sg.blocks` - and an RvtStageTrain `template` with `tb`, the stage-level weight copies and the stage record's
+    accumulators.  Every forward starts its own RvtStageTrain from the template; the block array is shared."""
+
+    def __init__(self, sw, sg):
+        self.tb = (RvtBlockTrain * max(len(sg.blocks), 1))()
+        for b, bw, gb in zip(self.tb, (bw for pair in sw.blocks for bw in pair), sg.blocks):
+            for k in fields(RvtBlockTrain):
+                setattr(b, k, L.ptr(getattr(gb, k) if k.startswith('d_') else bw[k]))
+        t = self.template = RvtStageTrain()
+        t.struct_bytes = ctypes.sizeof(RvtStageTrain)
+        t.tb = ctypes.cast(self.tb, ctypes.POINTER(RvtBlockTrain))
+        for k in fields(RvtStageTrain):
+            if k.startswith('d_'):
+                setattr(t, k, L.ptr(getattr(sg.stage, k)))
+        t.lstm_wt, t.conv_wd4, t.conv_wd = L.ptr(sw.lstm_wt), L.ptr(sw.conv_wd4), L.ptr(sw.conv_wd)
+
+
 class TrainCall:
-    """Everything one stage's training forward built for its backward: descriptors, host-side block arrays, the routes taken."""
-    __slots__ = ('call', 'tr', 'saved_arr', 'tb_arr', 'inp', 'keep')
+    """Everything one stage's training forward built for its backward: the descriptor, its own RvtStageTrain (a copy of the weight
+    set's template, which keeps the shared block table alive through `call.train`) and RvtBlockSaved array, the routes taken."""
+    __slots__ = ('call', 'tr', 'saved_arr', 'inp', 'keep')
 
 
 def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0, c0, T: int, B: int):
@@ -135,8 +157,8 @@ def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0
     H, W, C = g.H, g.W, g.C
     F_ = T * B
     E = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=dev)
-    tr = RvtStageTrain()
-    tr.struct_bytes, tr.routes = ctypes.sizeof(RvtStageTrain), routes
+    tr = RvtStageTrain.from_buffer_copy(call.train.template)
+    tr.routes = routes
     sv = StageSaved()
     sv.routes = routes
     y0, x0 = E(F_, H, W, C), E(F_, H, W, C)
@@ -174,43 +196,21 @@ def train_forward(call: StageCall, routes: RvtStageRoutes, inp: torch.Tensor, h0
     L.check('rvt_stage_seq_train_fwd', rc, lib)
     lb.fill_saved(sv, x)
     tc = TrainCall()
-    tc.call, tc.tr, tc.saved_arr, tc.tb_arr, tc.inp, tc.keep = call, tr, saved_arr, None, inp, (y0, x0)
+    tc.call, tc.tr, tc.saved_arr, tc.inp, tc.keep = call, tr, saved_arr, inp, (y0, x0)
     sv.train = tc
     return lb.Hall, lb.c_last, sv  # (per-step route: c_last was copied out of Call[T] by the library, BPTT keeps the T+1-slot array)
 
 
-def train_backward(sw, g, sv, dH, dc_last, T: int, B: int, need_input_grad: bool, prev_cot, sg, pre: str):
+def train_backward(sv, dH, dc_last, T: int, B: int, need_input_grad: bool, prev_cot):
     """BPTT backward of one stage in ONE library call.  Returns (d_input or None, dh0, dc0) like stage.stage_seq_backward."""
     tc = sv.train
     tr, call = tc.tr, tc.call
+    sw, g = call.sw, call.g
     dt, dev = sv.y0.dtype, sv.y0.device
     H, W, C = g.H, g.W, g.C
-    G = sg.g
-    nb = 2 * g.num_blocks
-    tb_arr = (RvtBlockTrain * max(nb, 1))()
-    i = 0
-    for pi, pair in enumerate(sw.blocks):
-        for which, bw in enumerate(pair):
-            bp = f'{pre}att_blocks.{pi}.{"att_window" if which == 0 else "att_grid"}.'
-            b = tb_arr[i]
-            b.qkv_wt, b.proj_wt, b.fc1_wt, b.fc2_wt = L.ptr(bw['qkv_wt']), L.ptr(bw['proj_wt']), L.ptr(bw['fc1_wt']), L.ptr(bw['fc2_wt'])
-            has_n1 = bw['n1_w'] is not None
-            b.d_n1_w, b.d_n1_b = (L.ptr(G(bp + 'norm1.weight')), L.ptr(G(bp + 'norm1.bias'))) if has_n1 else (None, None)
-            b.d_qkv_w, b.d_qkv_b = L.ptr(G(bp + 'self_attn.qkv.weight')), L.ptr(G(bp + 'self_attn.qkv.bias'))
-            b.d_S1, b.d_cs1 = L.ptr(G(bp + 'S1')), L.ptr(G(bp + 'cs1'))
-            b.d_n2_w, b.d_n2_b = L.ptr(G(bp + 'norm2.weight')), L.ptr(G(bp + 'norm2.bias'))
-            b.d_fc1_w, b.d_fc1_b = L.ptr(G(bp + 'mlp.net.0.0.weight')), L.ptr(G(bp + 'mlp.net.0.0.bias'))
-            b.d_S2, b.d_cs2 = L.ptr(G(bp + 'S2')), L.ptr(G(bp + 'cs2'))
-            i += 1
-    tc.tb_arr = tb_arr
-    tr.tb = ctypes.cast(tb_arr, ctypes.POINTER(RvtBlockTrain))
     tr.c0_saved = L.ptr(sv.c0)
-    tr.lstm_wt, tr.conv_wd4, tr.conv_wd = L.ptr(sw.lstm_wt), L.ptr(sw.conv_wd4), L.ptr(getattr(sw, 'conv_wd', None))
     if tr.routes.lstm_route == 3:
         tr.lstm_wtp3 = L.ptr(sw.scan3_packed(bwd=True))
-    tr.d_lstm_w, tr.d_lstm_b = L.ptr(G(pre + 'lstm.conv1x1.weight')), L.ptr(G(pre + 'lstm.conv1x1.bias'))
-    tr.d_ln_w, tr.d_ln_b = L.ptr(G(pre + 'downsample_cf2cl.norm.weight')), L.ptr(G(pre + 'downsample_cf2cl.norm.bias'))
-    tr.d_raw_conv = L.ptr(G('raw/conv'))
     if dH is None and tr.routes.lstm_route == 0:
         dH = torch.zeros((T, B, H, W, C), dtype=dt, device=dev)
     dcl = None if dc_last is None else dc_last.to(torch.float32).contiguous()

@@ -15,12 +15,13 @@ allocation, no concatenation.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib as L
+from . import _lib as L, stage_driver
 
 Tensor = torch.Tensor
 
@@ -66,6 +67,23 @@ class _Arena:
         return self.buf[off:off + cnt].view(*shape)
 
 
+def take_conv_dgrad(tab: Optional[L.DeviceTable], arena: _Arena, w: Optional[Tensor], Cout: int, Cin: int, k: int, stride: int,
+                    pad: int) -> Optional[Tensor]:
+    """The input-gradient weight copy of a strided conv, for the backbone's ModelWeights and the neck's ConvPack alike: concatenation over
+    parity classes (py,px) of [Cin][(a,b,cout)] = w[cout,cin,Ky[a],Kx[b]] - the layout rvt_conv_dgrad walks (rvt_amd/csrc/capi.hip).
+    Takes the room from `arena`; with a table (the arenas' second pass) one PACK_CONV_DGRAD entry per class that has taps.
+    pack_conv_dgrad below is the tests' host restatement."""
+    classes = [(conv_dgrad_taps(k, stride, pad, py), conv_dgrad_taps(k, stride, pad, px)) for py in range(stride) for px in range(stride)]
+    wd = arena.take(sum(Cin * len(ky) * len(kx) * Cout for ky, kx in classes))
+    off = 0
+    for ky, kx in classes:
+        cnt = Cin * len(ky) * len(kx) * Cout
+        if cnt and tab is not None:
+            _pack_entry(tab, w, wd[off:off + cnt], PACK_CONV_DGRAD, (Cout, Cin, k, len(ky), len(kx)), None, ky, kx, n=cnt)
+        off += cnt
+    return wd
+
+
 class StageWeights:
     """Everything one stage's kernels read (views into ModelWeights' flat buffers, or the fp32 parameters themselves)."""
     pack_epoch = 0            # bumped by ModelWeights.pack(): derived copies made lazily below are stale afterwards
@@ -109,6 +127,11 @@ class StageGrads:
         self.param_region = self.flat[:self.n_param]
         self.ls_table: Optional[L.DeviceTable] = None
         self.unpack_table: Optional[L.DeviceTable] = None
+        # the bucket views under the header's slot names (GRAD_NAMES below): one record per block in RvtBlockTrain order, one for the
+        # stage; and the backward driver's tables over them.  Filled by ModelWeights._build_grads
+        self.blocks: List[SimpleNamespace] = []
+        self.stage: Optional[SimpleNamespace] = None
+        self.train: Optional[stage_driver.TrainTables] = None
 
     def zero(self, keep_params: bool = False) -> None:
         """Start a backward: the raw products always restart from zero (their fold ADDS them into the parameter
@@ -119,7 +142,28 @@ class StageGrads:
         return self.view[name]
 
 
+# Gradient slot -> reference parameter, or raw product in the aux region of the bucket; names under the block's / the stage's prefix.
+# The slots are the header's: the d_* fields of RvtBlockTrain and RvtStageTrain (include/rvt_hip.h), then what only the host loop of
+# rvt_amd/stage.py accumulates.  Every other parameter gradient is written by a table launch: LAYERSCALE_FOLDS, CONV_UNPACK.
+BLOCK_GRADS = dict(d_n1_w='norm1.weight', d_n1_b='norm1.bias', d_qkv_w='self_attn.qkv.weight', d_qkv_b='self_attn.qkv.bias', d_S1='S1', d_cs1='cs1',
+                   d_n2_w='norm2.weight', d_n2_b='norm2.bias', d_fc1_w='mlp.net.0.0.weight', d_fc1_b='mlp.net.0.0.bias', d_S2='S2', d_cs2='cs2')
+STAGE_GRADS = dict(d_lstm_w='lstm.conv1x1.weight', d_lstm_b='lstm.conv1x1.bias', d_ln_w='downsample_cf2cl.norm.weight',
+                   d_ln_b='downsample_cf2cl.norm.bias', d_raw_conv='raw/conv')
+HOST_LOOP_GRADS = dict(d_dws_w='lstm.conv3x3_dws.weight', d_dws_b='lstm.conv3x3_dws.bias', d_mask_token='mask_token')
+# (raw product S = dy^T x, its column sum cs) of a branch -> (weight, bias, gamma) of the linear under the LayerScale; K / C of that linear
+LAYERSCALE_FOLDS = (('d_S1', 'd_cs1', 'self_attn.proj.weight', 'self_attn.proj.bias', 'ls1.gamma', 1),
+                    ('d_S2', 'd_cs2', 'mlp.net.2.weight', 'mlp.net.2.bias', 'ls2.gamma', 4))
+CONV_UNPACK = ('d_raw_conv', 'downsample_cf2cl.conv.weight')         # tap-major padded product -> the conv weight's own layout
+
+
 class ModelWeights:
+    """The kernel-side weight set of one (compute dtype, parameter storages) signature, and every host table that points into it:
+    the pack table, the gradient buckets with their records and fold tables, the backward driver's RvtBlockTrain arrays and
+    RvtStageTrain templates (StageGrads.train), the stage descriptors (stage_call).  Lifetime rule: a table hangs off the ModelWeights
+    whose arenas and buckets it points into and dies with it - on a signature change, on invalidate_weight_cache(), and on the rebuild
+    when a no-grad weight set is first asked for gradients (RNNDetector.model_weights).  pack() rewrites the arenas in place, so no
+    table is touched per step."""
+
     def __init__(self, mod, p: Dict[str, Tensor], geoms, dtype: torch.dtype, need_grad: bool):
         self.dtype, self.need_grad = dtype, need_grad
         dev = next(iter(p.values())).device
@@ -154,6 +198,7 @@ class ModelWeights:
         self.stages: List[StageWeights] = stages
         tab.upload(dev)
         self.table = tab
+        self._calls: Dict[tuple, stage_driver.StageCall] = {}
         self.grads: List[StageGrads] = []
         if need_grad:
             for si, g in enumerate(geoms):
@@ -177,22 +222,7 @@ class ModelWeights:
         emit(wname, sw.conv_w, PACK_CONV_FWD, (C, Cin, k, cp))
         sw.conv_wd = None
         if need_grad and Cin % 8 == 0:
-            # concatenation over parity classes (py,px) of [Cin][(a,b,cout)] = w[cout,cin,Ky[a],Kx[b]] — the layout
-            # rvt_conv_dgrad walks (rvt_amd/csrc/capi.hip)
-            parts = []
-            total = 0
-            for py in range(stride):
-                for px in range(stride):
-                    ky, kx = conv_dgrad_taps(k, stride, pad, py), conv_dgrad_taps(k, stride, pad, px)
-                    parts.append((ky, kx, Cin * len(ky) * len(kx) * C))
-                    total += parts[-1][2]
-            sw.conv_wd = arT.take(total)
-            off = 0
-            for ky, kx, cnt in parts:
-                if cnt and tab is not None:
-                    _pack_entry(tab, m(wname), sw.conv_wd[off:off + cnt], PACK_CONV_DGRAD, (C, Cin, k, len(ky), len(kx)),
-                                None, ky, kx, n=cnt)
-                off += cnt
+            sw.conv_wd = take_conv_dgrad(tab, arT, m(wname) if tab is not None else None, C, Cin, k, stride, pad)
         # ... and the block-sparse [4 Cin][4 Cout] layout of the one-launch input gradient (rvt_conv_dgrad4; 3x3 / 2 / 1 convs)
         sw.conv_wd4 = None
         if need_grad and k == 3 and stride == 2 and pad == 1 and Cin % 64 == 0 and C % 64 == 0 and dtype_is_bf16:
@@ -252,30 +282,44 @@ class ModelWeights:
         names = [n for n in mod._param_names if n.startswith(pre)]
         shapes = {n: tuple(p[n].shape) for n in names}
         C, k, cp = g.C, g.k, sw.cin_pad
-        aux = [('raw/conv', (C, k * k * cp))]
-        for bi in range(g.num_blocks):
-            for blk in ('att_window', 'att_grid'):
-                bp = f'{pre}att_blocks.{bi}.{blk}.'
-                aux += [(bp + 'S1', (C, C)), (bp + 'cs1', (C,)), (bp + 'S2', (C, 4 * C)), (bp + 'cs2', (C,))]
+        blocks = [f'{pre}att_blocks.{bi}.{blk}.' for bi in range(g.num_blocks) for blk in ('att_window', 'att_grid')]
+        aux = [(pre + STAGE_GRADS['d_raw_conv'], (C, k * k * cp))]
+        for bp in blocks:
+            for S, cs, _, _, _, r in LAYERSCALE_FOLDS:
+                aux += [(bp + BLOCK_GRADS[S], (C, r * C)), (bp + BLOCK_GRADS[cs], (C,))]
         sg = StageGrads(names, shapes, aux, dev)
+
+        def record(table: Dict[str, str], prefix: str) -> SimpleNamespace:
+            return SimpleNamespace(**{slot: sg.view.get(prefix + n) for slot, n in table.items()})      # None: the stage has no such parameter
+        sg.blocks = [record(BLOCK_GRADS, bp) for bp in blocks]
+        sg.stage = record({**STAGE_GRADS, **HOST_LOOP_GRADS}, pre)
+        sg.stage.d_lstm_w = sg.stage.d_lstm_w.view(4 * C, 2 * C)
+        sg.train = stage_driver.TrainTables(sw, sg)
         ls = L.DeviceTable('RvtLayerScaleDesc')
-        for bi in range(g.num_blocks):
-            for wi, blk in enumerate(('att_window', 'att_grid')):
-                bp = f'{pre}att_blocks.{bi}.{blk}.'
-                bw = sw.blocks[bi][wi]
-                for S, cs, Wn, bn, gn, K in ((bp + 'S1', bp + 'cs1', 'self_attn.proj.weight', 'self_attn.proj.bias', 'ls1.gamma', C),
-                                             (bp + 'S2', bp + 'cs2', 'mlp.net.2.weight', 'mlp.net.2.bias', 'ls2.gamma', 4 * C)):
-                    ls.add(C, S=sg.g(S).data_ptr(), cs=sg.g(cs).data_ptr(), W=self.master(bp + Wn).data_ptr(),
-                           b=self.master(bp + bn).data_ptr(), gamma=self.master(bp + gn).data_ptr(),
-                           dW=sg.g(bp + Wn).data_ptr(), db=sg.g(bp + bn).data_ptr(), dgamma=sg.g(bp + gn).data_ptr(), C=C, K=K, pad=0)
+        for bp, gb in zip(blocks, sg.blocks):
+            for S, cs, Wn, bn, gn, r in LAYERSCALE_FOLDS:
+                ls.add(C, S=getattr(gb, S).data_ptr(), cs=getattr(gb, cs).data_ptr(), W=self.master(bp + Wn).data_ptr(),
+                       b=self.master(bp + bn).data_ptr(), gamma=self.master(bp + gn).data_ptr(),
+                       dW=sg.g(bp + Wn).data_ptr(), db=sg.g(bp + bn).data_ptr(), dgamma=sg.g(bp + gn).data_ptr(), C=C, K=r * C, pad=0)
         ls.upload(dev)
         sg.ls_table = ls
         up = pack_table()
-        cw = sg.g(pre + 'downsample_cf2cl.conv.weight')
-        _pack_entry(up, sg.g('raw/conv'), cw, PACK_CONV_WGRAD_ACC, (C, g.Cin, k, cp))
+        _pack_entry(up, getattr(sg.stage, CONV_UNPACK[0]), sg.g(pre + CONV_UNPACK[1]), PACK_CONV_WGRAD_ACC, (C, g.Cin, k, cp))
         up.upload(dev)
         sg.unpack_table = up
         return sg
+
+    # ---- stage descriptors ---------------------------------------------------------------------------------
+    def stage_call(self, si: int, g, inp: Tensor) -> stage_driver.StageCall:
+        """The descriptor of stage si at geometry g for the flavour of `inp` - the loader's uint8 planes (T*B, Cin, h, w) or channels-last
+        frames -, built on first use and kept for this weight set's lifetime: the host loop and both C-side drivers ask here."""
+        u8 = inp.dtype == torch.uint8
+        key = (si, g.H_in, g.W_in, u8) + (tuple(inp.shape[-2:]) if u8 else (0, 0))
+        call = self._calls.get(key)
+        if call is None:
+            call = self._calls[key] = stage_driver.StageCall(self.stages[si], g, self.dtype, *key[3:],
+                                                             train=self.grads[si].train if self.need_grad else None)
+        return call
 
     # ---- per-step work --------------------------------------------------------------------------------------
     def pack(self) -> None:
