@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import ops, tuning
 from .stage import StageGeom, stage_seq_backward, stage_seq_forward
-from .weights import ModelWeights, param_signature, param_versions, round8
+from .weights import ModelWeights, cache_action, param_signature, param_versions, round8
 
 Tensor = torch.Tensor
 LstmState = Optional[Tuple[Tensor, Tensor]]
@@ -127,6 +127,8 @@ class RNNDetectorStage(_Holder):
 
 
 class RNNDetector(nn.Module):
+    _mw_cache: Optional[ModelWeights] = None          # the kernel-side weight set of the last forward (model_weights)
+
     def __init__(self, mdl_config, compute_dtype: torch.dtype = torch.float32):
         super().__init__()
         in_channels = mdl_config.input_channels
@@ -275,18 +277,20 @@ class RNNDetector(nn.Module):
         ``.data`` in inference code; training forwards re-pack every step anyway)."""
         self._mw_cache = None
 
+    def weight_caches(self) -> list:
+        """The weight set the last forward used: a captured graph addresses its buffers and tables by raw pointer and keeps it."""
+        return [self._mw_cache] if self._mw_cache is not None else []
+
     def model_weights(self, params, geoms, dt: torch.dtype, need_grad: bool) -> ModelWeights:
-        sig = (dt, param_signature(params))
-        mw = getattr(self, '_mw_cache', None)
-        fresh = mw is None or mw.sig != sig or (need_grad and not mw.need_grad)
-        if fresh:
-            mw = ModelWeights(self, dict(zip(self._param_names, params)), geoms, dt, need_grad)
-            mw.sig, mw.versions = sig, None
-            self._mw_cache = mw
-        ver = param_versions(params)
-        # training: re-pack every step (optimizers may write through .data, which does not bump _version: one launch);
-        # inference: only when a parameter changed (streaming inference calls forward once per time step)
-        if fresh or need_grad or mw.versions != ver:
+        sig, ver = (dt, param_signature(params)), param_versions(params)
+        mw = self._mw_cache
+        # training: re-pack every step (one launch); inference: only when a parameter changed (streaming inference calls forward once
+        # per time step).  A no-grad weight set has no input-gradient copies and no buckets: asked for gradients, it is rebuilt
+        action = cache_action(mw, sig, ver, need_grad)
+        if action == 'rebuild' or (need_grad and not mw.need_grad):
+            mw = self._mw_cache = ModelWeights(self, dict(zip(self._param_names, params)), geoms, dt, need_grad)
+            mw.sig = sig
+        if action != 'reuse':
             mw.pack()
             mw.versions = ver
         return mw

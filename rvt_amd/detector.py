@@ -50,6 +50,16 @@ class YoloXDetector(nn.Module):
         strides = self.backbone.get_strides(in_stages)
         self.yolox_head = build_yolox_head(head_cfg, in_channels=in_channels, strides=strides, compute_dtype=compute_dtype)
 
+    def invalidate_weight_cache(self) -> None:
+        """Force a rebuild of the kernel-side weight copies of all three parts on their next forward (call after writing parameters or
+        buffers through ``.data`` in inference code)."""
+        for part in (self.backbone, self.fpn, self.yolox_head):
+            part.invalidate_weight_cache()
+
+    def weight_caches(self) -> list:
+        """The kernel-side buffers and tables the last forward used: a captured graph addresses them by raw pointer and keeps them."""
+        return [c for part in (self.backbone, self.fpn, self.yolox_head) for c in part.weight_caches()]
+
     # ---- reference API ------------------------------------------------------------------------------
     def forward_backbone(self, x: Tensor, previous_states: Optional[LstmStates] = None, token_mask: Optional[Tensor] = None) \
             -> Tuple[BackboneFeatures, LstmStates]:

@@ -21,7 +21,6 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib as L
 from . import ops, weights
 
 Tensor = torch.Tensor
@@ -39,25 +38,20 @@ class _BaseConvFn(torch.autograd.Function):
     """y = SiLU(BatchNorm(conv(x))) on a channels-last (N, H, W, Cin) map; every arithmetic step is a HIP kernel."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, w: Tensor, gamma: Tensor, beta: Tensor, mod: 'BaseConv', training: bool, sync: bool):
+    def forward(ctx, x: Tensor, w: Tensor, gamma: Tensor, beta: Tensor, mod: 'BaseConv', pk: Optional['_Packed'], training: bool,
+                sync: bool):
+        """pk: the unit's views in its ConvPack when they fit x (BaseConv.forward decides), else None: packed per call."""
         dt, dev = x.dtype, x.device
         N, H, W, Cin = x.shape
         Cout, k, s, pad = mod.out_channels, mod.ksize, mod.stride, mod.pad
-        pk = mod._pk if mod._pk is not None and mod._pk.dtype == dt and mod._pk.cin == Cin else None
-        if not training and pk is not None and pk.fin is not None and not any(ctx.needs_input_grad[:4]):
-            # inference: BatchNorm (running statistics) + SiLU in the convolution's epilogue — one launch per unit
-            return ops.conv_bn_act_fwd(x, pk.wp, pk.fin[2], pk.fin[3], k, s, pad, BN_ACT_SILU)
         wp = pk.wp if pk is not None else weights.pack_conv_fwd(w.detach(), Cin, dt)      # [Cout][k*k*Cin] tap-major
         y0 = ops.conv_fwd(x, wp, k, s, pad)                                               # network_blocks.py:37-45 (bias=False)
         rows = y0.numel() // Cout
-        f32 = torch.float32
-        st = L.stream_of(y0)
         # [sum x | sum x^2] in fp64  (the pack zeroes its arena once per forward)
         stats = pk.stats if pk is not None and training else torch.zeros(2, Cout, dtype=torch.float64, device=dev)
-        ctx.pk = pk
         count = rows
         if training:
-            L.call('rvt_bn_stats', L.ptr(y0), L.ptr(stats), L.dtype_code(dt), rows, Cout, st)
+            ops.bn_stats(y0, stats)
             if sync:
                 # ONE exchange of [sum x | sum x^2 | rows] (the 2 C + 1 values torch's SyncBatchNorm gathers); the global row count comes
                 # back to the host because the finalize kernel takes it by value (ranks may hold different numbers of labelled frames)
@@ -67,28 +61,22 @@ class _BaseConvFn(torch.autograd.Function):
                 count = int(packed[2 * Cout].item())
             if count == 1:                                                                # (what nn.BatchNorm2d's training forward raises)
                 raise ValueError(f'Expected more than 1 value per channel when training, got input size {[N, Cout, *y0.shape[1:3]]}')
-        fin = torch.empty(4, Cout, dtype=f32, device=dev)                                 # mean, rstd, scale, shift
         bn = mod.bn
-        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        y = torch.empty_like(y0)
         if not bn.track_running_stats or (training and bn.momentum is None):
             # (an eval / no-grad forward never updates the running statistics: momentum is irrelevant there)
             raise NotImplementedError('rvt_amd.fpn.BaseConv: BatchNorm2d with track_running_stats=False, or a training forward with '
                                       'momentum=None (cumulative average), is not built (no shipped config uses either)')
         mom = 0.0 if bn.momentum is None else float(bn.momentum)
-        rm, rv = L.ptr(bn.running_mean), L.ptr(bn.running_var)
         if training:                                                                      # finalize + activation in one launch
-            L.call('rvt_bn_train_act_fwd', L.ptr(y0), L.ptr(stats), count, L.ptr(g32), L.ptr(b32), float(bn.eps), mom,
-                   rm, rv, L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(y), L.dtype_code(dt), rows, Cout,
-                   BN_ACT_SILU, st)
+            fin = torch.empty(4, Cout, dtype=torch.float32, device=dev)                   # mean, rstd, scale, shift
+            y = ops.bn_train_act_fwd(y0, stats, count, *_affine32(gamma, beta), bn.eps, mom, bn.running_mean, bn.running_var, fin, BN_ACT_SILU)
             if bn.track_running_stats and pk is None:                                     # (with a ConvPack: one batched increment per forward)
                 bn.num_batches_tracked += 1
-        else:
-            L.call('rvt_bn_finalize', L.ptr(stats), count, L.ptr(g32), L.ptr(b32), float(bn.eps), mom, rm, rv,
-                   L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), Cout, 0, st)
-            L.call('rvt_bn_act_fwd', L.ptr(y0), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(y), L.dtype_code(dt), rows, Cout, BN_ACT_SILU, st)
+        else:                        # (eval under autograd: statistics, count and momentum go along as they always did, unread)
+            fin = _eval_affine(bn, stats, count, mom)
+            y = ops.bn_act_fwd(y0, fin[2], fin[3], BN_ACT_SILU)
         ctx.save_for_backward(x, w, y0, fin)
-        ctx.mod, ctx.count, ctx.sync, ctx.training = mod, count, sync, training
+        ctx.mod, ctx.pk, ctx.count, ctx.sync, ctx.training = mod, pk, count, sync, training
         return y
 
     @staticmethod
@@ -101,19 +89,15 @@ class _BaseConvFn(torch.autograd.Function):
         Cout, k, s, pad = mod.out_channels, mod.ksize, mod.stride, mod.pad
         rows = y0.numel() // Cout
         dy = dy.contiguous()
-        st = L.stream_of(dy)
         ds = torch.zeros(2, Cout, dtype=torch.float64, device=dev)                        # sum dz (= dbeta), sum dz * xhat (= dgamma)
-        L.call('rvt_bn_act_bwd_stats', L.ptr(dy), L.ptr(y0), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(ds[0]),
-               L.ptr(ds[1]), L.dtype_code(dt), rows, Cout, BN_ACT_SILU, st)
+        ops.bn_act_bwd_stats(dy, y0, fin, ds, BN_ACT_SILU)
         ds_local = ds
         if ctx.sync:                                   # the input gradient needs the GLOBAL sums; dgamma / dbeta stay this rank's share
             ds = ds.clone()                            # (the data-parallel gradient reduction sums / averages them like every other parameter)
             _bn_reduce(ds)
-        dconv = torch.empty_like(y0)
         # (the kernel divides the two sums by its `rows` argument; with synchronised statistics the divisor is the global count)
         dsk = ds if ctx.count == rows else ds * (float(rows) / float(ctx.count))
-        L.call('rvt_bn_act_bwd_apply', L.ptr(dy), L.ptr(y0), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(dsk[0]),
-               L.ptr(dsk[1]), L.ptr(dconv), L.dtype_code(dt), rows, Cout, BN_ACT_SILU, st)
+        dconv = ops.bn_act_bwd_apply(dy, y0, fin, dsk, BN_ACT_SILU)
         dx = None
         if ctx.needs_input_grad[0]:
             wd = ctx.pk.wd if ctx.pk is not None else weights.pack_conv_dgrad(w.detach(), s, pad, dt)
@@ -132,7 +116,7 @@ class _BaseConvFn(torch.autograd.Function):
                 # arena is zeroed / rewritten by the next forward / backward (gradient accumulation, zero_grad(set_to_none=False),
                 # retain_graph): hand autograd a tensor of its own
                 dw = dw.clone()
-        return dx, dw, ds_local[1].to(w.dtype), ds_local[0].to(w.dtype), None, None, None
+        return dx, dw, ds_local[1].to(w.dtype), ds_local[0].to(w.dtype), None, None, None, None
 
 
 class BaseConv(nn.Module):
@@ -150,28 +134,54 @@ class BaseConv(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         """x: channels-last (N, H, W, Cin) in the compute dtype."""
-        pk = self._pk
-        if not self.training and not torch.is_grad_enabled() and pk is not None and pk.fin is not None and pk.dtype == x.dtype \
-                and pk.cin == x.shape[-1]:
-            # inference fast path: one launch, no autograd node
-            return ops.conv_bn_act_fwd(x.contiguous(), pk.wp, pk.fin[2], pk.fin[3], self.ksize, self.stride, self.pad, BN_ACT_SILU)
-        return _BaseConvFn.apply(x.contiguous(), self.conv.weight, self.bn.weight, self.bn.bias, self, self.training, self.training)
+        x = x.contiguous()
+        pk = self._pk if self._pk is not None and self._pk.dtype == x.dtype and self._pk.cin == x.shape[-1] else None
+        if not self.training and pk is not None and pk.fin is not None and not (torch.is_grad_enabled() and any(
+                t.requires_grad for t in (x, self.conv.weight, self.bn.weight, self.bn.bias))):
+            # inference fast path, decided here alone: BatchNorm (running statistics) + SiLU in the convolution's epilogue - one
+            # launch per unit, no autograd node (nothing could ask for a gradient; under no_grad no parameter is even looked up)
+            return ops.conv_bn_act_fwd(x, pk.wp, pk.fin[2], pk.fin[3], self.ksize, self.stride, self.pad, BN_ACT_SILU)
+        return _BaseConvFn.apply(x, self.conv.weight, self.bn.weight, self.bn.bias, self, pk, self.training, self.training)
+
+
+def _affine32(gamma: Tensor, beta: Tensor) -> Tuple[Tensor, Tensor]:
+    return gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+
+
+def _eval_affine(bn: nn.BatchNorm2d, *extras) -> Tensor:
+    """fin[4][C] = mean, rstd, scale, shift of an eval-mode BatchNorm, from its running statistics: one rvt_bn_finalize launch."""
+    fin = torch.empty(4, bn.num_features, dtype=torch.float32, device=bn.weight.device)
+    ops.bn_finalize(*_affine32(bn.weight, bn.bias), bn.eps, bn.running_mean, bn.running_var, fin, *extras)
+    return fin
 
 
 class _Packed:
+    """One unit's views in its ConvPack; fin: the eval-mode affine (None in training), dwp_clean: dwp is zero since the last forward."""
     __slots__ = ('wp', 'wd', 'stats', 'dwp', 'dtype', 'cin', 'fin', 'dwp_clean')
+
+    def __init__(self, wp: Tensor, wd: Tensor, stats: Tensor, dwp: Tensor, dtype: torch.dtype, cin: int):
+        self.wp, self.wd, self.stats, self.dwp, self.dtype, self.cin, self.fin, self.dwp_clean = wp, wd, stats, dwp, dtype, cin, None, False
 
 
 class ConvPack:
     """Kernel-side weight layouts of EVERY BaseConv below a module in two flat buffers, refreshed by ONE rvt_pack_table launch per
-    forward (training) or per parameter change (eval) — the same descriptor-table mechanism as the backbone's ModelWeights
-    (rvt_amd/weights.py): tap-major forward weights, stride-parity input-gradient panels, plus the BatchNorm statistics and raw
-    weight-gradient scratch, instead of ~10 small torch launches per convolution and step."""
+    forward (training) or per parameter change (eval): tap-major forward weights, stride-parity input-gradient panels, plus the
+    BatchNorm statistics and raw weight-gradient scratch, instead of ~10 small torch launches per convolution and step.  Built by the
+    builder of the backbone's ModelWeights (weights.build_arenas) and kept by the same cache rule (weights.cache_action)."""
 
     def __init__(self, root: nn.Module):
         self.convs = [m for m in root.modules() if isinstance(m, BaseConv)]
-        self.sig = None
-        self.versions = None
+        self.invalidate()
+
+    def invalidate(self) -> None:
+        """Rebuild on the next refresh (after a write through .data that no _version shows)."""
+        self.sig = None                                  # (versions and bn_versions are set by the rebuild)
+
+    def buffers(self) -> list:
+        """What a captured graph addresses by raw pointer: the arenas, the table, the eval affine of every unit."""
+        if self.sig is None:
+            return []
+        return [self.bufT, self.buf32, self.table] + [c._pk.fin for c in self.convs if c._pk is not None and c._pk.fin is not None]
 
     def refresh(self, dtype: torch.dtype, training: bool) -> None:
         ps = [c.conv.weight for c in self.convs]
@@ -179,13 +189,13 @@ class ConvPack:
             for c in self.convs:
                 c._pk = None
             return
-        sig = (dtype, tuple((p.data_ptr(), p.device) for p in ps))
-        if sig != self.sig:
+        sig, ver = (dtype, tuple((p.data_ptr(), p.device) for p in ps)), weights.param_versions(ps)
+        action = weights.cache_action(self, sig, ver, training)
+        if action == 'rebuild':
             self._build(dtype, ps[0].device)
-            self.sig, self.versions = sig, None
-        ver = tuple(p._version for p in ps)
-        if training or ver != self.versions:             # (optimizers may write through .data without bumping _version: training re-packs)
-            L.call('rvt_pack_table', L.ptr(self.table.dev), len(self.table), self.table.blocks, L.dtype_code(dtype), L.stream_of(self.bufT))
+            self.sig, self.bn_versions = sig, None       # (fresh views: no unit has its eval affine yet)
+        if action != 'reuse':
+            ops.pack_table(self.table, dtype, self.bufT)
             self.versions = ver
         if training:
             self.buf32.zero_()                           # batch statistics AND raw weight-gradient scratch of every unit: one memset
@@ -197,46 +207,29 @@ class ConvPack:
                 c._pk.dwp_clean = True
         else:                                            # inference: the BatchNorm affine of every unit, once per parameter / buffer change
             bnv = tuple((t.data_ptr(), t._version) for c in self.convs for t in (c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var))
-            if bnv != getattr(self, 'bn_versions', None) or any(c._pk.fin is None for c in self.convs):
+            if bnv != self.bn_versions:
                 for c in self.convs:
-                    bn, Cout = c.bn, c.out_channels
-                    fin = torch.empty(4, Cout, dtype=torch.float32, device=bn.weight.device)
-                    L.call('rvt_bn_finalize', None, 1, L.ptr(bn.weight.detach().float().contiguous()),
-                           L.ptr(bn.bias.detach().float().contiguous()), float(bn.eps), 0.0, L.ptr(bn.running_mean), L.ptr(bn.running_var),
-                           L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), Cout, 0, L.stream_of(fin))
-                    c._pk.fin = fin
+                    c._pk.fin = _eval_affine(c.bn)
                 self.bn_versions = bnv
 
     def _build(self, dtype: torch.dtype, dev) -> None:
-        arT, ar32 = weights._Arena(), weights._Arena()
-        for second in (False, True):
-            if second:
-                arT.buf = torch.empty(max(arT.n, 64), dtype=dtype, device=dev)
-                ar32.buf = torch.zeros(max(ar32.n, 64), dtype=torch.float32, device=dev)
-                n_stats = ar32_stats
-                arT.n = ar32.n = 0
-            tab = weights.pack_table()
-            for c in self.convs:                         # statistics first: one contiguous region to zero per forward
-                st = ar32.take(2, 2 * c.out_channels)         # two fp64 vectors
-                if second:
-                    c._pk = _Packed()
-                    c._pk.stats, c._pk.dtype, c._pk.cin, c._pk.fin, c._pk.dwp_clean = st.view(torch.float64), dtype, c.in_channels, None, False
-            ar32_stats = ar32.n
-            for c in self.convs:
+        def fill(tab, arT, ar32) -> int:
+            stats = [ar32.take(2, 2 * c.out_channels) for c in self.convs]    # two fp64 vectors per unit; first: one contiguous region
+            n_stats = ar32.n
+            for c, st in zip(self.convs, stats):
                 Cout, Cin, k, s, pad = c.out_channels, c.in_channels, c.ksize, c.stride, c.pad
                 w = c.conv.weight.detach()
                 wp = arT.take(Cout, k * k * Cin)
-                if second:
+                if tab is not None:
                     weights._pack_entry(tab, w, wp, weights.PACK_CONV_FWD, (Cout, Cin, k, Cin))
-                wd = weights.take_conv_dgrad(tab if second else None, arT, w, Cout, Cin, k, s, pad)
+                wd = weights.take_conv_dgrad(tab, arT, w, Cout, Cin, k, s, pad)
                 dwp = ar32.take(Cout, k * k * Cin)
-                if second:
-                    c._pk.wp, c._pk.wd, c._pk.dwp = wp, wd, dwp
-        self.bufT, self.buf32 = arT.buf, ar32.buf
-        self.stats_all = ar32.buf[:n_stats]
+                if tab is not None:
+                    c._pk = _Packed(wp, wd, st.view(torch.float64), dwp, dtype, Cin)
+            return n_stats
+        self.bufT, self.buf32, self.table, n_stats = weights.build_arenas(dtype, dev, fill, zero32=True)
+        self.stats_all = self.buf32[:n_stats]
         self.counters = [c.bn.num_batches_tracked for c in self.convs if c.bn.track_running_stats]
-        tab.upload(dev)
-        self.table = tab
 
 
 class Bottleneck(nn.Module):
@@ -312,6 +305,15 @@ class YOLOPAFPN(nn.Module):
         pan_out1 = self.C3_n3(torch.cat([self.bu_conv2(pan_out2), fpn_out1], -1))
         pan_out0 = self.C3_n4(torch.cat([self.bu_conv1(pan_out1), fpn_out0], -1))
         return tuple(t.permute(0, 3, 1, 2) for t in (pan_out2, pan_out1, pan_out0))
+
+    def invalidate_weight_cache(self) -> None:
+        """Force a rebuild of the kernel-side weight copies on the next forward (call after writing parameters or BatchNorm buffers
+        through ``.data`` in inference code; training forwards re-pack every step anyway)."""
+        self._pack.invalidate()
+
+    def weight_caches(self) -> list:
+        """The kernel-side buffers and tables the last forward used: a captured graph addresses them by raw pointer and keeps them."""
+        return self._pack.buffers()
 
 
 def build_yolox_fpn(fpn_cfg, in_channels: Tuple[int, ...], compute_dtype: torch.dtype = torch.float32) -> YOLOPAFPN:

@@ -31,6 +31,9 @@ class GraphedStep:
         # models whose kernel-side weight copies the captured step re-packs: a replay updates the parameters without bumping
         # their version counters on the host, so the next inference forward must not trust its cache
         self.models = tuple(models)
+        for m in self.models:                    # (checked before anything runs: a capture that fails at its first replay is too late)
+            if not all(callable(getattr(m, a, None)) for a in ('invalidate_weight_cache', 'weight_caches')):
+                raise TypeError(f'GraphedStep: a {type(m).__name__} has no invalidate_weight_cache() / weight_caches() (rvt_amd modules do)')
         # SIDE EFFECT: the captured step needs stable gradient addresses, so the models switch to zero-copy gradient hand-off
         # (rvt_amd/backbone.py: .grad = persistent bucket views, torch.autograd.grad sees no backbone gradients); close()
         # restores the flags for later eager use of the same modules
@@ -50,7 +53,7 @@ class GraphedStep:
         # the graph addresses the weight caches the warm-up built (descriptor tables, packed weights, gradient buckets) by raw
         # pointer: they live as long as the graph does.  __call__ drops the MODELS' references after every replay; without these the
         # buffers went back to the allocator and the next tensor allocated between two replays landed on a table the graph reads.
-        self._held = [getattr(m, '_mw_cache', None) for m in self.models]
+        self._held = [m.weight_caches() for m in self.models]
 
     def close(self) -> None:
         """Drop the graph and give the models their gradient hand-off mode back (eager use after a captured phase)."""

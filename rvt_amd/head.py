@@ -26,20 +26,17 @@ from __future__ import annotations
 
 import ctypes
 import math
+from types import SimpleNamespace
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _lib as L
-from . import ops
+from . import _lib as L, ops
 from .fpn import BaseConv, ConvPack
+from .weights import cache_action, param_signature, param_versions, round8
 
 Tensor = torch.Tensor
-
-
-def _pad8(n: int) -> int:
-    return (n + 7) // 8 * 8
 
 
 class _PredFn(torch.autograd.Function):
@@ -177,7 +174,17 @@ class YOLOXHead(nn.Module):
             self.obj_preds.append(nn.Conv2d(hidden, 1, 1, 1, 0))
         self.initialize_biases(prior_prob=0.01)
         self._pack = ConvPack(self)
-        self._pred_cache: Dict[int, tuple] = {}
+        self._pred_cache: Dict[int, SimpleNamespace] = {}      # level -> (sig, versions, out) of the eval-time prediction weights
+
+    def invalidate_weight_cache(self) -> None:
+        """Force a rebuild of the kernel-side weight copies on the next forward (call after writing parameters or BatchNorm buffers
+        through ``.data`` in inference code; training forwards re-pack every step anyway)."""
+        self._pack.invalidate()
+        self._pred_cache.clear()
+
+    def weight_caches(self) -> list:
+        """The kernel-side buffers and tables the last forward used: a captured graph addresses them by raw pointer and keeps them."""
+        return self._pack.buffers() + [t for hit in self._pred_cache.values() for t in hit.out]
 
     def initialize_biases(self, prior_prob: float) -> None:
         """Focal-loss prior on the class and objectness biases (yolo_head.py:155-165)."""
@@ -211,21 +218,21 @@ class YOLOXHead(nn.Module):
         nc, hid = self.num_classes, self.hidden_dim
         ps = (self.reg_preds[k].weight, self.reg_preds[k].bias, self.obj_preds[k].weight, self.obj_preds[k].bias,
               self.cls_preds[k].weight, self.cls_preds[k].bias)
-        key = (like.dtype, like.device, tuple((p.data_ptr(), p._version) for p in ps))
         if cache:
+            sig, ver = (like.dtype, param_signature(ps)), param_versions(ps)
             hit = self._pred_cache.get(k)
-            if hit is not None and hit[0] == key:
-                return hit[1]
-        np_ = _pad8(nc)
+            if cache_action(hit, sig, ver, False) == 'reuse':
+                return hit.out
+        np_ = round8(nc)
         w_ro = torch.cat([ps[0].reshape(4, hid), ps[2].reshape(1, hid), like.new_zeros(3, hid, dtype=ps[0].dtype)])
         b_ro = torch.cat([ps[1], ps[3], like.new_zeros(3, dtype=ps[1].dtype)])
         w_cl = torch.cat([ps[4].reshape(nc, hid), like.new_zeros(np_ - nc, hid, dtype=ps[4].dtype)])
         b_cl = torch.cat([ps[5], like.new_zeros(np_ - nc, dtype=ps[5].dtype)])
-        out = (w_ro, b_ro, w_cl, b_cl)
-        if cache:
-            out = (w_ro.detach().to(like.dtype).contiguous(), b_ro.detach().float().contiguous(),
-                   w_cl.detach().to(like.dtype).contiguous(), b_cl.detach().float().contiguous())
-            self._pred_cache[k] = (key, out)
+        if not cache:
+            return w_ro, b_ro, w_cl, b_cl
+        out = (w_ro.detach().to(like.dtype).contiguous(), b_ro.detach().float().contiguous(),
+               w_cl.detach().to(like.dtype).contiguous(), b_cl.detach().float().contiguous())
+        self._pred_cache[k] = SimpleNamespace(sig=sig, versions=ver, out=out)
         return out
 
     def forward(self, xin: Sequence[Tensor], labels: Optional[Tensor] = None):

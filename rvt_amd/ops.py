@@ -66,6 +66,77 @@ def conv_bn_act_fwd(x: Tensor, w: Tensor, scale: Tensor, shift: Tensor, k: int, 
     return y
 
 
+def _is(t: Tensor, dtype: torch.dtype, *shape: int) -> bool:
+    return t.dtype == dtype and tuple(t.shape) == shape
+
+
+def bn_stats(x: Tensor, stats: Tensor) -> None:
+    """stats[2][C] fp64 (zeroed by the caller) += [column sums of x | column sums of x^2]."""
+    C = x.shape[-1]
+    assert _is(stats, torch.float64, 2, C)
+    L.call('rvt_bn_stats', L.ptr(x), L.ptr(stats), L.dtype_code(x.dtype), x.numel() // C, C, L.stream_of(x))
+
+
+def bn_finalize(gamma: Tensor, beta: Tensor, eps: float, running_mean: Tensor, running_var: Tensor, fin: Tensor,
+                stats: Optional[Tensor] = None, count: int = 1, momentum: float = 0.0) -> None:
+    """Eval-mode BatchNorm: fin[4][C] fp32 = mean, rstd, scale = gamma * rstd, shift = beta - mean * scale from the running
+    statistics.  The eval form proper is the default: no statistics, count 1, momentum 0 (the kernel reads none of them)."""
+    C = fin.shape[1]
+    assert _is(fin, torch.float32, 4, C) and all(_is(v, torch.float32, C) for v in (gamma, beta, running_mean, running_var))
+    assert stats is None or _is(stats, torch.float64, 2, C)
+    L.call('rvt_bn_finalize', L.ptr(stats), count, L.ptr(gamma), L.ptr(beta), float(eps), float(momentum), L.ptr(running_mean),
+           L.ptr(running_var), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), C, 0, L.stream_of(fin))
+
+
+def bn_train_act_fwd(x: Tensor, stats: Tensor, count: int, gamma: Tensor, beta: Tensor, eps: float, momentum: float,
+                     running_mean: Tensor, running_var: Tensor, fin: Tensor, act: int) -> Tensor:
+    """Training-mode BatchNorm from the batch sums `stats` over `count` rows (the global count under synchronised BatchNorm) +
+    activation in one launch; updates the running statistics in place and leaves mean, rstd, scale, shift in fin[4][C]."""
+    C = x.shape[-1]
+    assert _is(fin, torch.float32, 4, C) and all(_is(v, torch.float32, C) for v in (gamma, beta, running_mean, running_var))
+    assert _is(stats, torch.float64, 2, C)
+    y = torch.empty_like(x)
+    L.call('rvt_bn_train_act_fwd', L.ptr(x), L.ptr(stats), count, L.ptr(gamma), L.ptr(beta), float(eps), float(momentum),
+           L.ptr(running_mean), L.ptr(running_var), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(y),
+           L.dtype_code(x.dtype), x.numel() // C, C, act, L.stream_of(x))
+    return y
+
+
+def bn_act_fwd(x: Tensor, scale: Tensor, shift: Tensor, act: int) -> Tensor:
+    """y = act(x * scale + shift), scale / shift fp32 [C]."""
+    C = x.shape[-1]
+    assert _is(scale, torch.float32, C) and _is(shift, torch.float32, C)
+    y = torch.empty_like(x)
+    L.call('rvt_bn_act_fwd', L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(y), L.dtype_code(x.dtype), x.numel() // C, C, act,
+           L.stream_of(x))
+    return y
+
+
+def bn_act_bwd_stats(dy: Tensor, x: Tensor, fin: Tensor, ds: Tensor, act: int) -> None:
+    """ds[2][C] fp64 (zeroed by the caller) += [sum dz (= dbeta) | sum dz * xhat (= dgamma)], dz = dy * act'(x * scale + shift);
+    fin = the forward's mean, rstd, scale, shift."""
+    C = x.shape[-1]
+    assert dy.shape == x.shape and dy.dtype == x.dtype and _is(fin, torch.float32, 4, C) and _is(ds, torch.float64, 2, C)
+    L.call('rvt_bn_act_bwd_stats', L.ptr(dy), L.ptr(x), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(ds[0]),
+           L.ptr(ds[1]), L.dtype_code(x.dtype), x.numel() // C, C, act, L.stream_of(dy))
+
+
+def bn_act_bwd_apply(dy: Tensor, x: Tensor, fin: Tensor, ds: Tensor, act: int) -> Tensor:
+    """dx = scale * (dz - ds[0] / rows - xhat * ds[1] / rows): the training-mode BatchNorm backward behind bn_act_bwd_stats."""
+    C = x.shape[-1]
+    assert dy.shape == x.shape and dy.dtype == x.dtype and _is(fin, torch.float32, 4, C) and _is(ds, torch.float64, 2, C)
+    dx = torch.empty_like(x)
+    L.call('rvt_bn_act_bwd_apply', L.ptr(dy), L.ptr(x), L.ptr(fin[2]), L.ptr(fin[3]), L.ptr(fin[0]), L.ptr(fin[1]), L.ptr(ds[0]),
+           L.ptr(ds[1]), L.ptr(dx), L.dtype_code(x.dtype), x.numel() // C, C, act, L.stream_of(dy))
+    return dx
+
+
+def pack_table(table: L.DeviceTable, dtype: torch.dtype, like: Tensor) -> None:
+    """One rvt_pack_table launch over an uploaded RvtPackDesc table, on the stream of `like`; dtype = the compute dtype of its
+    non-fp32 destinations."""
+    L.call('rvt_pack_table', L.ptr(table.dev), len(table), table.blocks, L.dtype_code(dtype), L.stream_of(like))
+
+
 def stem_supported(src: Tensor, dtype: torch.dtype, Cout: int, k: int, stride: int, pad: int) -> bool:
     """The stem kernels (csrc/stem.hpp) take the loader's uint8 planes; everything else goes prepack + conv + LayerNorm."""
     return bool(L.get_lib().rvt_stem_supported(L.dtype_code(dtype), int(src.dtype == torch.uint8), src.shape[1], Cout, k, stride,

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib as L, stage_driver
+from . import _lib as L, ops, stage_driver
 
 Tensor = torch.Tensor
 
@@ -54,9 +54,9 @@ def _pack_entry(tab: L.DeviceTable, src: Tensor, dst: Tensor, kind: int, d=(), s
 class _Arena:
     """Two-pass bump allocator over one flat tensor: first pass sizes, second pass hands out views."""
 
-    def __init__(self):
+    def __init__(self, buf: Optional[Tensor] = None):
         self.n = 0
-        self.buf: Optional[Tensor] = None
+        self.buf = buf
 
     def take(self, *shape) -> Optional[Tensor]:
         cnt = int(np.prod(shape))
@@ -64,7 +64,35 @@ class _Arena:
         self.n += (cnt + 63) // 64 * 64            # keep every view 128/256-byte aligned
         if self.buf is None:
             return None
+        if off + cnt > self.buf.numel():
+            raise RuntimeError(f'arena of {self.buf.numel()} elements: the view pass takes more than the sizing pass did')
         return self.buf[off:off + cnt].view(*shape)
+
+
+def build_arenas(dtype: torch.dtype, device, fill, zero32: bool = False):
+    """The two-pass build of a packed weight set, for the backbone's ModelWeights and the tail's ConvPack alike.  `fill(tab, arT, ar32)`
+    takes its room from the compute-dtype arena and the fp32 arena and, given a table, adds the pack entries that fill it.  It runs
+    once on unbacked arenas with tab = None (every view is None: sizing), then on arenas backed by fresh buffers with the table.
+    Returns (compute-dtype buffer, fp32 buffer - zeroed on request -, the uploaded table, what the second fill returned)."""
+    sizing = _Arena(), _Arena()
+    fill(None, *sizing)
+    arT = _Arena(torch.empty(max(sizing[0].n, 64), dtype=dtype, device=device))
+    ar32 = _Arena((torch.zeros if zero32 else torch.empty)(max(sizing[1].n, 64), dtype=torch.float32, device=device))
+    tab = pack_table()
+    built = fill(tab, arT, ar32)
+    if (arT.n, ar32.n) != (sizing[0].n, sizing[1].n):
+        raise RuntimeError(f'build_arenas: the view pass took {arT.n} + {ar32.n} elements, the sizing pass {sizing[0].n} + {sizing[1].n}')
+    return arT.buf, ar32.buf, tab.upload(device), built
+
+
+def cache_action(cache, sig, versions, training: bool) -> str:
+    """The weight-cache protocol of every module, decided once.  `cache` (None: nothing built yet) carries the `sig` it was built for
+    - compute dtype, parameter addresses - and the parameter `versions` it last packed.  'rebuild' on a new signature; 're-pack' when
+    training (optimizers may write through .data, which does not bump _version) or when a version moved; else 'reuse'.  What no
+    version shows - a write through .data in inference code - is the caller's to announce: invalidate_weight_cache()."""
+    if cache is None or cache.sig != sig:
+        return 'rebuild'
+    return 're-pack' if training or cache.versions != versions else 'reuse'
 
 
 def take_conv_dgrad(tab: Optional[L.DeviceTable], arena: _Arena, w: Optional[Tensor], Cout: int, Cin: int, k: int, stride: int,
@@ -92,7 +120,6 @@ class StageWeights:
     def scan3_packed(self, bwd: bool) -> Tensor:
         """The ConvLSTM weights in the operand order the wide-stage scan kernels stream (csrc/lstm_scan3.hpp), re-derived from
         `lstm_wn` once per pack() and direction; the buffers persist (stable addresses for hipGraph replay)."""
-        from . import ops
         st = self._scan3
         if st is None:
             st = self._scan3 = dict(fwd=None, bwd=None, fwd_epoch=-1, bwd_epoch=-1)
@@ -169,7 +196,6 @@ class ModelWeights:
         dev = next(iter(p.values())).device
         self.device = dev
         self._refresh: List[Tuple[Tensor, Tensor]] = []          # (fp32 contiguous shadow, parameter) for odd masters
-        self._p = p
         src_cache: Dict[str, Tensor] = {}
 
         def master(name: str) -> Tensor:
@@ -184,25 +210,14 @@ class ModelWeights:
             return src_cache[name]
         self.master = master
 
-        arT, ar32 = _Arena(), _Arena()
-        for second in (False, True):
-            if second:
-                arT.buf = torch.empty(max(arT.n, 64), dtype=dtype, device=dev)
-                ar32.buf = torch.empty(max(ar32.n, 64), dtype=torch.float32, device=dev)
-                arT.n = ar32.n = 0
-            tab = pack_table()
-            stages = []
-            for si, g in enumerate(geoms):
-                stages.append(self._build_stage(tab if second else None, arT, ar32, p, f'stages.{si}.', g, need_grad))
-        self.bufT, self.buf32 = arT.buf, ar32.buf
-        self.stages: List[StageWeights] = stages
-        tab.upload(dev)
-        self.table = tab
+        def fill(tab, arT, ar32) -> List[StageWeights]:
+            return [self._build_stage(tab, arT, ar32, p, f'stages.{si}.', g, need_grad) for si, g in enumerate(geoms)]
+        self.bufT, self.buf32, self.table, self.stages = build_arenas(dtype, dev, fill)
         self._calls: Dict[tuple, stage_driver.StageCall] = {}
         self.grads: List[StageGrads] = []
         if need_grad:
             for si, g in enumerate(geoms):
-                self.grads.append(self._build_grads(mod, p, f'stages.{si}.', g, stages[si], dev))
+                self.grads.append(self._build_grads(mod, p, f'stages.{si}.', g, self.stages[si], dev))
 
     # ---- packed weights ---------------------------------------------------------------------------------
     def _build_stage(self, tab: Optional[L.DeviceTable], arT: _Arena, ar32: _Arena, p, pre: str, g, need_grad: bool) -> StageWeights:
@@ -326,8 +341,7 @@ class ModelWeights:
         """fp32 masters -> kernel-side layouts: one launch (plus a copy per non-fp32 master, normally none)."""
         for shadow, param in self._refresh:
             shadow.copy_(param.detach())
-        L.call('rvt_pack_table', L.ptr(self.table.dev), len(self.table), self.table.blocks, L.dtype_code(self.dtype),
-               L.stream_of(self.bufT))
+        ops.pack_table(self.table, self.dtype, self.bufT)
         for sw in self.stages:
             sw.pack_epoch += 1
 
@@ -335,8 +349,7 @@ class ModelWeights:
         """LayerScale fold + conv weight-gradient unpack of stage si: two launches on the current stream."""
         sg = self.grads[si]
         L.call('rvt_layerscale_grad_table', L.ptr(sg.ls_table.dev), len(sg.ls_table), sg.ls_table.blocks, L.stream_of(sg.flat))
-        L.call('rvt_pack_table', L.ptr(sg.unpack_table.dev), len(sg.unpack_table), sg.unpack_table.blocks, L.RVT_F32,
-               L.stream_of(sg.flat))
+        ops.pack_table(sg.unpack_table, torch.float32, sg.flat)
 
 
 def param_signature(params) -> tuple:

@@ -10,6 +10,10 @@ runs unchanged on any revision that derives its binding from the header; the gol
 The host loop is forced (route_stage_driver = route_stage_driver_train = 0): the C-side drivers issue their launches inside one
 library call, and tests/test_stage_driver.py ties them to the host loop bit for bit.
 
+The detector tail (PAFPN, YOLOX head) has cases of its own, `--suite tail`, in tests/golden/tail_launch_trace.json: the tail's Python
+decides nothing by backend, so one golden, recorded on the emulator, serves the emulator cases and the MI355X ones
+(tests/test_tail_launch_trace.py).
+
 One normalisation: `rb`, the tile factor rvt_lstm_scan3_fwd / _bwd take (absent when the golden was recorded: the library read it
 from the tuning record), is found by its parameter name, taken out of the tuple and returned separately."""
 import argparse
@@ -59,6 +63,8 @@ def canonical(name, args):
     for ty, arg, a in zip(proto.argtypes, proto.argnames, args):
         if name in SCAN3 and arg == 'rb':
             rb = int(a)
+        elif isinstance(a, ctypes.Array):               # a host-side table (the head's level shapes, strides, maps): values, NULL-ness of pointers
+            out.append([int(bool(v)) if a._type_ is ctypes.c_void_p else int(v) for v in a])
         elif ty is ctypes.c_void_p:
             out.append(int(a is not None and int(a) != 0))
         elif ty is ctypes.c_float:
@@ -133,11 +139,85 @@ def trace_hip(key, mode, dev=torch.device('cuda', 0)):
         return out
 
 
+# ---- detector tail: (fixture, dtype) x mode, the same cases on either backend ----
+TAIL_GOLDEN = os.path.join(os.path.dirname(GOLDEN), 'tail_launch_trace.json')
+TAIL_FIXTURES = ('fpn_micro', 'head_micro')
+TAIL_MODES = ('train2',             # training forward + backward twice in a row: arena zeroing and counters once per forward
+              'nograd',             # eval forward under no_grad, twice: build + pack + BatchNorm affines, then plain reuse
+              'eval_grad_frozen',   # eval forward, grad mode on, nothing requires grad: still one launch per unit
+              'eval_grad',          # eval forward, grad mode on, parameters require grad: the unfused eval route
+              'eval_bump')          # eval forward, a conv weight's and a BatchNorm weight's _version bumped, eval forward
+TAIL_HEAD_MODES = ('detect',)       # YOLOXHead.detect_padded
+
+
+def tail_cases():
+    return [(f'tail/{n}/{d}/{m}', n, d, m) for n in TAIL_FIXTURES for d in DTYPES
+            for m in TAIL_MODES + (TAIL_HEAD_MODES if n == 'head_micro' else ())]
+
+
+def trace_tail(name, dt, mode, dev=torch.device('cpu')):
+    """Caller has installed the library of `dev`'s backend."""
+    if name == 'fpn_micro':
+        from tests import casegen_fpn as cg
+        from tests.test_fpn import _build
+        m, _ = _build(name, dev, DTYPES[dt])
+        xs = {s: torch.from_numpy(a).to(dev) for s, a in cg.make_inputs(name).items()}
+        cots = [torch.from_numpy(a).to(dev) for a in cg.make_cotangents(name)]
+
+        def train_step():
+            outs = m({s: x.clone().requires_grad_(True) for s, x in xs.items()})
+            sum((o.float() * ct).sum() for o, ct in zip(outs, cots)).backward()
+        a_conv = m.bu_conv2
+    else:
+        from tests import casegen_head as cg
+        from tests.test_head import _build
+        m, _ = _build(name, dev, DTYPES[dt])
+        xs = [torch.from_numpy(a).to(dev) for a in cg.make_inputs(name)]
+        labels = torch.from_numpy(cg.make_labels(name, cg.CASES[name])).to(dev)
+
+        def train_step():
+            m([x.clone().requires_grad_(True) for x in xs], labels)[1]['loss'].backward()
+        a_conv = m.stems[1]
+
+    def run():
+        if mode == 'train2':
+            m.train()
+            train_step()
+            train_step()
+            return
+        m.eval()
+        if mode == 'nograd':
+            with torch.no_grad():
+                m(xs)
+                m(xs)
+        elif mode == 'eval_grad_frozen':
+            m.requires_grad_(False)
+            m(xs)
+        elif mode == 'eval_grad':
+            m(xs)
+        elif mode == 'eval_bump':
+            with torch.no_grad():
+                m(xs)
+                a_conv.conv.weight.add_(0.0)
+                a_conv.bn.weight.add_(0.0)
+                m(xs)
+        else:
+            m.detect_padded(xs, 0.1, 0.45)
+    out = record(run)
+    if dev.type == 'cuda':
+        torch.cuda.synchronize()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--backend', required=True, choices=['emu', 'hip'])
-    ap.add_argument('--out', default=GOLDEN)
+    ap.add_argument('--suite', default='backbone', choices=['backbone', 'tail'])
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.suite == 'tail':
+        return main_tail(a)
+    a.out = a.out or GOLDEN
     gold = json.load(open(GOLDEN)) if os.path.exists(GOLDEN) else {}
     gold = {k: v for k, v in gold.items() if not k.startswith(a.backend + '/')}
     if a.backend == 'emu':
@@ -156,6 +236,21 @@ def main():
     with open(a.out, 'w') as f:
         json.dump(dict(sorted(gold.items())), f, indent=1)
         f.write('\n')
+
+
+def main_tail(a):
+    """One golden for both backends: written from the emulator by default; `--backend hip` is for comparing (--out elsewhere)."""
+    if a.backend == 'emu':
+        from tests.backends import emu_library
+        _lib._install_test_library(emu_library())
+    tuning.use(**tuning.TEST_GEOMETRY)
+    dev = torch.device('cpu') if a.backend == 'emu' else torch.device('cuda', 0)
+    gold = {}
+    for key, n, d, mode in tail_cases():
+        gold[key] = summary(trace_tail(n, d, mode, dev)[0])
+        print(key, gold[key]['count'], gold[key]['sha256'][:12], flush=True)
+    with open(a.out or TAIL_GOLDEN, 'w') as f:                       # one case per line
+        f.write('{\n' + ',\n'.join(f' {json.dumps(k)}: {json.dumps(v)}' for k, v in sorted(gold.items())) + '\n}\n')
 
 
 if __name__ == '__main__':
