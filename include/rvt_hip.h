@@ -36,6 +36,7 @@
  *       rvt_frames_unpack_augment                      packed frames by index -> flipped / zoomed planes, unpack + augmentation in one launch
  *       rvt_frames_gather                              packed frames by address, from device or pinned host stores, into one packed set
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
+ *       rvt_coco_recall                                the same records -> true positives below maxDets 1 / 10 / 100, the recall table's numerators
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
  *       rvt_optim_step                                 value clip + AdamW + OneCycle schedule of every parameter, one call per step
  *       rvt_grad_stats (+ _ws_bytes) / rvt_optim_step_guarded   per-tensor gradient statistics + a non-finite verdict into a device ring; the step that obeys it
@@ -919,8 +920,8 @@ int rvt_optim_step_guarded(const RvtOptimChunk* chunks, int n_chunks, const RvtO
 
 /* Prophesee / COCO mAP evaluation of detections on the device (rvt_amd/csrc/cocoeval.hpp; host mirror rvt_amd/evaluation.py).
  * Replaces utils/evaluation/prophesee/ (filter_boxes, evaluate_list, coco_eval.py) and the COCOeval core it calls (evaluateImg,
- * accumulate; bbox mode, iscrowd false, maxDets 100): no per-frame copy to the host, no Python loop.  Neither call synchronises
- * with the host; both replay in a hipGraph.
+ * accumulate; bbox mode, iscrowd false, maxDets 100; the recall table also at maxDets 1 and 10): no per-frame copy to the host, no
+ * Python loop.  No call synchronises with the host; all replay in a hipGraph.
  *
  * The match entry: one launch for F frames, one wave per (frame, category).
  *   det [F][max_det][7] fp32 and count [F] int32 exactly as the post-processing entry returns them (x1 y1 x2 y2 obj class_conf
@@ -944,7 +945,18 @@ int rvt_optim_step_guarded(const RvtOptimChunk* chunks, int n_chunks, const RvtO
  *
  * The accumulate entry: perm int64 [n_slots] = the record slots ordered by (key, slot) (a stable sort of rec_key),
  *   rec_thrs double [101] on the device -> precision double [10][101][num_classes][4], COCOeval.accumulate's table at maxDets 100:
- *   -1 where the cell has no non-ignored ground truth.  ws: the ws_bytes query's size (0 = unsupported), contents need not survive. */
+ *   -1 where the cell has no non-ignored ground truth.  ws: the ws_bytes query's size (0 = unsupported), contents need not survive.
+ *
+ * The recall entry: one launch for F frame rows of one stride, one wave per row.
+ *   rec_key / rec_matched / rec_ignored int64 [F][rec_stride] exactly as the match entry leaves them (a store whose match calls
+ *   used different strides takes one call per run of rows of equal stride).  The rank of a record is its slot minus the first
+ *   slot of its category in the row; a record is a true positive at (threshold t, range a) iff bit 4*t + a is set in matched and
+ *   clear in ignored.  tp int64 [3][num_classes][40], ADDED to (zero it to start an evaluation) with integer atomics:
+ *   tp[m][k][4*t + a] += the true positives of category k with rank < 1, 10, 100 for m = 0, 1, 2.  COCOeval.accumulate's
+ *   recall[t][k][a][m] is tp[m][k][4*t + a] / counters[4*k + a] where that count is positive, else -1.  Sums of integers: the
+ *   table does not depend on the grid or on the order in which the waves arrive.
+ *   Supported: 1 <= rec_stride <= 1024, 1 <= num_classes <= 16, F >= 1; anything else returns non-zero with the last error set
+ *   before any launch. */
 int rvt_coco_match(const float* det, const int* count, const float* labels, const int* label_count, const long long* t_us, int F,
                    int max_det, int G, int num_classes, int det_xywh, float min_diag, float min_side, const double* iou_thrs,
                    long long* rec_key, long long* rec_matched, long long* rec_ignored, int rec_stride, int* counters, void* stream);
@@ -952,6 +964,8 @@ size_t rvt_coco_accumulate_ws_bytes(long long n_slots, int num_classes);
 int rvt_coco_accumulate(const long long* perm, const long long* rec_matched, const long long* rec_ignored, long long n_slots,
                         int num_classes, const int* counters, const double* rec_thrs, double* precision, void* ws, size_t ws_bytes,
                         void* stream);
+int rvt_coco_recall(const long long* rec_key, const long long* rec_matched, const long long* rec_ignored, int F, int rec_stride,
+                    int num_classes, long long* tp, void* stream);
 
 #ifdef __cplusplus
 }

@@ -194,6 +194,8 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, 1.0 * F * (max_det * 7 * 4 + 4 + G * 7 * 4 + 4 + 8) + 24.0 * F * a.rec_stride + 80.0, 0.0
     if name == 'rvt_coco_accumulate':                            # permutation + the two mask planes read twice (count, emit); table out
         return 0.0, 2.0 * 24 * a.n_slots + 10 * 101 * a.num_classes * 4 * 8.0, 0.0
+    if name == 'rvt_coco_recall':                                # the three record planes in (a wave's second look at its key row is on chip); table added to
+        return 0.0, 24.0 * a.F * a.rec_stride + 2.0 * 3 * a.num_classes * 40 * 8, 0.0
     # sparse frame cache: no nnz among the arguments, so a launch is priced at what its arrays admit (pack: every byte non-zero up to
     # `capacity`; unpack: the whole values array read).  frames_pack_bytes / frames_unpack_bytes take the measured nnz.
     if name == 'rvt_frames_pack':

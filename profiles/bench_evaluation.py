@@ -4,8 +4,9 @@
      on the same tensors in the same run: the tests' clustered prediction tensors (tests/casegen_postprocess.py) tiled to the batch
      size, conf_thre 0.1, nms_thre 0.45, max_det 256; the labels are the frame's first detections moved by a few pixels.
      Both are timed with device events over --calls calls after a warm-up.
-  2. `evaluate()` (key sort, the accumulate kernels, the one read-back) for a split-sized store: 20 000 and 200 000 frames of
-     synthetic detections (tests/casegen_evaluation.py, 2 000 distinct frames repeated), host clock around the synchronising call.
+  2. `evaluate()` (key sort, the accumulate kernels, the recall kernel, the one read-back) for a split-sized store: 20 000 and 200 000 frames of
+     synthetic detections (tests/casegen_evaluation.py, 2 000 distinct frames repeated), host clock around the synchronising call;
+     beside it `rvt_coco_accumulate` and `rvt_coco_recall` alone on the same stores, event-timed.
   3. The numpy restatement (tests/cocoeval_ref.py) on the same 20 000 frames on this box's host cores, once; its six metrics are
      compared with the device's before anything is reported.
 
@@ -95,6 +96,22 @@ def evaluate_ms(ev, reps=5):
     return statistics.median(ts[1:]), min(ts[1:]), max(ts[1:]), out
 
 
+def kernels_ms(ev, calls):
+    """Event-timed medians of the two table kernels on the store as it stands: rvt_coco_accumulate on a permutation sorted once
+    outside the timing, and the rvt_coco_recall launches of the store's spans (with the zeroing of their table)."""
+    from rvt_amd import _lib as L
+    from rvt_amd.evaluation import N_COUNTERS
+    K, n = ev.num_classes, ev.slots
+    key, matched, ignored = (ev._planes[i, :n] for i in range(3))
+    perm = torch.sort(key, stable=True)[1]
+    ws = torch.empty(max(int(L.get_lib().rvt_coco_accumulate_ws_bytes(n, K)), 1), dtype=torch.uint8, device=key.device)
+    out = torch.empty(10 * 101 * K * 4 + N_COUNTERS, dtype=torch.float64, device=key.device)
+    acc = event_median_ms(lambda: L.call('rvt_coco_accumulate', L.ptr(perm), L.ptr(matched), L.ptr(ignored), n, K, L.ptr(ev._counters),
+                                         L.ptr(ev._thr[10:]), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_of(out)), calls)
+    rec = event_median_ms(ev._recall_tp, calls)
+    return acc, rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--calls', type=int, default=50)
@@ -112,18 +129,24 @@ def main():
     s = STORE
     case = store_case()
     lines += [f'# 2. evaluate() on a store of N frames ({s["base"]} distinct synthetic frames repeated, {s["K"]} classes, max_det {s["max_det"]}): '
-              'median of 5 host-timed calls [min..max], sort + accumulate + read-back',
+              'median of 5 host-timed calls [min..max], sort + accumulate + recall + read-back',
               '#   frames    slots  records | evaluate ms               | AP']
-    first = None
+    first, kernel_lines = None, []
     for n in [int(v) for v in args.frames.split(',')]:
         ev = DetectionEvaluator(s['dataset'], s['ds2'])
         fill(ev, case, n, dev)
         med, lo, hi, out = evaluate_ms(ev)
         lines.append(f'{ev.frames:10d} {ev.slots:8d} {int(ev.counts()["records"].sum()):8d} | {med:8.2f} [{lo:.2f}..{hi:.2f}] | {out["AP"]:.6f}')
         print(lines[-1], flush=True)
+        acc, rec = kernels_ms(ev, args.calls)
+        kernel_lines.append(f'{ev.frames:10d} {ev.slots:8d} | {acc[0]:7.3f} [{acc[1]:.3f}..{acc[2]:.3f}] | {rec[0]:7.3f} [{rec[1]:.3f}..{rec[2]:.3f}] | '
+                            f'AR_100 {ev.summary()["AR_100"]:.6f}')
+        print(kernel_lines[-1], flush=True)
         if first is None:
             first = (ev.frames, out)
         del ev
+    lines += [f'# 2b. the table kernels alone on the same stores: median of {args.calls} event-timed calls [min..max]; evaluate() above runs both',
+              '#   frames    slots | rvt_coco_accumulate ms     | rvt_coco_recall (+ zeroing its table) ms |'] + kernel_lines
     n, dev_out = first
     frames = cge.to_frames(case) * (n // s['base'])
     t0 = time.perf_counter()

@@ -85,4 +85,17 @@ int rvt_coco_accumulate(const long long* perm, const long long* rec_matched, con
     return check_launch("coco_accumulate");
 }
 
+int rvt_coco_recall(const long long* rec_key, const long long* rec_matched, const long long* rec_ignored, int F, int rec_stride,
+                    int num_classes, long long* tp, void* stream) {
+    RVT_CHECK(rec_stride >= 1 && rec_stride <= EVAL_MAX_DET, "coco_recall: rec_stride=%d outside the supported range 1..%d", rec_stride,
+              EVAL_MAX_DET);
+    RVT_CHECK(num_classes >= 1 && num_classes <= EVAL_MAX_NC, "coco_recall: num_classes=%d outside the supported range 1..%d",
+              num_classes, EVAL_MAX_NC);
+    RVT_CHECK(F >= 1, "coco_recall: F=%d frames", F);
+    RVT_CHECK(rec_key && rec_matched && rec_ignored && tp, "coco_recall: null argument");
+    hipLaunchKernelGGL(coco_recall_kernel, dim3((unsigned)imin(F, EVAL_RECALL_GRID)), dim3(64), 0, (hipStream_t)stream, rec_key,
+                       rec_matched, rec_ignored, F, rec_stride, num_classes, (unsigned long long*)tp);
+    return check_launch("coco_recall");
+}
+
 }  // extern "C"

@@ -435,4 +435,85 @@ coco_finish_kernel(int K, const int* __restrict__ counters, const unsigned long 
     }
 }
 
+// ---- recall ----------------------------------------------------------------------------------------------------------------------------------
+// COCOeval's recall cell at maxDets m is tp_total / npig, tp_total = the true positives among the records whose rank inside their
+// own (frame, category) list is below m: it does not depend on the global score order, so it needs neither the sort nor the scan.
+// One wave per frame row (a wave walks the rows blockIdx.x, blockIdx.x + gridDim.x, ...).  Per row: the records per category are
+// counted (LDS integer atomics), an exclusive prefix gives every category's first slot (a row holds its categories one after the
+// other), and rank = slot - first slot.  Lane 4 t + a then owns column (t, a) of the wave's [3][K][40] counters in LDS: rank < 1,
+// < 10, < 100 (each adds to its own and the wider cuts), true positive = matched & ~ignored.  The wave's totals go to the global
+// table with 64-bit INTEGER atomics: sums of integers, the same bits whatever the grid and the arrival order.
+// Every index is a slot below R or a category checked against [0, K): any key bits terminate in bounds.
+__device__ __forceinline__ void eval_atomic_add(unsigned long long* p, unsigned long long v) {
+#ifndef RVT_EMU
+    atomicAdd(p, v);
+#else
+    *p += v;
+#endif
+}
+
+constexpr int EVAL_RECALL_GRID = 1024;   // waves of a launch at most: one flush of 120 K atomics each
+
+__global__ void __launch_bounds__(64)
+coco_recall_kernel(const long long* __restrict__ rkey, const long long* __restrict__ rmatched, const long long* __restrict__ rignored,
+                   int F, int R, int K, unsigned long long* __restrict__ tp) {
+    __shared__ int s_cnt[EVAL_MAX_NC], s_first[EVAL_MAX_NC];
+    __shared__ unsigned s_tp[3][EVAL_MAX_NC][EVAL_LANES];
+    __shared__ unsigned long long s_hit[64];
+    __shared__ int s_cat[64], s_rank[64];
+    const int lane = threadIdx.x;
+    for (int e = lane; e < 3 * EVAL_MAX_NC * EVAL_LANES; e += 64) (&s_tp[0][0][0])[e] = 0u;
+    for (int f = blockIdx.x; f < F; f += gridDim.x) {
+        const size_t base = (size_t)f * R;
+        if (lane < EVAL_MAX_NC) s_cnt[lane] = 0;
+        __syncthreads();
+        for (int i = lane; i < R; i += 64) {
+            const long long key = rkey[base + i], c = key >> 32;
+            if (key != EVAL_NO_RECORD && c >= 0 && c < K) atomicAdd(&s_cnt[(int)c], 1);
+        }
+        __syncthreads();
+        if (lane < EVAL_MAX_NC) {
+            int first = 0;
+            for (int c = 0; c < lane; c++) first += s_cnt[c];
+            s_first[lane] = first;
+        }
+        __syncthreads();
+        for (int i0 = 0; i0 < R; i0 += 64) {
+            const int i = i0 + lane;
+            unsigned long long hit = 0ull;
+            int cat = 0, rank = EVAL_TOP;
+            if (i < R) {
+                const long long key = rkey[base + i], c = key >> 32;
+                if (key != EVAL_NO_RECORD && c >= 0 && c < K) {
+                    cat = (int)c;
+                    rank = i - s_first[cat];
+                    if (rank >= 0 && rank < EVAL_TOP) hit = (unsigned long long)rmatched[base + i] & ~(unsigned long long)rignored[base + i];
+                }
+            }
+            __syncthreads();
+            s_hit[lane] = hit; s_cat[lane] = cat; s_rank[lane] = rank;
+            __syncthreads();
+            const int cnt64 = R - i0 < 64 ? R - i0 : 64;
+            if (lane < EVAL_LANES)
+                for (int q = 0; q < cnt64; q++) {
+                    const unsigned long long h = s_hit[q];
+                    if (h == 0ull) continue;                             // wave-uniform: no true positive in this record
+                    if ((h >> lane) & 1ull) {
+                        const int c = s_cat[q], r = s_rank[q];
+                        s_tp[2][c][lane]++;
+                        if (r < 10) s_tp[1][c][lane]++;
+                        if (r < 1) s_tp[0][c][lane]++;
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    for (int e = lane; e < 3 * K * EVAL_LANES; e += 64) {
+        const int m = e / (K * EVAL_LANES), rest = e - m * K * EVAL_LANES, k = rest / EVAL_LANES, l = rest - k * EVAL_LANES;
+        const unsigned v = s_tp[m][k][l];
+        if (v) eval_atomic_add(tp + e, (unsigned long long)v);
+    }
+}
+
 }  // namespace rvt

@@ -9,15 +9,19 @@ device until the precision table is read back.
   * `DetectionEvaluator(dataset, downsample_by_2, num_classes=None)`: `add_frames(det, count, label_rows, label_count, t_us)`
     is ONE launch per batch of frames with no host synchronisation and appends one compact record per kept detection to device
     storage (padded per frame); `evaluate()` sorts the record keys (`torch.sort`), runs the accumulate kernels and does the ONE
-    read-back of the evaluation, the table and the counters; `precision_table()`, `reset()`, `reserve()`.
+    read-back of the evaluation, the table and the counters; `precision_table()`, `reset()`, `reserve()`.  The same read-back
+    carries the integer table of rvt_coco_recall: `recall_table()` is COCOeval.eval['recall'], `summary()` the twelve numbers of
+    COCOeval.summarize with per-class AP / AP_50 / AR_100.  `merge(other)` appends another evaluator's store (the result has the
+    bits of one evaluator fed both frame lists in order) and `all_gather(group)` makes every rank of a torch.distributed group
+    hold the union of the ranks' stores in rank order, with fixed-size collectives only.
   * `PropheseeEvaluator(dataset, downsample_by_2)`: the reference's surface (LABELS, PREDICTIONS, add_labels, add_predictions,
     reset_buffer, has_data, evaluate_buffer) over the same kernels, fed with the reference's BBOX_DTYPE structured arrays.
 
 Semantics are the reference's, quirks included: the filter also drops detections, a frame that loses every label is not an
 image (its detections are not false positives), the score is class_conf, every metric is 0.0 when no detection survives in any
 image, and an area range or category without ground truth averages out as -1 cells do in COCOeval.summarize.  Metrics are per
-rank, as in the reference.  There is no PyTorch fallback: a missing kernel or an unsupported shape raises with the library's
-message.
+rank, as in the reference, until all_gather() is called.  There is no PyTorch fallback: a missing kernel or an unsupported
+shape raises with the library's message.
 """
 from __future__ import annotations
 
@@ -63,6 +67,21 @@ def summarize(precision: np.ndarray) -> Dict[str, float]:
             'AP_S': mean(precision[:, :, :, 1]), 'AP_M': mean(precision[:, :, :, 2]), 'AP_L': mean(precision[:, :, :, 3])}
 
 
+RECALL_METRICS = ('AR_1', 'AR_10', 'AR_100', 'AR_S', 'AR_M', 'AR_L')
+SUMMARY_KEYS = METRICS + RECALL_METRICS           # COCOeval.summarize's stats[0..11]
+
+
+def _mean_cells(s: np.ndarray) -> float:
+    s = s[s > -1]
+    return float(np.mean(s)) if s.size else -1.0
+
+
+def summarize_recall(recall: np.ndarray) -> Dict[str, float]:
+    """COCOeval.summarize's numbers 7-12 from recall [10][K][4][3]: the mean over the cells > -1, or -1."""
+    return {'AR_1': _mean_cells(recall[:, :, 0, 0]), 'AR_10': _mean_cells(recall[:, :, 0, 1]), 'AR_100': _mean_cells(recall[:, :, 0, 2]),
+            'AR_S': _mean_cells(recall[:, :, 1, 2]), 'AR_M': _mean_cells(recall[:, :, 2, 2]), 'AR_L': _mean_cells(recall[:, :, 3, 2])}
+
+
 class DetectionEvaluator:
     def __init__(self, dataset: str, downsample_by_2: bool, num_classes: Optional[int] = None):
         self.dataset, self.downsample_by_2 = dataset, bool(downsample_by_2)
@@ -78,6 +97,7 @@ class DetectionEvaluator:
         self._counters: Optional[Tensor] = None
         self._thr: Optional[Tensor] = None           # the two threshold tables, double [10 + 101]
         self._last: Optional[Dict[str, Any]] = None
+        self._last_recall: Optional[Dict[str, np.ndarray]] = None    # read back with _last, valid while _last is
 
     # ---- storage ------------------------------------------------------------------------------------------------------------
     def _bind(self, dev: torch.device) -> None:
@@ -171,14 +191,19 @@ class DetectionEvaluator:
         key, matched, ignored = (self._planes[i, :n] for i in range(3))
         perm = torch.sort(key, stable=True)[1]                           # (category, descending score, arrival order)
         ws = torch.empty(max(int(L.get_lib().rvt_coco_accumulate_ws_bytes(n, K)), 1), dtype=torch.uint8, device=self._dev)
-        out = torch.empty(10 * 101 * K * 4 + N_COUNTERS, dtype=torch.float64, device=self._dev)
+        out = torch.empty(10 * 101 * K * 4 + N_COUNTERS + 3 * K * 40, dtype=torch.float64, device=self._dev)
         L.call('rvt_coco_accumulate', L.ptr(perm), L.ptr(matched), L.ptr(ignored), n, K, L.ptr(self._counters),
                L.ptr(self._thr[10:]), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_of(out))
-        out[10 * 101 * K * 4:].copy_(self._counters)
+        out[10 * 101 * K * 4:10 * 101 * K * 4 + N_COUNTERS].copy_(self._counters)
+        out[10 * 101 * K * 4 + N_COUNTERS:].copy_(self._recall_tp().reshape(-1))     # integers far below 2^53: exact as doubles
         host = out.cpu().numpy()                                         # the one read-back
-        c = host[10 * 101 * K * 4:].astype(np.int64)
+        c = host[10 * 101 * K * 4:10 * 101 * K * 4 + N_COUNTERS].astype(np.int64)
+        tp = host[10 * 101 * K * 4 + N_COUNTERS:].astype(np.int64).reshape(3, K, 10, 4)
         self._last = {'precision': host[:10 * 101 * K * 4].reshape(10, 101, K, 4).copy(), 'npig': c[:4 * K].reshape(K, 4),
                       'records': c[64:64 + K], 'images': int(c[80]), 'images_with_detections': int(c[81]), 'truncated_frames': int(c[82])}
+        npig = self._last['npig'][None, :, None, :]                      # [1][K][1][4] against tp [3][K][10][4]
+        recall = np.where(npig > 0, tp / np.maximum(npig, 1), -1.0)      # one double division per cell, as COCOeval's tp_sum[-1] / npig
+        self._last_recall = {'tp': tp, 'recall': np.ascontiguousarray(recall.transpose(2, 1, 3, 0))}
         return self._last
 
     def precision_table(self) -> np.ndarray:
@@ -212,6 +237,123 @@ class DetectionEvaluator:
         out = summarize(r['precision']) if r['images_with_detections'] > 0 else {k: 0.0 for k in METRICS}
         out['truncated_frames'] = r['truncated_frames']
         return out
+
+    # ---- recall and the full summary ----------------------------------------------------------------------------------------
+    def _recall_tp(self) -> Tensor:
+        """int64 [3][num_classes][40] on the device: the true positives with rank < 1, 10, 100 inside their (frame, category)
+        list, one rvt_coco_recall launch per run of add_frames calls with the same slots per frame.  No host synchronisation."""
+        K = self.num_classes
+        tp = torch.zeros(3, K, 40, dtype=torch.int64, device=self._dev)
+        runs: List[List[int]] = []
+        for first, F, R in self._spans:
+            if runs and runs[-1][2] == R and runs[-1][0] + runs[-1][1] * R == first and runs[-1][1] + F <= 0x7fffffff:
+                runs[-1][1] += F
+            else:
+                runs.append([first, F, R])
+        for first, F, R in runs:
+            key, matched, ignored = (self._planes[i, first:first + F * R] for i in range(3))
+            L.call('rvt_coco_recall', L.ptr(key), L.ptr(matched), L.ptr(ignored), F, R, K, L.ptr(tp), L.stream_of(tp))
+        return tp
+
+    def recall_table(self) -> np.ndarray:
+        """COCOeval.eval['recall']: double [10 IoU thresholds][num_classes][4 area ranges][3 maxDets = 1, 10, 100]; -1 where the
+        cell has no non-ignored ground truth, else true positives / npig (one double division)."""
+        self._run()
+        return self._last_recall['recall']
+
+    def recall_counts(self) -> np.ndarray:
+        """The numerators of recall_table(): int64 [3 maxDets][num_classes][10][4], the table rvt_coco_recall filled."""
+        self._run()
+        return self._last_recall['tp']
+
+    def summary(self) -> Dict[str, Any]:
+        """The twelve numbers of COCOeval.summarize in its order (SUMMARY_KEYS), `per_class` (a list of {'AP', 'AP_50', 'AR_100'},
+        one entry per class) and truncated_frames.  Each number is the mean over the cells > -1, or -1; all of them are 0.0 when
+        no detection survives in any image, the rule of evaluate()."""
+        r = self._run()
+        K = self.num_classes
+        if r['images_with_detections'] > 0:
+            p, rc = r['precision'], self._last_recall['recall']
+            out: Dict[str, Any] = dict(summarize(p), **summarize_recall(rc))
+            out['per_class'] = [{'AP': _mean_cells(p[:, :, k, 0]), 'AP_50': _mean_cells(p[0, :, k, 0]), 'AR_100': _mean_cells(rc[:, k, 0, 2])}
+                                for k in range(K)]
+        else:
+            out = {k: 0.0 for k in SUMMARY_KEYS}
+            out['per_class'] = [{'AP': 0.0, 'AP_50': 0.0, 'AR_100': 0.0} for _ in range(K)]
+        out['truncated_frames'] = r['truncated_frames']
+        return out
+
+    # ---- several evaluators, one result ------------------------------------------------------------------------------------
+    def merge(self, other: 'DetectionEvaluator') -> None:
+        """Append `other`'s store to this one: afterwards this evaluator answers as one that was given its own frames and then
+        `other`'s, bit for bit (an exact score tie goes to the earlier arrival: this evaluator's records first).  `other` is left
+        as it is.  Raises ValueError, before anything is touched, unless dataset, downsample_by_2, num_classes and device agree.
+        No host synchronisation beyond what reserve() does."""
+        if not isinstance(other, DetectionEvaluator):
+            raise ValueError(f'merge() takes a DetectionEvaluator, got {type(other).__name__}')
+        if other is self:
+            raise ValueError('merge(): an evaluator cannot be merged into itself')
+        for name in ('dataset', 'downsample_by_2', 'num_classes'):
+            if getattr(self, name) != getattr(other, name):
+                raise ValueError(f'merge(): {name} differs: {getattr(self, name)!r} here, {getattr(other, name)!r} there')
+        if self._dev is not None and other._dev is not None and self._dev != other._dev:
+            raise ValueError(f'merge(): this evaluator holds records on {self._dev}, the other on {other._dev}')
+        if other._dev is None:                                           # never saw a tensor: holds nothing
+            return
+        self._bind(other._dev)
+        n0, n1 = self._n, other._n
+        self.reserve(n0 + n1)
+        self._planes[:, n0:n0 + n1].copy_(other._planes[:, :n1])
+        self._counters += other._counters
+        self._spans += [(n0 + first, F, R) for first, F, R in other._spans]
+        self._n += n1
+        self._frames += other._frames
+        self._last = None
+
+    def all_gather(self, group=None) -> None:
+        """Every rank of `group` ends up holding the union of the ranks' stores in rank order, as if rank 0's evaluator had
+        merged rank 1's, then rank 2's, ...: by the contract of merge() every rank then returns identical results.  Collective:
+        every rank of the group must call it, a rank that holds nothing included.  Fixed-size collectives only: an all_gather of
+        five int64 sizes, all_gathers of the record planes and the span rows padded to the largest rank, an all_reduce of the
+        counters.  Raises ValueError on every rank, before the store is touched, when the ranks' settings differ."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError('all_gather() needs an initialised torch.distributed process group')
+        world = dist.get_world_size(group)
+        if self._dev is None:                                            # this rank never saw a tensor: take the backend's device
+            nccl = 'nccl' in str(dist.get_backend(group))
+            self._bind(torch.device('cuda', torch.cuda.current_device()) if nccl else torch.device('cpu'))
+        dev, n = self._dev, self._n
+        sizes = torch.tensor([n, len(self._spans), self.num_classes, self.min_diag, self.min_side], dtype=torch.int64).to(dev)
+        all_sizes = [torch.empty_like(sizes) for _ in range(world)]
+        dist.all_gather(all_sizes, sizes, group=group)
+        all_sizes = torch.stack(all_sizes).cpu().tolist()
+        for r, s in enumerate(all_sizes):
+            if s[2:] != all_sizes[0][2:]:
+                raise ValueError(f'all_gather(): rank {r} evaluates (num_classes, min_diag, min_side) = {tuple(s[2:])}, '
+                                 f'rank 0 {tuple(all_sizes[0][2:])}')
+        max_n, max_s = max(1, max(s[0] for s in all_sizes)), max(1, max(s[1] for s in all_sizes))
+        planes = torch.zeros(3, max_n, dtype=torch.int64, device=dev)
+        planes[:, :n].copy_(self._planes[:, :n])
+        spans = torch.zeros(max_s, 3, dtype=torch.int64)
+        if self._spans:
+            spans[:len(self._spans)] = torch.tensor(self._spans, dtype=torch.int64)
+        spans = spans.to(dev)
+        all_planes = [torch.empty_like(planes) for _ in range(world)]
+        all_spans = [torch.empty_like(spans) for _ in range(world)]
+        dist.all_gather(all_planes, planes, group=group)
+        dist.all_gather(all_spans, spans, group=group)
+        dist.all_reduce(self._counters, op=dist.ReduceOp.SUM, group=group)
+        span_rows = torch.stack(all_spans).cpu().tolist()
+        store = torch.empty(3, sum(s[0] for s in all_sizes), dtype=torch.int64, device=dev)
+        at, merged, frames = 0, [], 0
+        for r, s in enumerate(all_sizes):
+            store[:, at:at + s[0]].copy_(all_planes[r][:, :s[0]])
+            for first, F, R in span_rows[r][:s[1]]:
+                merged.append((at + first, F, R))
+                frames += F
+            at += s[0]
+        self._planes, self._n, self._spans, self._frames, self._last = store, at, merged, frames, None
 
 
 class PropheseeEvaluator:
