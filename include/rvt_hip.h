@@ -35,6 +35,7 @@
  *       rvt_frames_pack (+ _ws_bytes) / rvt_frames_unpack   byte planes <-> bitmap + non-zero bytes, unpacked by frame index (the compact store)
  *       rvt_frames_unpack_augment                      packed frames by index -> flipped / zoomed planes, unpack + augmentation in one launch
  *       rvt_frames_gather                              packed frames by address, from device or pinned host stores, into one packed set
+ *       rvt_render_preview                             event planes + detection / label boxes -> RGB preview images, one launch
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_coco_recall                                the same records -> true positives below maxDets 1 / 10 / 100, the recall table's numerators
  *       rvt_pack_table                                 all kernel-side weight layouts of a module, one launch per step
@@ -838,6 +839,51 @@ int rvt_frames_unpack_augment(const void* masks, const void* seg_offset, const v
                               const int* table, int B, int C, int H, int W, void* out, void* status, void* stream);
 int rvt_frames_gather(const long long* table, long long n, long long E, void* masks, void* seg_offset, void* value_base, void* values,
                       long long capacity, void* status, int max_blocks, void* stream);
+
+/* Detection previews (rvt_amd/csrc/capi_viz.hip; host mirror rvt_amd/viz.py): event planes and box lists to RGB images, the device
+ * counterpart of the reference's detection visualisation callback (callbacks/viz_base.py:164-174 ev_repr_to_img, callbacks/detection.py:
+ * 52-62, utils/evaluation/prophesee/visualize/vis_utils.py:88-106).  Integer work: bit-exact.  Everything below is defined at the
+ * resolution of the planes (H x W); `scale` s in {1, 2, 4} replicates the finished image: output pixel (Y, X) is base pixel
+ * (Y / s, X / s), Hs = H s, Ws = W s.
+ *
+ * rvt_render_preview: planes [F][C][H][W], uint8 or (planes_signed != 0) int8, C even, 2 <= C <= 512, H, W <= 2^20.
+ *   Base image: d = (sum of channels C/2 .. C-1) - (sum of channels 0 .. C/2-1) in int32; d > 0 -> (255, 255, 255), d < 0 ->
+ *   (0, 0, 0), d == 0 -> (127, 127, 127): the reference's ev_repr_to_img, its reading of the first half as "negative" included.
+ *   Panels: P = 1 or 2, all on the same base image, panel p with its own box list or none (rows NULL): rows fp32 [F][N][7],
+ *   count int32 [F], kind.  RVT_VIZ_KIND_DET: the detection row of the post-processing entry (x1 y1 x2 y2 obj class_conf class):
+ *   x = x1, y = y1, w = x2 - x1, h = y2 - y1 (one rounded fp32 subtraction each), score = class_conf.  RVT_VIZ_KIND_LABEL: the
+ *   label row of the augmentation entry (t x y w h class_id conf).  A frame draws its first n = clamp(count[f], 0, min(N,
+ *   RVT_VIZ_MAX_BOXES)) rows (a label count of -1: none); rows behind RVT_VIZ_MAX_BOXES are not drawn.
+ *   One box: x0 = trunc(x), y0 = trunc(y), x1 = x0 + trunc(w), y1 = y0 + trunc(h), cls = trunc(class), truncation toward zero.
+ *   Skipped when any of x, y, w, h, class is not finite or of magnitude >= 2^20, or w < 0, h < 0 or class < 0.  Outline: the
+ *   pixels inside the image with (x0 <= x <= x1 and y in {y0, y1}) or (y0 <= y <= y1 and x in {x0, x1}), colour
+ *   palette[cls % n_palette] (palette uint8 [n_palette][3], device).
+ *   Tag (flags & RVT_VIZ_TEXT): the text is names[cls % n_names] (names uint8 [n_names][RVT_VIZ_NAME_BYTES], zero-terminated
+ *   ASCII or all 12 bytes; n_names <= 4096), for a detection followed by ' ' and the score as d.dd with the digits of
+ *   q = (int)(score * 100.0f + 0.5f) clamped to [0, 100] (one fp32 multiply, one fp32 add, a truncation; a score that is not
+ *   finite prints 1.00 for +inf and 0.00 otherwise).  A filled rectangle in the box colour, 6 len + 1 wide and 9 high, left edge
+ *   x0, top ty = y0 - 9 when that is >= 0, else y0 + 1, clipped to the image.  Character i sits in the 6 x 8 cell whose top left
+ *   pixel is (x0 + 1 + 6 i, ty + 1): bit 4 - gx of glyphs[ch & 127][gy] lights pixel (gx, gy) of the cell, gx < 5, gy < 7
+ *   (glyphs uint8 [128][RVT_VIZ_GLYPH_ROWS], device).  Glyph pixels are black when r + g + b >= 384, white otherwise.
+ *   Order: painter's, in row order: the base image, then for j = 0 .. n-1 the outline of box j, then its tag.
+ *   out uint8 [Fout][P][Hs][Ws][3]; seen as [Fout][P Hs][Ws][3] it is the reference's prediction-over-label stack.  Image i
+ *   shows frame f = frame_index[i] (int64 [Fout] on the device; NULL: f = i, and Fout <= F), box lists indexed by f.  f == -1
+ *   writes an all-zero image; any other f outside [0, F) writes an all-zero image and ORS RVT_VIZ_STATUS_INDEX into status
+ *   (int32 [1]; nothing else touches it: clear it before the call to read it afterwards).
+ *   One launch for all images and panels: no workspace, no allocation, no host synchronisation, no atomics; replays in a hipGraph
+ *   after planes, rows, counts and frame_index were rewritten in place.  The planes of a frame are read once for all panels; every
+ *   byte of out is written exactly once and none is read; nothing outside out[Fout][P][Hs][Ws][3] is written, at any byte address
+ *   of out.  16-byte loads and stores when W % 16 == 0 and planes and out are 16-byte aligned, byte accesses through the same
+ *   code otherwise.  rows / count / status 4-byte, frame_index 8-byte aligned.  Anything unsupported returns non-zero with the
+ *   last error set before any launch. */
+enum { RVT_VIZ_KIND_DET = 0, RVT_VIZ_KIND_LABEL = 1 };
+enum { RVT_VIZ_TEXT = 1 };               /* flags */
+enum { RVT_VIZ_STATUS_INDEX = 1 };       /* the bit of status */
+enum { RVT_VIZ_MAX_BOXES = 512, RVT_VIZ_NAME_BYTES = 12, RVT_VIZ_GLYPH_ROWS = 7 };
+int rvt_render_preview(const void* planes, int planes_signed, long long F, int C, int H, int W, const float* rows0, const int* count0,
+                       int N0, int kind0, const float* rows1, const int* count1, int N1, int kind1, int P, const long long* frame_index,
+                       long long Fout, const unsigned char* palette, int n_palette, const unsigned char* names, int n_names,
+                       const unsigned char* glyphs, int scale, int flags, void* out, int* status, void* stream);
 
 /* The optimizer step on the device (rvt_amd/csrc/optim.hpp; host mirror rvt_amd/optim.py): gradient clipping by value, AdamW
  * (decoupled weight decay, no amsgrad) and the OneCycle learning-rate schedule of every parameter of every parameter group in one

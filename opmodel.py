@@ -206,6 +206,8 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, frames_unpack_augment_bytes(a.Fout, a.E, a.values_len, a.B), 0.0
     if name == 'rvt_frames_gather':                              # the counts live in the device table: every frame full up to `capacity`
         return 0.0, frames_gather_bytes(a.n, a.E, min(a.capacity, a.n * a.E)), 0.0
+    if name == 'rvt_render_preview':                             # the planes of every rendered frame read once for all panels, the images written once
+        return 0.0, render_preview_bytes(a.Fout, a.C, a.H, a.W, a.P, a.scale), 0.0
     # the optimizer's chunk table: no element count among the arguments, so a launch is priced at what its table admits (every chunk
     # full).  grad_stats_bytes / optim_step_bytes take the real element count.
     if name == 'rvt_grad_stats':
@@ -263,6 +265,12 @@ def frames_gather_bytes(n: int, E: int, nnz: int) -> float:
     seg_offset rows, value_base, values: 8 Gf n + 4 (Sf + 1) n + 8 (n + 1) + nnz) read once and written once, plus the int64 [n][4]
     table.  The reads cross the host link when the stores are pinned host memory; the writes are HBM's."""
     return 2.0 * (n * _frames_meta_bytes(E) + 8 + nnz) + 32.0 * n
+
+
+def render_preview_bytes(Fout: int, C: int, H: int, W: int, P: int, scale: int) -> float:
+    """HBM bytes of one rvt_render_preview: the C byte planes of each of the Fout rendered frames read once, the P panels of
+    (H scale) x (W scale) RGB pixels written once.  (Box rows, counts, the index and the three small tables: not counted.)"""
+    return 1.0 * Fout * C * H * W + 3.0 * Fout * P * H * scale * W * scale
 
 
 def grad_stats_bytes(n_elems: int, n_chunks: int, n_tensors: int) -> float:

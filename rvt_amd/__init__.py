@@ -9,3 +9,5 @@ from . import framecache  # noqa: F401,E402  (sparse frame cache: event tensors 
 from .framecache import FrameGather, PackedFrames, gather_frames, pack_frames, unpack_augment, unpack_frames  # noqa: F401,E402
 from . import loader  # noqa: F401,E402  (epoch loader over the frame cache: sequences, samplers, batches for the step)
 from .loader import BatchLoader, SequenceStore, SparseLabels  # noqa: F401,E402
+from . import viz  # noqa: F401,E402  (detection previews: event frames and boxes to RGB images, one launch)
+from .viz import DetectionPreview, ev_repr_to_img, render_preview  # noqa: F401,E402
