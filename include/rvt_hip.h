@@ -35,6 +35,7 @@
  *       rvt_frames_pack (+ _ws_bytes) / rvt_frames_unpack   byte planes <-> bitmap + non-zero bytes, unpacked by frame index (the compact store)
  *       rvt_frames_unpack_augment                      packed frames by index -> flipped / zoomed planes, unpack + augmentation in one launch
  *       rvt_frames_gather                              packed frames by address, from device or pinned host stores, into one packed set
+ *       rvt_frames_pack2 (+ _ws_bytes) / _unpack2 / _gather2   the same three for format version 2: masks only for non-empty 64-byte groups
  *       rvt_render_preview                             event planes + detection / label boxes -> RGB preview images, one launch
  *       rvt_coco_match / rvt_coco_accumulate (+ _ws_bytes)   detections + labels -> Prophesee / COCO mAP precision table
  *       rvt_coco_recall                                the same records -> true positives below maxDets 1 / 10 / 100, the recall table's numerators
@@ -839,6 +840,57 @@ int rvt_frames_unpack_augment(const void* masks, const void* seg_offset, const v
                               const int* table, int B, int C, int H, int W, void* out, void* status, void* stream);
 int rvt_frames_gather(const long long* table, long long n, long long E, void* masks, void* seg_offset, void* value_base, void* values,
                       long long capacity, void* status, int max_blocks, void* stream);
+
+/* Format, version 2 (rvt_amd/csrc/capi_frames2.hip; host mirror rvt_amd/framecache.py, PackedFrames2): version 1 with a second mask
+ * level.  A mask word is kept only for the groups that hold a non-zero byte, so the fixed cost of a frame falls from 8 Gf bytes to
+ * 16 Sf + 16 and the variable cost is 8 bytes per non-empty group.  Geometry (E, group, Gf, segment, Sf) as in version 1.
+ *   group_mask uint64 [F][Sf]          bit g of segment s is set iff group 64 s + g exists and holds a non-zero byte
+ *   seg_offset uint32 [F][Sf + 1]      as in version 1: exclusive prefix sum of the segments' non-zero byte counts, last entry = the frame's count
+ *   grp_offset uint32 [F][Sf + 1]      exclusive prefix sum of popcount(group_mask[f][s]), last entry = the frame's count of non-empty groups
+ *   value_base int64  [F + 1]          as in version 1
+ *   mask_base  int64  [F + 1]          exclusive prefix sum of the frames' non-empty group counts; mask_base[F] = ngroups
+ *   masks      uint64 [mask_capacity]  version 1's mask of each NON-EMPTY group, frame order then group order, no padding; the bits
+ *                                      behind E are zero; no stored word is zero
+ *   values     uint8  [capacity]       as in version 1
+ *   status     int32  [1]              the version-1 bits; bit 0: nnz > capacity or ngroups > mask_capacity
+ * The mask of group g (segment s, bit j) is masks[mask_base[f] + grp_offset[f][s] + popcount(group_mask[f][s] & ((1 << j) - 1))] when
+ * bit j of group_mask[f][s] is set, and 0 otherwise.
+ * Packed size, status excluded: 16 Sf F + 8 F + 16 (F + 1) + 8 ngroups + nnz bytes.
+ *
+ * rvt_frames_pack2: frames [F][E] -> the seven arrays and status.  Four launches on the stream (group masks + counts, the prefix
+ *   sums per frame, the prefix sums over the frames, compaction of masks and values; three when both capacities are 0), no host
+ *   synchronisation, no allocation; ws: rvt_frames_pack2_ws_bytes(F, E) bytes (0 = F or E out of range), 4-byte aligned, any
+ *   contents.  status is WRITTEN: 1 when nnz > capacity or ngroups > mask_capacity, else 0.  Out of capacity, the five index arrays
+ *   are still complete (value_base[F] and mask_base[F] are the room a retry needs) and exactly the value bytes below `capacity` and
+ *   the mask words below `mask_capacity` are written: nothing behind either, mask words by aligned 8-byte stores, a value run's
+ *   first and last bytes by byte stores (memory next to a run is never read and rewritten).
+ * rvt_frames_unpack2: out [Fout][E] by index, with rvt_frames_unpack's rules: index NULL = frames 0 .. Fout-1, -1 writes a zero
+ *   frame, any other index outside [0, F) writes a zero frame and ORS bit 1 into status.  One launch, no workspace; replays in a
+ *   hipGraph after the packed arrays and the index were rewritten in place.  Reads of masks stay inside [0, masks_len) and reads of
+ *   values inside [0, values_len) whatever the other arrays hold; a segment whose group_mask word is 0 loads no mask and no value.
+ *   out may sit at any byte address and nothing outside out[Fout][E] is written.
+ * rvt_frames_gather2: rvt_frames_gather for version-2 sets: bit for bit the concatenation of the single-frame slices in table order.
+ *   table: int64 [n][8] in DEVICE memory, row f = {address of the frame's Sf group_mask words (8-byte aligned), address of its Sf + 1
+ *   seg_offset entries, address of its Sf + 1 grp_offset entries (4-byte aligned), address of its first compacted mask (8-byte
+ *   aligned; may be 0 when the group count is 0), address of its first value byte (any; may be 0 when the count is 0), its count of
+ *   non-zero bytes, its count of non-empty groups, 0}; device or PINNED host addresses.  value_base and mask_base are made on the
+ *   device.  status is WRITTEN: bit 0 when the value total exceeds capacity or the group total mask_capacity (the five index arrays
+ *   are still complete and exactly the entries below the capacities are written), bit 2 when a row's value count was outside
+ *   [0, E] or its group count outside [0, Gf] (it is taken as 0).  Two launches (the prefix sums, then the copy on at most
+ *   max_blocks workgroups, 0 = the default), no workspace, no allocation, no host synchronisation; replays in a hipGraph after the
+ *   table was rewritten in place.  n = 0 returns 0 and launches nothing.
+ * All three: group_mask / value_base / mask_base / masks / index / table 8-byte, seg_offset / grp_offset / status 4-byte aligned. */
+enum { RVT_FRAMES_GATHER2_COLS = 8 };    /* int64 columns of a row of rvt_frames_gather2's table */
+size_t rvt_frames_pack2_ws_bytes(long long F, long long E);
+int rvt_frames_pack2(const void* frames, long long F, long long E, void* group_mask, void* seg_offset, void* grp_offset, void* value_base,
+                     void* mask_base, void* masks, long long mask_capacity, void* values, long long capacity, void* status, void* ws,
+                     size_t ws_bytes, void* stream);
+int rvt_frames_unpack2(const void* group_mask, const void* seg_offset, const void* grp_offset, const void* value_base,
+                       const void* mask_base, const void* masks, long long masks_len, const void* values, long long values_len,
+                       long long F, long long E, const long long* index, long long Fout, void* out, void* status, void* stream);
+int rvt_frames_gather2(const long long* table, long long n, long long E, void* group_mask, void* seg_offset, void* grp_offset,
+                       void* value_base, void* mask_base, void* masks, long long mask_capacity, void* values, long long capacity,
+                       void* status, int max_blocks, void* stream);
 
 /* Detection previews (rvt_amd/csrc/capi_viz.hip; host mirror rvt_amd/viz.py): event planes and box lists to RGB images, the device
  * counterpart of the reference's detection visualisation callback (callbacks/viz_base.py:164-174 ev_repr_to_img, callbacks/detection.py:

@@ -206,6 +206,14 @@ def _price(name: str, a) -> Optional[Tuple[float, float, float]]:
         return 0.0, frames_unpack_augment_bytes(a.Fout, a.E, a.values_len, a.B), 0.0
     if name == 'rvt_frames_gather':                              # the counts live in the device table: every frame full up to `capacity`
         return 0.0, frames_gather_bytes(a.n, a.E, min(a.capacity, a.n * a.E)), 0.0
+    # format version 2: neither nnz nor ngroups among the arguments, so the same bounds (every byte and every group live up to the
+    # two capacities; unpack: both arrays read whole).  frames_*2_bytes take the measured counts.
+    if name == 'rvt_frames_pack2':
+        return 0.0, frames_pack2_bytes(a.F, a.E, min(a.mask_capacity, a.F * ((a.E + 63) // 64)), min(a.capacity, a.F * a.E)), 0.0
+    if name == 'rvt_frames_unpack2':
+        return 0.0, frames_unpack2_bytes(a.Fout, a.E, a.masks_len, a.values_len), 0.0
+    if name == 'rvt_frames_gather2':
+        return 0.0, frames_gather2_bytes(a.n, a.E, min(a.mask_capacity, a.n * ((a.E + 63) // 64)), min(a.capacity, a.n * a.E)), 0.0
     if name == 'rvt_render_preview':                             # the planes of every rendered frame read once for all panels, the images written once
         return 0.0, render_preview_bytes(a.Fout, a.C, a.H, a.W, a.P, a.scale), 0.0
     # the optimizer's chunk table: no element count among the arguments, so a launch is priced at what its table admits (every chunk
@@ -265,6 +273,33 @@ def frames_gather_bytes(n: int, E: int, nnz: int) -> float:
     seg_offset rows, value_base, values: 8 Gf n + 4 (Sf + 1) n + 8 (n + 1) + nnz) read once and written once, plus the int64 [n][4]
     table.  The reads cross the host link when the stores are pinned host memory; the writes are HBM's."""
     return 2.0 * (n * _frames_meta_bytes(E) + 8 + nnz) + 32.0 * n
+
+
+def _frames2_meta_bytes(E: int) -> int:
+    """group_mask, seg_offset and grp_offset rows plus one value_base and one mask_base entry of one frame of E bytes (format
+    version 2, include/rvt_hip.h): 16 Sf + 8 + 16."""
+    Sf = ((E + 63) // 64 + 63) // 64
+    return 8 * Sf + 2 * 4 * (Sf + 1) + 16
+
+
+def frames_pack2_bytes(F: int, E: int, ngroups: int, nnz: int) -> float:
+    """HBM bytes of one rvt_frames_pack2 when the counts are known: the dense frames read twice (group masks, then compaction: the
+    masks are recomputed, not kept) and the packed set (16 Sf F + 8 F + 16 (F + 1) + 8 ngroups + nnz) written once.  The workspace
+    (8 bytes per segment, written and read) is not counted."""
+    return 2.0 * F * E + F * _frames2_meta_bytes(E) + 16 + 8 * ngroups + nnz
+
+
+def frames_unpack2_bytes(Fout: int, E: int, ngroups: int, nnz: int) -> float:
+    """HBM bytes of one rvt_frames_unpack2 that fetches Fout frames holding ngroups non-empty groups and nnz non-zero bytes between
+    them: their rows, base entries and index entries read, their masks and values read, the dense frames written."""
+    return 1.0 * Fout * E + Fout * (_frames2_meta_bytes(E) + 8) + 8 * ngroups + nnz
+
+
+def frames_gather2_bytes(n: int, E: int, ngroups: int, nnz: int) -> float:
+    """Bytes of one rvt_frames_gather2 that fetches n frames holding ngroups non-empty groups and nnz non-zero bytes between them:
+    their packed bytes read once and written once, plus the int64 [n][8] table.  The reads cross the host link when the stores are
+    pinned host memory; the writes are HBM's."""
+    return 2.0 * (n * _frames2_meta_bytes(E) + 16 + 8 * ngroups + nnz) + 64.0 * n
 
 
 def render_preview_bytes(Fout: int, C: int, H: int, W: int, P: int, scale: int) -> float:

@@ -30,6 +30,9 @@
 //                               two groups when the frame does not start on a line), their prefix count, and rebuilds the line from
 //                               the staged values; whole lines leave as one 16-byte store, the (at most two) lines a segment shares
 //                               with its neighbours by byte stores.  A segment without values reads none and stores zeros.
+// Format version 2 (capi_frames2.hip: a mask only for the non-empty groups) is these kernels with a second mask level; it calls the
+// pieces below (fc_line_load / fc_line_store, the scans, fc_compact_lines, fc_unpack_parked).  The kernels are static: two parts of
+// the library include this file.
 // A frame of a pack's input that does not start on a 16-byte boundary (E % 16 != 0) is read byte by byte; every shape the package
 // builds (20 x 360 x 640, 20 x 240 x 304, 10 x 240 x 304) is a multiple of 16.
 #pragma once
@@ -151,7 +154,7 @@ __device__ __forceinline__ int fc_park_segment(const unsigned long long* __restr
 }
 
 // -------------------------------------------------------------------------------------------------- pack, launch 1: masks + counts
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_mask_kernel(const unsigned char* __restrict__ frames, long long F, long long E, long long Gf, long long Sf,
                    unsigned long long* __restrict__ masks, unsigned* __restrict__ seg_count) {
     __shared__ __attribute__((aligned(16))) unsigned short bits[FC_WAVES][256];
@@ -178,7 +181,7 @@ frames_mask_kernel(const unsigned char* __restrict__ frames, long long F, long l
 
 // ------------------------------------------------------------------------------------------ pack, launch 2: seg_offset of each frame
 // grid F: seg_offset[f][0..Sf] = exclusive scan of seg_count[f][0..Sf), frame_count[f] = the total
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_seg_scan_kernel(const unsigned* __restrict__ seg_count, long long Sf, unsigned* __restrict__ seg_offset,
                        unsigned* __restrict__ frame_count) {
     __shared__ int part[2][FC_WAVES];
@@ -199,7 +202,7 @@ frames_seg_scan_kernel(const unsigned* __restrict__ seg_count, long long Sf, uns
 
 // --------------------------------------------------------------------------------------------- pack, launch 3: value_base and status
 // one workgroup: value_base[0..F] = exclusive scan of frame_count[0..F); status = nnz > capacity
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_base_scan_kernel(const unsigned* __restrict__ frame_count, long long F, long long capacity, long long* __restrict__ value_base,
                         int* __restrict__ status) {
     __shared__ long long part[2][FC_WAVES];
@@ -216,8 +219,85 @@ frames_base_scan_kernel(const unsigned* __restrict__ frame_count, long long F, l
     }
 }
 
+// The non-zero bytes of a segment held as four lines per lane, lane-consecutive (v, and m = fc_nonzero16 of each), to the n_fit
+// bytes behind dst, through the wave's LDS image img (FC_SEG + 16 bytes): the image starts at the run's own alignment within a
+// 16-byte line, whole lines leave as aligned 16-byte stores and the run's edges by byte stores.  Every lane of the wave calls it.
+__device__ __forceinline__ void fc_compact_lines(const u32x4 (&v)[4], const unsigned (&m)[4], unsigned char* __restrict__ dst, int n_fit,
+                                                 unsigned char* img, int lane) {
+    // where each line's bytes go: byte order is (j, lane), so four exclusive scans over the lanes, two 16-bit counts per scan
+    // (a wave's sum of one j is at most 1024: the low half never carries into the high one)
+    const int p0 = __builtin_popcount(m[0]) | (__builtin_popcount(m[1]) << 16);
+    const int p1 = __builtin_popcount(m[2]) | (__builtin_popcount(m[3]) << 16);
+    const int i0 = fc_wave_scan(p0, lane), i1 = fc_wave_scan(p1, lane);
+    const int t0 = __shfl(i0, 63), t1 = __shfl(i1, 63);
+    const int e0 = i0 - p0, e1 = i1 - p1;
+    int pos[4];
+    pos[0] = e0 & 0xffff;
+    pos[1] = (t0 & 0xffff) + (e0 >> 16);
+    pos[2] = (t0 & 0xffff) + (t0 >> 16) + (e1 & 0xffff);
+    pos[3] = (t0 & 0xffff) + (t0 >> 16) + (t1 & 0xffff) + (e1 >> 16);
+
+    const int a = (int)((uintptr_t)dst & 15);                   // the image starts where the run starts within its line
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        int q = a + pos[j];
+        unsigned mm = m[j];
+        while (mm) {
+            const int k = __builtin_ctz(mm);
+            mm &= mm - 1;
+            img[q++] = (unsigned char)fc_byte_of(v[j], k);
+        }
+    }
+    wave_rendezvous();
+    unsigned char* line0 = dst - a;
+    const int end = a + n_fit, nlines = (end + 15) >> 4;
+    for (int L = lane; L < nlines; L += 64) fc_line_store(line0, 16 * L, a, end, *reinterpret_cast<const u32x4*>(img + 16 * L));
+}
+
+// Decode of a parked segment (fc_park_segment's 64 masks and prefix counts at mg[1..64] / pg[1..64], a zero group on either side,
+// pg[65] = total): the run of `total` values of segment s of packed frame idx staged through img (FC_SEG + 32 bytes of LDS) by
+// aligned lines, reads clamped to [0, values_len), then the len bytes at o rebuilt line by line of the OUTPUT address: whole
+// lines by one 16-byte store, the segment's edges by byte stores.  total == 0: nothing is read (idx may name no frame) and zeros
+// are stored.  Every lane of the wave calls it.
+__device__ __forceinline__ void fc_unpack_parked(int total, const long long* __restrict__ value_base, const unsigned* __restrict__ seg_offset,
+                                                 long long idx, long long Sf, long long s, const unsigned char* __restrict__ values,
+                                                 long long values_len, unsigned char* img, const unsigned long long* mg, const int* pg,
+                                                 unsigned char* __restrict__ o, int len, int lane) {
+    int av = 0;
+    if (total > 0) {                                            // (the same in every lane)
+        const long long start = value_base[idx] + (long long)seg_offset[idx * (Sf + 1) + s];
+        av = (int)(((uintptr_t)values + (uintptr_t)start) & 15);
+        const long long first = start - av;                     // index into values of the image's byte 0
+        const int nl = (av + total + 15) >> 4;
+        for (int L = lane; L < nl; L += 64)                     // (lines of the ADDRESS values + first; the array is the run [0, values_len))
+            *reinterpret_cast<u32x4*>(img + 16 * L) = fc_line_load(values, first + 16 * L, 0LL, values_len);
+    }
+    wave_rendezvous();
+
+    const int a = (int)((uintptr_t)o & 15);
+    unsigned char* line0 = o - a;
+    const int nlines = (a + len + 15) >> 4;
+    for (int L = lane; L < nlines; L += 64) {
+        const int r0 = 16 * L - a;                              // segment byte under the line's byte 0 (negative: the neighbour's)
+        const int bit = r0 + 64, gi = bit >> 6, bo = bit & 63;
+        const unsigned long long lo = mg[gi], hi = mg[gi + 1];
+        unsigned mm = (unsigned)((bo ? (lo >> bo) | (hi << (64 - bo)) : lo) & 0xffffULL);
+        int off = av + pg[gi] + __builtin_popcountll(lo & ((1ULL << bo) - 1));
+        unsigned q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+        while (mm) {
+            const int k = __builtin_ctz(mm);
+            mm &= mm - 1;
+            const unsigned b = (unsigned)img[off++] << (8 * (k & 3));
+            const int wd = k >> 2;
+            q0 |= wd == 0 ? b : 0u; q1 |= wd == 1 ? b : 0u; q2 |= wd == 2 ? b : 0u; q3 |= wd == 3 ? b : 0u;
+        }
+        const u32x4 q = {q0, q1, q2, q3};
+        fc_line_store(line0, 16 * L, a, a + len, q);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ pack, launch 4: value compaction
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_compact_kernel(const unsigned char* __restrict__ frames, long long F, long long E, long long Sf,
                       const unsigned* __restrict__ seg_offset, const long long* __restrict__ value_base,
                       unsigned char* __restrict__ values, long long capacity) {
@@ -241,40 +321,11 @@ frames_compact_kernel(const unsigned char* __restrict__ frames, long long F, lon
         v[j] = fc_line_load(frame, (unsigned long long)(s * FC_SEG + j * 1024 + lane * 16), 0ULL, (unsigned long long)E, aligned);
         m[j] = fc_nonzero16(v[j]);
     }
-    // where each line's bytes go: byte order is (j, lane), so four exclusive scans over the lanes, two 16-bit counts per scan
-    // (a wave's sum of one j is at most 1024: the low half never carries into the high one)
-    const int p0 = __builtin_popcount(m[0]) | (__builtin_popcount(m[1]) << 16);
-    const int p1 = __builtin_popcount(m[2]) | (__builtin_popcount(m[3]) << 16);
-    const int i0 = fc_wave_scan(p0, lane), i1 = fc_wave_scan(p1, lane);
-    const int t0 = __shfl(i0, 63), t1 = __shfl(i1, 63);
-    const int e0 = i0 - p0, e1 = i1 - p1;
-    int pos[4];
-    pos[0] = e0 & 0xffff;
-    pos[1] = (t0 & 0xffff) + (e0 >> 16);
-    pos[2] = (t0 & 0xffff) + (t0 >> 16) + (e1 & 0xffff);
-    pos[3] = (t0 & 0xffff) + (t0 >> 16) + (t1 & 0xffff) + (e1 >> 16);
-
-    unsigned char* dst = values + start;
-    const int a = (int)((uintptr_t)dst & 15);                   // the image starts where the run starts within its line
-    unsigned char* img = stage[wave];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        int q = a + pos[j];
-        unsigned mm = m[j];
-        while (mm) {
-            const int k = __builtin_ctz(mm);
-            mm &= mm - 1;
-            img[q++] = (unsigned char)fc_byte_of(v[j], k);
-        }
-    }
-    wave_rendezvous();
-    unsigned char* line0 = dst - a;
-    const int end = a + n_fit, nlines = (end + 15) >> 4;
-    for (int L = lane; L < nlines; L += 64) fc_line_store(line0, 16 * L, a, end, *reinterpret_cast<const u32x4*>(img + 16 * L));
+    fc_compact_lines(v, m, values + start, n_fit, stage[wave], lane);
 }
 
 // -------------------------------------------------------------------------------------------------------------------------- unpack
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_unpack_kernel(const unsigned long long* __restrict__ masks, const unsigned* __restrict__ seg_offset,
                      const long long* __restrict__ value_base, const unsigned char* __restrict__ values, long long values_len,
                      long long F, long long E, long long Gf, long long Sf, const long long* __restrict__ index, long long Fout,
@@ -299,39 +350,8 @@ frames_unpack_kernel(const unsigned long long* __restrict__ masks, const unsigne
         mgrp[wave][65] = 0; pgrp[wave][65] = total;
     }
 
-    unsigned char* img = vstage[wave];
-    int av = 0;
-    if (total > 0) {                                            // (the same in every lane)
-        const long long start = value_base[idx] + (long long)seg_offset[idx * (Sf + 1) + s];
-        av = (int)(((uintptr_t)values + (uintptr_t)start) & 15);
-        const long long first = start - av;                     // index into values of the image's byte 0
-        const int nl = (av + total + 15) >> 4;
-        for (int L = lane; L < nl; L += 64)                     // (lines of the ADDRESS values + first; the array is the run [0, values_len))
-            *reinterpret_cast<u32x4*>(img + 16 * L) = fc_line_load(values, first + 16 * L, 0LL, values_len);
-    }
-    wave_rendezvous();
-
-    unsigned char* o = out + fo * E + s * FC_SEG;
-    const int a = (int)((uintptr_t)o & 15);
-    unsigned char* line0 = o - a;
-    const int nlines = (a + len + 15) >> 4;
-    for (int L = lane; L < nlines; L += 64) {
-        const int r0 = 16 * L - a;                              // segment byte under the line's byte 0 (negative: the neighbour's)
-        const int bit = r0 + 64, gi = bit >> 6, bo = bit & 63;
-        const unsigned long long lo = mgrp[wave][gi], hi = mgrp[wave][gi + 1];
-        unsigned mm = (unsigned)((bo ? (lo >> bo) | (hi << (64 - bo)) : lo) & 0xffffULL);
-        int off = av + pgrp[wave][gi] + __builtin_popcountll(lo & ((1ULL << bo) - 1));
-        unsigned q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-        while (mm) {
-            const int k = __builtin_ctz(mm);
-            mm &= mm - 1;
-            const unsigned b = (unsigned)img[off++] << (8 * (k & 3));
-            const int wd = k >> 2;
-            q0 |= wd == 0 ? b : 0u; q1 |= wd == 1 ? b : 0u; q2 |= wd == 2 ? b : 0u; q3 |= wd == 3 ? b : 0u;
-        }
-        const u32x4 q = {q0, q1, q2, q3};
-        fc_line_store(line0, 16 * L, a, a + len, q);
-    }
+    fc_unpack_parked(total, value_base, seg_offset, idx, Sf, s, values, values_len, vstage[wave], mgrp[wave], pgrp[wave],
+                     out + fo * E + s * FC_SEG, len, lane);
 }
 
 }  // namespace rvt

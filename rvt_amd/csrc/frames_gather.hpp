@@ -30,7 +30,7 @@ constexpr int GA_COLS = RVT_FRAMES_GATHER_COLS;                // int64 columns 
 constexpr int GA_DEFAULT_BLOCKS = 64;
 
 // --------------------------------------------------------------------------------------------- launch 1: value_base and status
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_gather_scan_kernel(const long long* __restrict__ table, long long n, long long E, long long capacity,
                           long long* __restrict__ value_base, int* __restrict__ status) {
     __shared__ long long part[2][FC_WAVES];
@@ -120,7 +120,7 @@ __device__ __forceinline__ void ga_copy_bytes(const unsigned char* __restrict__ 
     }
 }
 
-__global__ void __launch_bounds__(FC_THREADS)
+static __global__ void __launch_bounds__(FC_THREADS)
 frames_gather_copy_kernel(const long long* __restrict__ table, long long n, long long E, long long Gf, long long Sf,
                           unsigned long long* __restrict__ masks, unsigned* __restrict__ seg_offset,
                           const long long* __restrict__ value_base, unsigned char* __restrict__ values, long long capacity) {

@@ -30,7 +30,7 @@ import torch
 
 from . import augment as A
 from . import framecache as fc
-from .framecache import PackedFrames
+from .framecache import PackedFrames, PackedFrames2
 from .types import DataType, DatasetSamplingMode, Mode
 
 TOO_FEW_STREAMS_MSG = ("Each worker must at least get 'batch_size' number of datapipes. Otherwise, we would have to support dynamic "
@@ -143,7 +143,7 @@ def _validate_labels(N: int, o2r: np.ndarray, rows: np.ndarray, row_offset: np.n
 
 
 class SequenceStore:
-    """One recording's built windows: `frames` (host PackedFrames of N windows), `objframe_idx_2_repr_idx` (int64, increasing: the
+    """One recording's built windows: `frames` (host PackedFrames or PackedFrames2 of N windows), `objframe_idx_2_repr_idx` (int64, increasing: the
     window each labelled frame ends) and the labelled frames' fp32 [n][7] rows (t x y w h class_id class_confidence)."""
 
     def __init__(self, frames: PackedFrames, objframe_idx_2_repr_idx: np.ndarray, rows_per_frame: Sequence[np.ndarray]):
@@ -280,17 +280,22 @@ class _Staging:
     """Host residency: a packed set of T * B frames on the device, sized for the densest frames of the stores, and what fills it:
     staging='copy' a pinned twin of the set, staging='gather' a pinned int64 [T * B][4] table and its device twin."""
 
-    def __init__(self, n_frames, frame_shape, dtype, cap, dev, pin, gather=False):
-        self.dev = PackedFrames.empty(frame_shape, dtype, n_frames, max(cap, 1), dev, zero=True)
+    def __init__(self, n_frames, frame_shape, dtype, cap, dev, pin, gather=False, version=1, mask_cap=0):
+        def make(device, **kw):                                  # (format version 2: room for mask_cap mask words as well)
+            if version == 2:
+                return PackedFrames2.empty(frame_shape, dtype, n_frames, max(cap, 1), max(mask_cap, 1), device, zero=True, **kw)
+            return PackedFrames.empty(frame_shape, dtype, n_frames, max(cap, 1), device, zero=True, **kw)
+        self.dev = make(dev)
         self.host = self.table_host = self.table_dev = None
         if gather:
-            self.table_host = torch.zeros(n_frames * fc.GATHER_COLS, dtype=torch.int64)
+            cols = fc.GATHER2_COLS if version == 2 else fc.GATHER_COLS
+            self.table_host = torch.zeros(n_frames * cols, dtype=torch.int64)
             if pin:
                 self.table_host = self.table_host.pin_memory()
-            self.table_rows = self.table_host.numpy().reshape(n_frames, fc.GATHER_COLS)        # the same memory, for numpy to fill
-            self.table_dev = torch.zeros(n_frames * fc.GATHER_COLS, dtype=torch.int64, device=dev)
+            self.table_rows = self.table_host.numpy().reshape(n_frames, cols)                  # the same memory, for numpy to fill
+            self.table_dev = torch.zeros(n_frames * cols, dtype=torch.int64, device=dev)
         else:
-            self.host = PackedFrames.empty(frame_shape, dtype, n_frames, max(cap, 1), 'cpu', pin=pin, zero=True)
+            self.host = make('cpu', pin=pin)
         self.ready = torch.cuda.Event() if dev.type == 'cuda' else None
 
 
@@ -302,7 +307,9 @@ class BatchLoader:
     None = 'gather', the measured faster one; the batches are the same bit for bit.
     fused: None / False = unpack_frames + augment_planes (the measured faster route),
     True = unpack_augment (one launch, no dense intermediate).  seed: the epoch's random order comes from seed + epoch (the same on
-    every rank); the streams' permutations and the augmentation draws use torch's global generator, seeded likewise when given."""
+    every rank); the streams' permutations and the augmentation draws use torch's global generator, seeded likewise when given.
+    The stores' frames are PackedFrames or PackedFrames2 (format version 2), all of one version; version-2 stores take every route
+    but fused=True, and give the batches of the converted version-1 stores bit for bit."""
 
     def __init__(self, stores: Sequence[SequenceStore], batch_size: int, sequence_length: int, mode: DatasetSamplingMode,
                  dataset_mode: Mode, augm_config: Any = None, dataset_hw: Optional[Tuple[int, int]] = None, device=None,
@@ -336,9 +343,15 @@ class BatchLoader:
         # the one-launch kernel takes 1.96 ms against 1.49 ms); fused=True trades that for one (T, B, C, H, W) buffer less
         self.fused = False if fused is None else bool(fused)
         f0 = self.stores[0].frames
+        self.version = 2 if isinstance(f0, PackedFrames2) else 1          # format version of the packed stores: all of one
         for s in self.stores:
             if s.frames.frame_shape != f0.frame_shape or s.frames.dtype != f0.dtype:
                 raise ValueError(f'stores hold {s.frames.dtype} frames {s.frames.frame_shape} and {f0.dtype} frames {f0.frame_shape}')
+            if isinstance(s.frames, PackedFrames2) != (self.version == 2):
+                raise ValueError('stores hold packed frames of format versions 1 and 2: framecache.convert() them to one version')
+        if self.fused and self.version == 2:
+            raise ValueError('fused=True (unpack_augment) reads format version 1 only: version-2 stores take the two-launch route '
+                             '(fused=None / False), or framecache.convert(frames, 1) them')
         if len(f0.frame_shape) != 3:
             raise ValueError(f'frames must be (C, H, W) planes, got {f0.frame_shape}')
         self.frame_shape, self.dtype = tuple(f0.frame_shape), f0.dtype
@@ -397,13 +410,15 @@ class BatchLoader:
                 for s in self.stores:
                     s.frames = s.frames.pin_memory()
             cap = max(int(np.diff(s.frames.value_base.numpy()).max()) for s in self.stores)
+            # (format version 2: the staging sets also hold the masks of the frames' non-empty groups, sized likewise)
+            mcap = max(int(np.diff(s.frames.mask_base.numpy()).max()) for s in self.stores) if self.version == 2 else 0
             self.side = torch.cuda.Stream(device=dev) if pin else None
             gather = self.staging == 'gather'
             self.gatherer = fc.FrameGather([s.frames for s in self.stores], dev) if gather else None
             self.gather_blocks = 0                               # 0 = the library's default grid cap
             for p in self.parts.values():
                 n = self.T * p['B']
-                p['staging'] = [_Staging(n, self.frame_shape, self.dtype, n * cap, dev, pin, gather) for _ in range(2)]
+                p['staging'] = [_Staging(n, self.frame_shape, self.dtype, n * cap, dev, pin, gather, self.version, n * mcap) for _ in range(2)]
 
     # ---- orders ----
     def _generator(self) -> Optional[torch.Generator]:
@@ -512,17 +527,22 @@ class BatchLoader:
             runs.append(self.stores[k].frames.slice(int(need[at] - self.base[k]), int(need[end - 1] - self.base[k]) + 1))
             at = end
         h = st.host
+        # the arrays with a row per frame, those with an entry per frame and one more, and the variable-length runs
+        per_frame, bases, run_arrays = ((('group_mask', 'seg_offset', 'grp_offset'), ('value_base', 'mask_base'), ('masks', 'values'))
+                                        if self.version == 2 else (('masks', 'seg_offset'), ('value_base',), ('values',)))
         if runs:
             g = fc.concat(runs)
-            n, nv = g.num_frames, g.values.numel()
-            h.masks[:n].copy_(g.masks)
-            h.seg_offset[:n].copy_(g.seg_offset)
-            h.value_base[:n + 1].copy_(g.value_base)
-            h.values[:nv].copy_(g.values)
+            n = g.num_frames
+            for k in per_frame:
+                getattr(h, k)[:n].copy_(getattr(g, k))
+            for k in bases:
+                getattr(h, k)[:n + 1].copy_(getattr(g, k))
+            for k in run_arrays:
+                getattr(h, k)[:getattr(g, k).numel()].copy_(getattr(g, k))
 
         def fill(non_blocking):
-            for d, s in zip((st.dev.masks, st.dev.seg_offset, st.dev.value_base, st.dev.values), (h.masks, h.seg_offset, h.value_base, h.values)):
-                d.copy_(s, non_blocking=non_blocking)
+            for k in per_frame + bases + run_arrays:
+                getattr(st.dev, k).copy_(getattr(h, k), non_blocking=non_blocking)
         self._on_side_stream(st, fill)
         return st, local
 
@@ -538,7 +558,8 @@ class BatchLoader:
 
         def fill(non_blocking):
             if n:
-                st.table_dev[:n * fc.GATHER_COLS].copy_(st.table_host[:n * fc.GATHER_COLS], non_blocking=non_blocking)
+                cols = self.gatherer.cols
+                st.table_dev[:n * cols].copy_(st.table_host[:n * cols], non_blocking=non_blocking)
                 self.gatherer.launch(st.table_dev, n, st.dev, self.gather_blocks)
         self._on_side_stream(st, fill)
         return st, local
